@@ -19,13 +19,6 @@ rank places its own `--queries` samples); `--strong` shards a fixed total of
 `--queries` samples (BASELINE config 4: `--strong --queries 1000000`).
 Rank 0 prints ONE JSON line.
 """
-import os as _os
-# A process has four hardware queues by default (ROCm: GPU_MAX_HW_QUEUES), and streams that share one run their work one after the other.
-# The handle's three streams and the caller's use them up; with N > 1 the RCCL stream of torch.distributed is a fifth, and which two then
-# share a queue is the runtime's choice (DESIGN.md 4 "A side stream", tools/probe_context.py: a fifth stream cost a third of the rate).
-# Eight queues for every N, so that the N = 1 and N > 1 lines are measured under the same setting (at N = 1 it changes nothing: 13.4 M/s
-# either way, profiles/r06_sweep_hwq.txt).  Read by the HIP runtime when it initialises: set before torch is imported; a caller's value wins.
-_os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import argparse
 import glob
 import re
@@ -63,10 +56,36 @@ def parse_args():
     ap.add_argument("--no-overlap", action="store_true", help="time the stream-ordered ugp_place_device (one call at a time) instead of ugp_place_device_overlapped")
     ap.add_argument("--no-extra", action="store_true", help="skip the extra keys (BASELINE configs 3 and 4 on one device, the end-to-end CLI run)")
     ap.add_argument("--depth", type=int, default=0, help="overlapped calls kept on the device at a time (2..4; 0 = the library's default)")
-    ap.add_argument("--repeats", type=int, default=3, help="windows of --steps steps timed in all (`value` is the MEDIAN window; min / max are extra keys)")
-    ap.add_argument("--dump-gathered", default="", help="test hook: rank 0 writes the records gathered by the first window's last step (all ranks' shards, padded) to this .npz")
+    ap.add_argument("--repeats", type=int, default=1, help="windows the --steps timed steps are split into (`value` is the MEDIAN window; min / max are extra keys)")
+    ap.add_argument("--dump-gathered", default="", help="test hook: rank 0 writes the records gathered by the last timed step (all ranks' shards, padded) to this .npz")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="rank 0 writes the placements of the last timed step (all ranks') as DIR/<name>.npy, float64")
     ap.add_argument("--qsets", type=int, default=4, help="distinct uploaded query sets the timed loop rotates through (no step places the samples of the step before it)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+RESULT_FIELDS = ("best_set_difference", "num_best", "best_j", "best_has_unique")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, records):
+    """The placements a caller of the timed path receives, one float64 array per field as out_dir/<field>.npy.  `records`: an (n, 4)
+    int32 array or the structured array of usher_amd.dist (every value fits float64 exactly).  Above DUMP_MAX_BYTES in all, a fixed
+    seeded sample of the rows is written, its row numbers in out_dir/row_index.npy."""
+    cols = [np.asarray(records[f] if records.dtype.names else records[:, i]) for i, f in enumerate(RESULT_FIELDS)]
+    n = len(cols[0])
+    idx = None
+    if n * 8 * len(cols) > DUMP_MAX_BYTES:
+        keep = (DUMP_MAX_BYTES - 4096) // (8 * (len(cols) + 1))   # (4 KiB for the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        cols = [c[idx] for c in cols]
+    os.makedirs(out_dir, exist_ok=True)
+    for f, c in zip(RESULT_FIELDS, cols):
+        np.save(os.path.join(out_dir, f + ".npy"), c.astype(np.float64))
+    if idx is not None:
+        np.save(os.path.join(out_dir, "row_index.npy"), idx.astype(np.float64))
 
 
 def self_launch(args) -> int:
@@ -390,31 +409,42 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     pl.timing_sum()   # (reset the library's running totals: the timed region starts here)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()   # no synchronisation between steps: consecutive ugp_place_device calls overlap on the device
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
+    # exactly --steps timed steps, split into --repeats windows (no synchronisation between the steps of a window: consecutive
+    # ugp_place_device calls overlap on the device); `value` is the MEDIAN window's rate, min / max beside it
+    n_win = max(1, min(args.repeats, args.steps))
+    win_steps = [args.steps // n_win + (1 if i < args.steps % n_win else 0) for i in range(n_win)]
+    windows = []
+    for ks in win_steps:
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        tw = time.perf_counter()
+        for _ in range(ks):
+            step()
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        tw = time.perf_counter() - tw
+        if world > 1:
+            tt = torch.tensor([tw], dtype=torch.float64, device="cpu" if share else dev)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            tw = float(tt.item())
+        windows.append(tw / ks)   # (seconds per step)
     last_out = outs[(n_step[0] - 1) % depth]
     last_set = (n_step[0] - 1) % n_sets
     res_last = last_out.cpu().numpy()[:Q].copy()   # (results of the timed region's last step: query set `last_set`)
     if args.dump_gathered and rank == 0:   # (tests/test_multi_gpu.py checks every rank's shard of this against the closed form)
         g = (gathered if world > 1 else last_out).cpu().numpy()
         np.savez(args.dump_gathered, records=g, cap=cap, world=world, last_set=last_set, total=total_q, seed=args.seed, strong=int(args.strong))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sp.unpad(gathered, total_q, cap) if world > 1 else res_last)
     # HIP events recorded by the library on the streams its kernels ran on, summed over the timed steps
     tm = pl.timing_sum()
     assert tm["calls"] == args.steps, tm
-    scale = args.steps / max(1, tm["calls"])
-    place_ms, table_ms, merge_ms, coarse_ms = tm["place_ms"] * scale, tm["table_ms"] * scale, tm["merge_ms"] * scale, tm["coarse_ms"] * scale
+    place_ms, table_ms, merge_ms, coarse_ms = tm["place_ms"], tm["table_ms"], tm["merge_ms"], tm["coarse_ms"]
     tiles, groups, packed = tm["n_tiles"], tm["n_groups"], tm["packed_path"]
     skipped, wtotal, nskips = tm["words_skipped"], tm["words_total"], tm["reserved"]
-    if world > 1:
-        tt = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if share else dev)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed = float(tt.item())
 
     # per-rank set-up times and the all-gather on its own (N > 1): what the ranks cost each other outside the kernels
     flat_all, gather_ms = [round(t_flat, 3)], None
@@ -429,25 +459,6 @@ def main():
             dist.all_gather_into_tensor(gathered, last_out.cpu() if share else last_out)
         torch.cuda.synchronize()
         gather_ms = round((time.perf_counter() - tg) * 1e3 / 5, 4)
-    # the same window again (--repeats - 1 times); `value` is the MEDIAN window, min / max beside it
-    windows = [elapsed]
-    for _ in range(max(0, args.repeats - 1)):
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        tw = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        torch.cuda.synchronize()
-        tw = time.perf_counter() - tw
-        if world > 1:
-            tt = torch.tensor([tw], dtype=torch.float64, device="cpu" if share else dev)
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            tw = float(tt.item())
-        windows.append(tw)
     pl.timing_sum()
     out = outs[0]
     # every query set once through the stream-ordered entry point: set 0's results are what the host-buffer path and the CPU baseline
@@ -656,10 +667,10 @@ def main():
 
     result = None
     if rank == 0:
-        # `value` = the MEDIAN of the --repeats windows of K steps each (the first window is `windows.ms_per_step[0]`)
+        # `value` = the rate of the MEDIAN of the --repeats windows the K timed steps were split into (`windows` holds seconds per step)
         w_med = sorted(windows)[len(windows) // 2]
-        ms_per_step = w_med * 1e3 / args.steps
-        value = total_q * args.steps / w_med
+        ms_per_step = w_med * 1e3
+        value = total_q / w_med
         # roofline of the dominant kernel: algorithmic bytes per launch, SURVEY 8(d):
         # every T-sample tile makes one pass over the tree: B_tree + T * (L/2 + 16); T = 512 on the packed path
         T = 512 if packed else 64
@@ -777,11 +788,11 @@ def main():
                        "parallelism": "queries sharded x%d, MAT replicated, RCCL all-gather of results" % world,
                        "rccl_ranks": world, "devices_visible": torch.cuda.device_count(),
                        "seed": args.seed, "gen_s": round(t_gen, 2), "flatten_upload_s": round(t_flat, 2)},
-            # the K-step window --repeats times in all: `value` is the median window
-            "windows": {"n": len(windows), "value_is": "median window", "ms_per_step": [round(w * 1e3 / args.steps, 3) for w in windows],
-                        "value_first_window": round(total_q * args.steps / windows[0], 2),
-                        "value_min": round(total_q * args.steps / max(windows), 2), "value_median": round(total_q * args.steps / sorted(windows)[len(windows) // 2], 2),
-                        "value_max": round(total_q * args.steps / min(windows), 2)},
+            # the K timed steps in --repeats windows: `value` is the median window
+            "windows": {"n": len(windows), "steps": win_steps, "value_is": "median window", "ms_per_step": [round(w * 1e3, 3) for w in windows],
+                        "value_first_window": round(total_q / windows[0], 2),
+                        "value_min": round(total_q / max(windows), 2), "value_median": round(total_q / sorted(windows)[len(windows) // 2], 2),
+                        "value_max": round(total_q / min(windows), 2)},
             # SURVEY 8(d) defines the metric with query upload and result download inside the clock: this is that figure (two
             # batches in flight from and to host buffers), next to `value` (rows resident in HBM, as the bench contract asks)
             "value_pcie_inclusive": (host_path or {}).get("two_in_flight", {}).get("placements_per_s") if host_path and host_path.get("two_in_flight") else None,
