@@ -209,6 +209,21 @@ int ugp_ex_prepare(ugp_mat *mat, const ugp_place_opts *opts, ugp_ex **out);
 void ugp_ex_destroy(ugp_ex *ex);
 int ugp_place_batch_prepared(ugp_mat *mat, const ugp_queries *q, const ugp_ex *ex, const uint32_t *skip_node, ugp_result *out /* [n_queries], host */,
                              int32_t *d_scores /* device, or NULL */);
+/* matUtils uncertainty (uncertainty.cpp:132-339): for each node S of `nodes` (breadth-first indices) the search findEPPs runs --
+ * the sample is S's root path in the reference's LITERAL order (S's own mutations, then each ancestor's, most recent per position,
+ * masked entries kept, not sorted), every node but S is scored in the depth-first expansion, the initial best is |Q| + |root
+ * mutations| + 1 with best_j_vec = {0} -- and its results:
+ *   epps[i]      = num_best (equally parsimonious placements); 0 when Q(S) is empty (the reference skips the search and prints
+ *                  uninitialised values there, uncertainty.cpp:167, 326-333);
+ *   tie_count[i] = the true size of the tie set (= epps[i]); tie_dfs[i * cap ..] its first min(cap, tie_count[i]) depth-first
+ *                  positions, ascending (the reference appends in TBB's order; a serial run's order is fixed here);
+ *   nsize[i]     = get_neighborhood_size (:41-130) over the WHOLE tie set when num_best > 1, else 0 -- never depends on cap.
+ * Every pair is scored (dense; exact for the literal row order, which ugp_place_batch_ex cannot take).  The tables come from
+ * ugp_uncertainty_attach, once per handle: `tree` must be the tree the handle was created from (same parent array; the arrays
+ * are copied and may be freed).  A tree with two non-masked mutations at one position on one branch is UGP_ERR_UNSUPPORTED. */
+int ugp_uncertainty_attach(ugp_mat *mat, const ugp_tree_desc *tree);
+int ugp_uncertainty(ugp_mat *mat, const uint32_t *nodes /* BFS */, uint64_t n, uint32_t cap, uint32_t *epps, uint32_t *nsize,
+                    uint32_t *tie_dfs /* [n * cap] */, uint32_t *tie_count);
 /* bfs_of[k] = breadth-first index of the node at position k of `order` (how a caller maps its own node vector). */
 int ugp_node_order(ugp_mat *mat, uint32_t order, uint32_t *bfs_of /* [n_nodes] */);
 /* mask_out[k] = 1 for the nodes of the subtree of root_j that lie at most max_levels below it (merge.cpp:253-256). */

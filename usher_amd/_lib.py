@@ -73,6 +73,8 @@ SYMBOLS = {
     "ugp_place_batch_prepared": (C.c_int, [P, C.POINTER(ugp_queries), P, P, P, P]),
     "ugp_device_warmup": (C.c_int, [C.c_int]),
     "ugp_node_order": (C.c_int, [P, C.c_uint32, P]),
+    "ugp_uncertainty_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc)]),
+    "ugp_uncertainty": (C.c_int, [P, P, C.c_uint64, C.c_uint32, P, P, P, P]),
     "ugp_subtree_mask": (C.c_int, [P, C.c_uint32, C.c_uint32, C.c_uint32, P]),
     "ugp_qset_upload": (C.c_int, [P, C.POINTER(ugp_queries), C.POINTER(P)]),
     "ugp_qset_destroy": (None, [P]),

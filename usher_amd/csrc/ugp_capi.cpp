@@ -23,6 +23,7 @@
 #include "ugp_flatten.hpp"
 #include "ugp_kernels.hpp"
 #include "ugp_knobs.hpp"
+#include "ugp_uncertainty.hpp"
 #include "ugp_update.hpp"
 #include "usher_amd.h"
 
@@ -284,6 +285,7 @@ struct ugp_mat {
         PinBuf stage_up;   // ugp_mat_update: records, entries and word positions in one staging buffer
         PinBuf stage;   // ugp_touched_fetch: the four result arrays cross in one go (asynchronous copies into pinned memory, one wait)
     } upd;
+    ugp::UncState *unc = nullptr;    // matUtils uncertainty tables (ugp_uncertainty_attach), or none
     hipEvent_t kb_done = nullptr;    // behind the latest k_best8 launch of this handle ...
     hipStream_t kb_done_on = nullptr;   // ... on this stream
 };
@@ -1292,6 +1294,7 @@ void ugp_mat_destroy(ugp_mat *m) {
     if (m->kb_done) (void)hipEventDestroy(m->kb_done);
     if (m->coarse) ugp_mat_destroy(m->coarse);
     delete m->own_qs;
+    ugp::unc_free(m->unc);
     delete m;
 }
 
@@ -1706,6 +1709,25 @@ int ugp_subtree_mask(ugp_mat *m, uint32_t order, uint32_t root_j, uint32_t max_l
         }
     } catch (const std::bad_alloc &) { return fail(UGP_ERR_NOMEM, "out of host memory"); }
     return UGP_OK;
+}
+
+// ---- matUtils uncertainty (ugp_uncertainty.hip) ----------------------------------------------------------------------
+
+int ugp_uncertainty_attach(ugp_mat *m, const ugp_tree_desc *tree) {
+    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
+    const uint64_t N = m->flat.n_nodes;
+    if (m->h_parent.size() != N) return fail(UGP_ERR_INVALID, "this handle has no host topology (created from a coarse tree?)");
+    if (tree->n_nodes != N) return fail(UGP_ERR_INVALID, "the tree is not the handle's tree (node count)");
+    for (uint64_t j = 1; j < N; j++)
+        if (tree->parent[j] != m->h_parent[j]) return fail(UGP_ERR_INVALID, "the tree is not the handle's tree (parent array)");
+    try { ensure_dfs_order(m); } catch (const std::bad_alloc &) { return fail(UGP_ERR_NOMEM, "out of host memory"); }
+    return ugp::unc_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->unc);
+}
+
+int ugp_uncertainty(ugp_mat *m, const uint32_t *nodes, uint64_t n, uint32_t cap, uint32_t *epps, uint32_t *nsize, uint32_t *tie_dfs,
+                    uint32_t *tie_count) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::unc_run(m->unc, nodes, n, cap, epps, nsize, tie_dfs, tie_count);
 }
 
 namespace {

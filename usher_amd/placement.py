@@ -266,6 +266,20 @@ class Placer:
         self._ck(self._L.ugp_place_batch_prepared(self._h, C.byref(batch.desc), ex, None if sk is None else _ptr(sk), _ptr(out), C.c_void_p(d_scores) if d_scores else None))
         return out
 
+    def uncertainty(self, nodes, cap: int = 64):
+        """matUtils uncertainty (ugp_uncertainty) for tree nodes given by BFS index: (epps, neighborhood_size, ties, tie_count),
+        ties[i] = the first min(cap, tie_count[i]) tied nodes as depth-first positions, ascending.  The tables are made on
+        the first call (ugp_uncertainty_attach) from the arrays this Placer was built from."""
+        if not getattr(self, "_unc_ready", False):
+            self._ck(self._L.ugp_uncertainty_attach(self._h, C.byref(self._t.desc)))
+            self._unc_ready = True
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
+        n = len(nodes)
+        epps = np.zeros(n, np.uint32); nsize = np.zeros(n, np.uint32); cnt = np.zeros(n, np.uint32)
+        ties = np.zeros((n, cap), np.uint32)
+        self._ck(self._L.ugp_uncertainty(self._h, _ptr(nodes), n, int(cap), _ptr(epps), _ptr(nsize), _ptr(ties), _ptr(cnt)))
+        return epps, nsize, [ties[i, :min(int(cnt[i]), cap)].copy() for i in range(n)], cnt
+
     def node_order(self, order: str) -> np.ndarray:
         out = np.zeros(self.n_nodes, dtype=np.uint32)
         self._ck(self._L.ugp_node_order(self._h, {"bfs": 0, "dfs": 1}[order], _ptr(out)))
