@@ -224,6 +224,37 @@ int ugp_place_batch_prepared(ugp_mat *mat, const ugp_queries *q, const ugp_ex *e
 int ugp_uncertainty_attach(ugp_mat *mat, const ugp_tree_desc *tree);
 int ugp_uncertainty(ugp_mat *mat, const uint32_t *nodes /* BFS */, uint64_t n, uint32_t cap, uint32_t *epps, uint32_t *nsize,
                     uint32_t *tie_dfs /* [n * cap] */, uint32_t *tie_count);
+/* RIPPLES (ripples/main.cpp): the options of :22-44 that the search reads.  branch_len >= 1 and parsimony_improvement >= 0
+ * (UGP_ERR_INVALID otherwise: the reference's size_t arithmetic of :445-453 is not reproduced for negative values). */
+typedef struct ugp_ripples_opts {
+    uint32_t branch_len;              /* -l: rows on each side of a breakpoint pair                         */
+    int32_t min_range, max_range;     /* -r / -R: bounds of pos[j-1] - pos[i]                               */
+    int32_t parsimony_improvement;    /* -p                                                                 */
+    uint32_t num_descendants;         /* -n: candidate nodes have >= n nodes in their subtree (:280-289)    */
+} ugp_ripples_opts;
+/* One selected breakpoint pair of one branch, before the interval refinement of :608-666. */
+typedef struct ugp_ripples_event {
+    uint64_t branch;                  /* index into branches[]                                              */
+    uint32_t i, j;                    /* the donor takes rows [i, j) of the branch's pruned sample          */
+    uint32_t donor, acceptor;         /* BFS indices                                                        */
+    uint32_t donor_count, acceptor_count;   /* Recomb_Node::parsimony: unmatched mutations in / out of range */
+    int32_t donor_score, acceptor_score;    /* Recomb_Node::node_parsimony: pass-1 node_set_difference       */
+    uint8_t donor_sibling, acceptor_sibling;   /* Recomb_Node::is_sibling ('y' = 1)                         */
+    uint8_t pad[6];
+} ugp_ripples_event;
+/* Replaces main.cpp:280-289 (tree_num_leaves) and the per-branch setup: tables of `tree` (the handle's tree: same parent array)
+ * and name_rank[k] = the rank of node k's identifier in std::string order (a permutation of 0 .. n-1; the donor / acceptor lists
+ * sort by (count, name)).  Arrays are copied.  Two non-masked mutations at one position on one branch: UGP_ERR_UNSUPPORTED. */
+int ugp_ripples_attach(ugp_mat *mat, const ugp_tree_desc *tree, const uint32_t *name_rank);
+/* Replaces main.cpp:300-680 up to the refinement, for each branch of `branches` (BFS, any order, repeats allowed): the pruned
+ * sample of the branch's root path (:68-90, :317-325), pass 1 (:343-377: mapper2_body(inp, true) over every node with
+ * >= num_descendants subtree nodes), the unmatched-mutation filter and both node passes of every breakpoint pair (:383-575),
+ * the sort / 1000-truncation and the donor-acceptor choice (:577-606).  Events come out in branch order, then pair order (i, then
+ * j ascending), at most one per pair; out[0 .. min(cap, *n_out)) is written and *n_out is the true count.  is_sibling: the
+ * reference sets node_has_unique only for nodes that tied or beat the running best, which depends on TBB's schedule; here
+ * exactly the final ties carry their has_unique (a leaf always reads 1). */
+int ugp_ripples(ugp_mat *mat, const ugp_ripples_opts *opts, const uint32_t *branches /* BFS */, uint64_t n, ugp_ripples_event *out,
+                uint64_t cap, uint64_t *n_out);
 /* bfs_of[k] = breadth-first index of the node at position k of `order` (how a caller maps its own node vector). */
 int ugp_node_order(ugp_mat *mat, uint32_t order, uint32_t *bfs_of /* [n_nodes] */);
 /* mask_out[k] = 1 for the nodes of the subtree of root_j that lie at most max_levels below it (merge.cpp:253-256). */

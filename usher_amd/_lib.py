@@ -18,6 +18,11 @@ class ugp_tree_desc(C.Structure):
                 ("mut_ref", C.c_void_p), ("mut_par", C.c_void_p), ("mut_nuc", C.c_void_p)]
 
 
+class ugp_ripples_opts(C.Structure):
+    _fields_ = [("branch_len", C.c_uint32), ("min_range", C.c_int32), ("max_range", C.c_int32),
+                ("parsimony_improvement", C.c_int32), ("num_descendants", C.c_uint32)]
+
+
 class ugp_queries(C.Structure):
     _fields_ = [("n_queries", C.c_uint64), ("ent_off", C.c_void_p), ("pos", C.c_void_p), ("ref", C.c_void_p),
                 ("nuc", C.c_void_p), ("is_missing", C.c_void_p)]
@@ -75,6 +80,8 @@ SYMBOLS = {
     "ugp_node_order": (C.c_int, [P, C.c_uint32, P]),
     "ugp_uncertainty_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc)]),
     "ugp_uncertainty": (C.c_int, [P, P, C.c_uint64, C.c_uint32, P, P, P, P]),
+    "ugp_ripples_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc), P]),
+    "ugp_ripples": (C.c_int, [P, C.POINTER(ugp_ripples_opts), P, C.c_uint64, P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ugp_subtree_mask": (C.c_int, [P, C.c_uint32, C.c_uint32, C.c_uint32, P]),
     "ugp_qset_upload": (C.c_int, [P, C.POINTER(ugp_queries), C.POINTER(P)]),
     "ugp_qset_destroy": (None, [P]),

@@ -23,6 +23,7 @@
 #include "ugp_flatten.hpp"
 #include "ugp_kernels.hpp"
 #include "ugp_knobs.hpp"
+#include "ugp_ripples.hpp"
 #include "ugp_uncertainty.hpp"
 #include "ugp_update.hpp"
 #include "usher_amd.h"
@@ -286,6 +287,7 @@ struct ugp_mat {
         PinBuf stage;   // ugp_touched_fetch: the four result arrays cross in one go (asynchronous copies into pinned memory, one wait)
     } upd;
     ugp::UncState *unc = nullptr;    // matUtils uncertainty tables (ugp_uncertainty_attach), or none
+    ugp::RipState *rip = nullptr;    // RIPPLES tables (ugp_ripples_attach), or none
     hipEvent_t kb_done = nullptr;    // behind the latest k_best8 launch of this handle ...
     hipStream_t kb_done_on = nullptr;   // ... on this stream
 };
@@ -1295,6 +1297,7 @@ void ugp_mat_destroy(ugp_mat *m) {
     if (m->coarse) ugp_mat_destroy(m->coarse);
     delete m->own_qs;
     ugp::unc_free(m->unc);
+    ugp::rip_free(m->rip);
     delete m;
 }
 
@@ -1728,6 +1731,24 @@ int ugp_uncertainty(ugp_mat *m, const uint32_t *nodes, uint64_t n, uint32_t cap,
                     uint32_t *tie_count) {
     if (!m) return fail(UGP_ERR_INVALID, "null argument");
     return ugp::unc_run(m->unc, nodes, n, cap, epps, nsize, tie_dfs, tie_count);
+}
+
+// ---- RIPPLES (ugp_ripples.hip) -----------------------------------------------------------------------------------------
+
+int ugp_ripples_attach(ugp_mat *m, const ugp_tree_desc *tree, const uint32_t *name_rank) {
+    if (!m || !tree || !tree->parent || !name_rank) return fail(UGP_ERR_INVALID, "null argument");
+    const uint64_t N = m->flat.n_nodes;
+    if (m->h_parent.size() != N) return fail(UGP_ERR_INVALID, "this handle has no host topology (created from a coarse tree?)");
+    if (tree->n_nodes != N) return fail(UGP_ERR_INVALID, "the tree is not the handle's tree (node count)");
+    for (uint64_t j = 1; j < N; j++)
+        if (tree->parent[j] != m->h_parent[j]) return fail(UGP_ERR_INVALID, "the tree is not the handle's tree (parent array)");
+    return ugp::rip_attach(tree, name_rank, m->device, &m->rip);
+}
+
+int ugp_ripples(ugp_mat *m, const ugp_ripples_opts *opts, const uint32_t *branches, uint64_t n, ugp_ripples_event *out, uint64_t cap,
+                uint64_t *n_out) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::rip_run(m->rip, opts, branches, n, out, cap, n_out);
 }
 
 namespace {

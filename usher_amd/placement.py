@@ -280,6 +280,31 @@ class Placer:
         self._ck(self._L.ugp_uncertainty(self._h, _ptr(nodes), n, int(cap), _ptr(epps), _ptr(nsize), _ptr(ties), _ptr(cnt)))
         return epps, nsize, [ties[i, :min(int(cnt[i]), cap)].copy() for i in range(n)], cnt
 
+    RIPPLES_EVENT = np.dtype([("branch", np.uint64), ("i", np.uint32), ("j", np.uint32), ("donor", np.uint32), ("acceptor", np.uint32),
+                              ("donor_count", np.uint32), ("acceptor_count", np.uint32), ("donor_score", np.int32),
+                              ("acceptor_score", np.int32), ("donor_sibling", np.uint8), ("acceptor_sibling", np.uint8),
+                              ("pad", np.uint8, 6)])
+
+    def ripples(self, branches, name_rank, branch_len: int = 3, min_range: int = 1000, max_range: int = 10 ** 7,
+                parsimony_improvement: int = 3, num_descendants: int = 10) -> np.ndarray:
+        """RIPPLES' search (ugp_ripples, ripples/main.cpp:300-680 up to the interval refinement) for the branches given by BFS
+        index: a structured array of raw events (RIPPLES_EVENT), in branch order, then pair order.  name_rank[k] = the rank of
+        node k's name in byte order; the tables are made on the first call (ugp_ripples_attach) and kept for the same ranks."""
+        rank = np.ascontiguousarray(name_rank, dtype=np.uint32)
+        if getattr(self, "_rip_rank", None) is None or not np.array_equal(self._rip_rank, rank):
+            self._ck(self._L.ugp_ripples_attach(self._h, C.byref(self._t.desc), _ptr(rank)))
+            self._rip_rank = rank.copy()
+        br = np.ascontiguousarray(branches, dtype=np.uint32)
+        opts = _lib.ugp_ripples_opts(int(branch_len), int(min_range), int(max_range), int(parsimony_improvement), int(num_descendants))
+        n_out = C.c_uint64(0)
+        cap = max(16, 4 * len(br))
+        while True:
+            out = np.zeros(cap, self.RIPPLES_EVENT)
+            self._ck(self._L.ugp_ripples(self._h, C.byref(opts), _ptr(br), len(br), _ptr(out), cap, C.byref(n_out)))
+            if n_out.value <= cap:
+                return out[:n_out.value]
+            cap = int(n_out.value)
+
     def node_order(self, order: str) -> np.ndarray:
         out = np.zeros(self.n_nodes, dtype=np.uint32)
         self._ck(self._L.ugp_node_order(self._h, {"bfs": 0, "dfs": 1}[order], _ptr(out)))
