@@ -18,6 +18,14 @@ replicated, results are all-gathered over RCCL.  Default is weak scaling (each
 rank places its own `--queries` samples); `--strong` shards a fixed total of
 `--queries` samples (BASELINE config 4: `--strong --queries 1000000`).
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, the warm-up and timed
+steps, `--dump-outputs` / `--dump-gathered`, and a line with `value`,
+`ms_per_step`, the timed windows and the configuration.  `--full` adds
+everything else the line has carried: the rotation check, the kernels alone
+and the roofline, the host-buffer path, the per-rank all-gather, the CPU
+baseline and `other_configs` (the last two still subject to `--cpu-queries` /
+`--no-extra`).
 """
 import argparse
 import glob
@@ -50,11 +58,13 @@ def parse_args():
                     help="tree shape: random attachment (SURVEY 8d recipe) or SARS-CoV-2-like (shallow, polytomy-dominated)")
     ap.add_argument("--iupac-true", action="store_true", help="with --ambiguous: every IUPAC cell holds the sample's own base (default: any set of 2-3 bases)")
     ap.add_argument("--ambiguous", action="store_true", help="BASELINE config 5: 100-5000 N cells + 0-30 IUPAC cells per query")
-    ap.add_argument("--cpu-queries", type=int, default=-1, help="queries timed on the CPU oracle (0 = skip; default: sized for ~10-30 s)")
+    ap.add_argument("--full", action="store_true", help="besides the headline, every other figure and check: rotation check, kernels alone, roofline, "
+                                                        "host-buffer path, all-gather, CPU baseline, other configurations")
+    ap.add_argument("--cpu-queries", type=int, default=-1, help="with --full: queries timed on the CPU oracle (0 = skip; default: sized for ~10-30 s)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--sort-by-source", action="store_true", help="experiment: hand the queries over already ordered by their generator source node")
     ap.add_argument("--no-overlap", action="store_true", help="time the stream-ordered ugp_place_device (one call at a time) instead of ugp_place_device_overlapped")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra keys (BASELINE configs 3 and 4 on one device, the end-to-end CLI run)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra keys (BASELINE configs 3 and 4 on one device, the end-to-end CLI run)")
     ap.add_argument("--depth", type=int, default=0, help="overlapped calls kept on the device at a time (2..4; 0 = the library's default)")
     ap.add_argument("--repeats", type=int, default=1, help="windows the --steps timed steps are split into (`value` is the MEDIAN window; min / max are extra keys)")
     ap.add_argument("--dump-gathered", default="", help="test hook: rank 0 writes the records gathered by the last timed step (all ranks' shards, padded) to this .npz")
@@ -446,6 +456,45 @@ def main():
     tiles, groups, packed = tm["n_tiles"], tm["n_groups"], tm["packed_path"]
     skipped, wtotal, nskips = tm["words_skipped"], tm["words_total"], tm["reserved"]
 
+    def headline_result(rotation_exact=None):
+        """The keys of rank 0's line that a plain run reports: the timed steps' rate and what they ran on."""
+        # `value` = the rate of the MEDIAN of the --repeats windows the K timed steps were split into (`windows` holds seconds per step)
+        w_med = sorted(windows)[len(windows) // 2]
+        T = 512 if packed else 64
+        return {
+            "metric": "sample placements/sec on 10M-node MAT; bit-exact parsimony score vs reference",
+            "value": round(total_q / w_med, 2), "unit": "placements/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(w_med * 1e3, 3), "higher_is_better": True, "scaling": "strong" if args.strong else "weak", "vs_baseline": None,
+            "dtype": "u16 packed (4-bit allele sets, 4-bit SWAR node counters, 16-bit D/cost)" if packed else "u32 (4-bit allele sets, int32 counters)", "data": "synthetic",
+            "config": {"workload": "synthetic %s MAT %d nodes / %d mutations / %d variable sites, L=%d; %s%s"
+                                   % (args.shape, info["n_nodes"], info["n_muts"], info["n_sites"], args.genome,
+                                      ("%d queries in total, sharded" % total_q) if args.strong else ("%d queries per GPU per step" % Q),
+                                      (" (100-5000 N + 0-30 IUPAC cells each%s)" % (", every code holding the sample's own base" if args.iupac_true else "")) if args.ambiguous else ""),
+                       "nodes": int(info["n_nodes"]), "queries_per_gpu": Q, "queries_total": total_q, "tile": T, "tiles": tiles, "waves_per_tile": groups,
+                       "query_sets_rotated": n_sets, **({"last_step_equals_stream_ordered_call": rotation_exact} if args.full else {}),
+                       "parallelism": "queries sharded x%d, MAT replicated, RCCL all-gather of results" % world,
+                       "rccl_ranks": world, "devices_visible": torch.cuda.device_count(),
+                       "seed": args.seed, "gen_s": round(t_gen, 2), "flatten_upload_s": round(t_flat, 2)},
+            # the K timed steps in --repeats windows: `value` is the median window
+            "windows": {"n": len(windows), "steps": win_steps, "value_is": "median window", "ms_per_step": [round(w * 1e3, 3) for w in windows],
+                        "value_first_window": round(total_q / windows[0], 2),
+                        "value_min": round(total_q / max(windows), 2), "value_median": round(total_q / w_med, 2),
+                        "value_max": round(total_q / min(windows), 2)},
+        }
+
+    if not args.full:
+        # a plain run ends here: nothing is measured or checked beyond the timed steps (all of that: --full)
+        result = headline_result() if rank == 0 else None
+        for h in qsets:
+            pl.free_qset(h)
+        pl.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(result))
+        return
+
     # per-rank set-up times and the all-gather on its own (N > 1): what the ranks cost each other outside the kernels
     flat_all, gather_ms = [round(t_flat, 3)], None
     if world > 1:
@@ -667,10 +716,7 @@ def main():
 
     result = None
     if rank == 0:
-        # `value` = the rate of the MEDIAN of the --repeats windows the K timed steps were split into (`windows` holds seconds per step)
-        w_med = sorted(windows)[len(windows) // 2]
-        ms_per_step = w_med * 1e3
-        value = total_q / w_med
+        ms_per_step = sorted(windows)[len(windows) // 2] * 1e3   # (the median window's, as in the headline)
         # roofline of the dominant kernel: algorithmic bytes per launch, SURVEY 8(d):
         # every T-sample tile makes one pass over the tree: B_tree + T * (L/2 + 16); T = 512 on the packed path
         T = 512 if packed else 64
@@ -774,25 +820,8 @@ def main():
                    "calibration": {"reference_1thread_scaled": round(12.8 * 44483.0 / info["n_nodes"], 5), "port_over_reference": round((1.0 / dt1) / (12.8 * 44483.0 / info["n_nodes"]), 3),
                                    "basis": "BASELINE.md: 12.8 placements/s/thread at 44,483 nodes, scaled by 44,483 / N"},
                    "mismatches_vs_gpu": bad}
-        result = {
-            "metric": "sample placements/sec on 10M-node MAT; bit-exact parsimony score vs reference",
-            "value": round(value, 2), "unit": "placements/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong" if args.strong else "weak", "vs_baseline": None,
-            "dtype": "u16 packed (4-bit allele sets, 4-bit SWAR node counters, 16-bit D/cost)" if packed else "u32 (4-bit allele sets, int32 counters)", "data": "synthetic",
-            "config": {"workload": "synthetic %s MAT %d nodes / %d mutations / %d variable sites, L=%d; %s%s"
-                                   % (args.shape, info["n_nodes"], info["n_muts"], info["n_sites"], args.genome,
-                                      ("%d queries in total, sharded" % total_q) if args.strong else ("%d queries per GPU per step" % Q),
-                                      (" (100-5000 N + 0-30 IUPAC cells each%s)" % (", every code holding the sample's own base" if args.iupac_true else "")) if args.ambiguous else ""),
-                       "nodes": int(info["n_nodes"]), "queries_per_gpu": Q, "queries_total": total_q, "tile": T, "tiles": tiles, "waves_per_tile": groups,
-                       "query_sets_rotated": n_sets, "last_step_equals_stream_ordered_call": rotation_exact,
-                       "parallelism": "queries sharded x%d, MAT replicated, RCCL all-gather of results" % world,
-                       "rccl_ranks": world, "devices_visible": torch.cuda.device_count(),
-                       "seed": args.seed, "gen_s": round(t_gen, 2), "flatten_upload_s": round(t_flat, 2)},
-            # the K timed steps in --repeats windows: `value` is the median window
-            "windows": {"n": len(windows), "steps": win_steps, "value_is": "median window", "ms_per_step": [round(w * 1e3, 3) for w in windows],
-                        "value_first_window": round(total_q / windows[0], 2),
-                        "value_min": round(total_q / max(windows), 2), "value_median": round(total_q / sorted(windows)[len(windows) // 2], 2),
-                        "value_max": round(total_q / min(windows), 2)},
+        result = headline_result(rotation_exact)
+        result.update({
             # SURVEY 8(d) defines the metric with query upload and result download inside the clock: this is that figure (two
             # batches in flight from and to host buffers), next to `value` (rows resident in HBM, as the bench contract asks)
             "value_pcie_inclusive": (host_path or {}).get("two_in_flight", {}).get("placements_per_s") if host_path and host_path.get("two_in_flight") else None,
@@ -804,7 +833,7 @@ def main():
             # `value` has the query rows resident in HBM when the timed region starts (bench contract); the same batch through
             # the host-buffer entry point -- SURVEY 8(d)'s definition of the metric -- is this:
             "host_buffer_path": host_path,
-        }
+        })
     for h in qsets:
         pl.free_qset(h)
     pl.close()

@@ -103,14 +103,14 @@ def test_bench_multi_rank_flow_on_one_box(ranks, tmp_path):
     /dev/shm, shard the queries and print ONE JSON line with the aggregate.  On a box with fewer GPUs the BENCH_SHARE_DEVICE hook
     lets the ranks share the device(s) and gather through gloo -- the flow is what is tested, not the figure: 8 ranks as the
     driver's scaling run launches them, every rank flattening on its share of the host's cores (no rank's set-up far above the
-    others'), the all-gather timed on its own."""
+    others'), the all-gather timed on its own (`--full`: the keys beyond the headline)."""
     import json
     ranks = _ranks_on_this_box(ranks)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     if _n_devices() < ranks:
         env["BENCH_SHARE_DEVICE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--nodes", "300000", "--queries", "2400", "--steps", "2", "--warmup", "1",
-                        "--strong", "--repeats", "1"], capture_output=True, text=True, timeout=1800, env=env)
+                        "--strong", "--repeats", "1", "--full"], capture_output=True, text=True, timeout=1800, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

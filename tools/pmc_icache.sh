@@ -1,6 +1,6 @@
 #!/bin/bash
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-B="python3 bench.py --queries 16384 --steps 3 --warmup 1 --cpu-queries 0"
+B="python3 bench.py --full --queries 16384 --steps 3 --warmup 1 --cpu-queries 0"
 rm -rf gpurun_out/ic1 gpurun_out/ic2
 rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH -d gpurun_out/ic1 -o p --output-format csv -- $B > gpurun_out/ic1.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_WAIT_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_INSTS_SMEM SQ_INST_CYCLES_VMEM_RD SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA -d gpurun_out/ic2 -o p --output-format csv -- $B > gpurun_out/ic2.log 2>&1
