@@ -68,6 +68,12 @@ def merged_answer(flat_best, flat_ties, t_best, t_ties):
 @pytest.mark.parametrize("seed,n_leaves,n_new,chunk", [(5, 400, 60, 16), (6, 1500, 90, 64), (7, 120, 40, 8)])
 def test_flattened_tree_plus_records_equal_a_search_of_the_edited_tree(seed, n_leaves, n_new, chunk, monkeypatch):
     monkeypatch.setenv("UGP_COARSE_MIN_NODES", "0")     # the locality pre-pass and its coarse tree too (their nodes are excluded as well)
+    check_flattened_tree_plus_records(seed, n_leaves, n_new, chunk)
+
+
+def check_flattened_tree_plus_records(seed, n_leaves, n_new, chunk):
+    """The body of the test above, under UGP_COARSE_MIN_NODES=0 (also run in child processes by test_knobs_gpu.py: UGP_TOUCHED_RECS
+    is read once per process)."""
     arrays, queries = synth.make_case(seed, n_leaves=n_leaves, n_queries=n_new, n_sites=90, n_ambig=(0, 0, 1, 3), p_masked=0.01)
     T, flat_nodes = tree_from_arrays(arrays)
     flat_of = {id(n): j for j, n in enumerate(flat_nodes)}
