@@ -167,7 +167,7 @@ int ugp_tied_nodes(ugp_mat *mat, const ugp_queries *q, uint32_t cap,
 
 /* ---- the other callers of mapper2_body ------------------------------------------------------------------
  * matUtils uncertainty (uncertainty.cpp:212-235: every node but the sample's own, depth-first indices), annotate
- * (annotate.cpp:615-638: depth-first indices), merge (merge.cpp:253-280: the breadth-first expansion of a subtree, cut
+ * (annotate.cpp:615-638: depth-first indices; rows it cannot take: ugp_annotate_search), merge (merge.cpp:253-280: the breadth-first expansion of a subtree, cut
  * max_levels below its root) and ripples (ripples/main.cpp:343-377: nodes with enough descendants, a per-node
  * distance, per-node scores) run the same search over THEIR node vector: the index j they hand to mapper2_body --
  * which also breaks ties, usher_mapper.cpp:483-486 -- is a position in that vector.  These entry points take the
@@ -224,6 +224,30 @@ int ugp_place_batch_prepared(ugp_mat *mat, const ugp_queries *q, const ugp_ex *e
 int ugp_uncertainty_attach(ugp_mat *mat, const ugp_tree_desc *tree);
 int ugp_uncertainty(ugp_mat *mat, const uint32_t *nodes /* BFS */, uint64_t n, uint32_t cap, uint32_t *epps, uint32_t *nsize,
                     uint32_t *tie_dfs /* [n * cap] */, uint32_t *tie_count);
+/* matUtils annotate (annotate.cpp:301-419, 466-481, 611-638).  ugp_annotate_attach makes the depth-first tables of `tree` once per
+ * handle (the handle's tree: same parent array; arrays are copied).  Clades are CSR lists of exemplar nodes (BFS indices);
+ * an exemplar listed twice counts twice, as in the reference.
+ * ugp_clade_alleles: for each clade, every mutation entry (its index in tree->mut_off's CSR) that the reference's walk
+ *   rsearch(exemplar, true) adds (:355-390) -- the first non-masked entry of a position wins (later ones on the same node and
+ *   older ones above are skipped), masked entries always count, entries with ref == mut count nothing -- and how many of the
+ *   clade's exemplars add it.  Entries come per clade (out_off[c] .. out_off[c + 1]) in depth-first order of their node, then
+ *   stored order; only entries with a count > 0 are listed.  out_ent / out_cnt receive the first min(cap, *n_out) of them and
+ *   *n_out the true total; out_off [n_clades + 1] is always written.
+ * ugp_clade_descendants: out[i] = exemplars of clade pair_clade[i] strictly below node pair_node[i] (BFS): is_ancestor
+ *   (mutation_annotated_tree.cpp:920-929) starts at the parent, so a node is not its own descendant.
+ * ugp_annotate_search: annotate's search (:611-638) literally, for any rows -- repeated positions and masked (negative) positions
+ *   included, which ugp_place_batch_ex refuses: mapper2_body over every node of the depth-first expansion in the rows' stored
+ *   order, best = 1e9.  Per query: best[s] = the best score, tie_count[s] = the number of tied nodes, tie_dfs[s * cap ..] the
+ *   first min(cap, tie_count[s]) of them as depth-first positions, ascending.  Rows must have is_missing = 0 (UGP_ERR_INVALID);
+ *   a tree with two non-masked mutations at one position on one branch is UGP_ERR_UNSUPPORTED here.  Queries run one at a time:
+ *   when a later query fails its checks, the earlier queries' outputs are already written. */
+int ugp_annotate_attach(ugp_mat *mat, const ugp_tree_desc *tree);
+int ugp_clade_alleles(ugp_mat *mat, const uint64_t *clade_off /* [n_clades + 1] */, const uint32_t *nodes /* BFS */, uint64_t n_clades,
+                      uint64_t *out_off /* [n_clades + 1] */, uint32_t *out_ent, uint32_t *out_cnt, uint64_t cap, uint64_t *n_out);
+int ugp_clade_descendants(ugp_mat *mat, const uint64_t *clade_off, const uint32_t *nodes /* BFS */, uint64_t n_clades,
+                          const uint32_t *pair_clade, const uint32_t *pair_node /* BFS */, uint64_t n_pairs, uint32_t *out);
+int ugp_annotate_search(ugp_mat *mat, const ugp_queries *q, uint32_t cap, int32_t *best /* [n_queries] */, uint32_t *tie_dfs /* [n_queries * cap] */,
+                        uint32_t *tie_count /* [n_queries] */);
 /* RIPPLES (ripples/main.cpp): the options of :22-44 that the search reads.  branch_len >= 1 and parsimony_improvement >= 0
  * (UGP_ERR_INVALID otherwise: the reference's size_t arithmetic of :445-453 is not reproduced for negative values). */
 typedef struct ugp_ripples_opts {

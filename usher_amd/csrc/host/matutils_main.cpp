@@ -1,16 +1,26 @@
 // matutils_main.cpp -- `matutils-amd`: the matUtils subcommands this project runs on the GPU.
 //
 //   matutils-amd uncertainty -i tree.pb -s samples.txt [-e epps.tsv] [-o placements.tsv] [-T n] [--device k]
+//   matutils-amd annotate -i tree.pb -o out.pb [-c | -M | -P | -C file ...] [-f -m -s -p -l -d -u -D -T] [--device k]
 //
 // uncertainty_main / findEPPs_wrapper (uncertainty.cpp:279-339, 541-560): load the MAT, uncondense its leaves, read the sample
 // names, and for every sample report its equally parsimonious placements and neighborhood size (-e) and the candidate parents
 // (-o), in the reference's file formats.  The per-sample searches run on the device as one batch (ugp_uncertainty).
+// annotate_main (annotate.cpp:94-156): clade roots from exemplar samples, mutation sets, paths or node ids, written into the
+// .pb metadata.  Exemplar allele counts, the searches and the overlap counts run on the device (ugp_annotate.hip).
+#include <sys/stat.h>
+
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <map>
+#include <sstream>
 #include <string>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "mat.hpp"
@@ -161,11 +171,705 @@ int uncertainty(int argc, char **argv) {
     return 0;
 }
 
+// ---- annotate (annotate.cpp) --------------------------------------------------------------------------------------
+
+void annotate_usage(FILE *f) {
+    fprintf(f,
+            "Usage: matutils-amd annotate -i tree.pb -o out.pb [-c names.tsv] [-C clade_to_nid.tsv] [-P paths.tsv] [-M mutations.tsv]\n"
+            "       [-f 0.8] [-m 0.2] [-s 0.6] [-p 0.1] [-l] [-d dir] [-u mutations.tsv] [-D details.tsv] [-T n] [--device k]\n"
+            "  -i, --input-mat              input mutation-annotated tree [REQUIRED]\n"
+            "  -o, --output-mat             output mutation-annotated tree [REQUIRED]\n"
+            "  -c, --clade-names            tsv of clade assignments of samples (clade roots are searched for)\n"
+            "  -C, --clade-to-nid           tsv mapping clades to internal node identifiers\n"
+            "  -P, --clade-paths            tsv mapping clades to mutation paths\n"
+            "  -M, --clade-mutations        tsv mapping clades to sets of mutations\n"
+            "  -f, --allele-frequency       minimum allele frequency in the -c samples [0.8]\n"
+            "  -m, --mask-frequency         minimum allele frequency below -f that is masked [0.2]\n"
+            "  -s, --set-overlap            minimum fraction of the clade samples below the clade root [0.6]\n"
+            "  -p, --clip-sample-frequency  maximum proportion of exemplars in a branch when sorting candidates [0.1]\n"
+            "  -l, --clear-current          remove current annotations first\n"
+            "  -d, --output-directory       directory of the output files [./]\n"
+            "  -u, --write-mutations        tsv of each clade's mutations found in at least -f of the samples\n"
+            "  -D, --write-details          tsv of details about the nodes considered for each clade root\n"
+            "  -T, --threads                accepted for compatibility (the searches run on the device)\n"
+            "      --device                 HIP device ordinal [0]\n");
+}
+
+void split_delim(const std::string &s, char delim, std::vector<std::string> &words) {   // string_split, :383-398
+    size_t start = 0, end;
+    while ((end = s.find(delim, start)) != std::string::npos) {
+        words.emplace_back(s.substr(start, end - start));
+        start = end + 1;
+    }
+    std::string last = s.substr(start);
+    if (!last.empty()) words.push_back(last);
+}
+void split_ws(const std::string &s, std::vector<std::string> &words) {   // string_split, :401-413
+    std::istringstream ss(s);
+    std::string w;
+    while (ss >> w) words.push_back(w);
+}
+bool mutation_from_string(const std::string &s, uh::Mutation &m) {   // mutation_annotated_tree.cpp:358-380
+    char ref, alt;
+    int position;
+    if (sscanf(s.c_str(), "%c%d%c", &ref, &position, &alt) != 3 || ref < 'A' || ref > 'Z' || alt < 'A' || alt > 'Z') {
+        fprintf(stderr, "mutation_from_string: expected /[A-Z][0-9]+[A-Z/, got '%s'\n", s.c_str());
+        return false;
+    }
+    m = uh::Mutation();
+    m.ref_nuc = uh::nuc_id(ref);
+    m.position = position;
+    m.mut_nuc = uh::nuc_id(alt);
+    m.par_nuc = m.ref_nuc;
+    if (m.str() != s) {
+        fprintf(stderr, "mutation_from_string: unexpected characters at the end of '%s'\n", s.c_str());
+        return false;
+    }
+    return true;
+}
+bool by_position(const uh::Mutation &a, const uh::Mutation &b) { return a.position < b.position; }
+
+std::string node_mutations_string(const uh::Node *n) {
+    std::string s = n->id + ":";
+    for (size_t i = 0; i < n->mutations.size(); i++) { if (i) s += ','; s += n->mutations[i].str(); }
+    return s;
+}
+std::string path_to_node(const uh::Node *n) {   // :437-455
+    std::vector<std::string> parts;
+    for (const uh::Node *a = n; a; a = a->parent) parts.push_back(node_mutations_string(a));
+    std::string path;
+    for (size_t k = parts.size(); k-- > 0;) { path += parts[k]; if (k) path += " > "; }
+    return path;
+}
+void write_mutations(FILE *f, const std::vector<uh::Mutation> &ms, bool unmasked, bool masked) {   // :457-471
+    bool got = false;
+    for (const auto &m : ms) {
+        const std::string s = m.str();
+        const bool is_masked = s.back() == 'N';
+        if ((unmasked && !is_masked) || (masked && is_masked)) { if (got) fprintf(f, ", "); fprintf(f, "%s", s.c_str()); got = true; }
+    }
+}
+FILE *must_open(const std::string &name, const char *mode) {
+    FILE *f = fopen(name.c_str(), mode);
+    if (!f) { fprintf(stderr, "ERROR: Could not open file '%s' with mode '%s'\n", name.c_str(), mode); exit(1); }
+    return f;
+}
+
+void init_annotations(const std::vector<uh::Node *> &dfs, bool clear) {   // :158-168
+    for (uh::Node *n : dfs) { if (clear) n->clade_annotations.clear(); n->clade_annotations.emplace_back(""); }
+    // the reference indexes every node's annotations with the root's count: nodes with fewer would be read out of bounds
+    for (const uh::Node *n : dfs)
+        if (n->clade_annotations.size() != dfs[0]->clade_annotations.size()) {
+            fprintf(stderr, "ERROR: the nodes of the input MAT carry different numbers of clade annotations (use --clear-current)\n");
+            exit(1);
+        }
+}
+
+void lineages_from_nids(uh::Tree &T, const std::string &fname, bool clear) {   // assignLineages(T, clade_to_nid, clear), :170-206
+    init_annotations(T.dfs(), clear);
+    const size_t na = T.num_annotations();
+    std::ifstream in(fname);
+    if (!in) { fprintf(stderr, "ERROR: Could not open the clade to node id assignment file: %s!\n", fname.c_str()); exit(1); }
+    fprintf(stderr, "Reading clade to node id assignment file and completing assignments.\n");
+    std::string line;
+    while (std::getline(in, line)) {
+        std::vector<std::string> w;
+        split_delim(line, '\t', w);
+        if (w.size() > 2 || w.size() == 1) { fprintf(stderr, "ERROR: Incorrect format for clade to node id assignment file: %s!\n", fname.c_str()); exit(1); }
+        if (w.empty()) { fprintf(stderr, "ERROR: Node id  not found!\n"); exit(1); }   // words[1] of an empty line: no such node
+        uh::Node *n = T.get_node(w[1]);
+        if (!n) { fprintf(stderr, "ERROR: Node id %s not found!\n", w[1].c_str()); exit(1); }
+        if (n->clade_annotations[na - 1] != "")
+            fprintf(stderr, "WARNING: Assigning clade %s to node %s failed as the node is already assigned to clade %s!\n", w[0].c_str(),
+                    w[1].c_str(), n->clade_annotations[na - 1].c_str());
+        else n->clade_annotations[na - 1] = w[0];
+    }
+}
+
+bool node_has_muts(const uh::Node *n, const std::vector<std::string> &muts) {   // :808-830
+    if (n->mutations.size() != muts.size()) return false;
+    for (const auto &m : n->mutations) if (std::find(muts.begin(), muts.end(), m.str()) == muts.end()) return false;
+    return true;
+}
+
+void lineages_from_paths(uh::Tree &T, const std::string &fname, std::unordered_set<std::string> &done) {   // :832-913
+    const size_t na = T.num_annotations();
+    std::ifstream in(fname);
+    if (!in) { fprintf(stderr, "ERROR: Could not open the clade paths file: %s!\n", fname.c_str()); exit(1); }
+    fprintf(stderr, "Reading clade paths file and making assignments.\n");
+    int found = 0, failed_n = 0;
+    std::string line;
+    while (std::getline(in, line)) {
+        std::vector<std::string> w;
+        split_delim(line, '\t', w);
+        if (w.size() == 1 && !line.empty() && line.back() == '\t') w.push_back("");
+        if (w.size() != 2) {
+            fprintf(stderr, "ERROR: Incorrect format for clade paths file: %s!  Expected 2 tab-separated words, got %ld (%s)\n", fname.c_str(),
+                    (long)w.size(), line.c_str());
+            exit(1);
+        }
+        const std::string clade = w[0];
+        if (done.count(clade)) { fprintf(stderr, "Clade %s has already been assigned, ignoring path.\n", clade.c_str()); continue; }
+        std::vector<std::string> pw;
+        split_ws(w[1], pw);
+        uh::Node *node = T.root;
+        bool failed = false;
+        for (const std::string &el : pw) {
+            if (el.empty() || el == ">") continue;
+            std::vector<std::string> muts;
+            split_delim(el, ',', muts);
+            uh::Node *kid = nullptr;
+            for (uh::Node *c : node->children) if (node_has_muts(c, muts)) { kid = c; break; }
+            if (!kid) {
+                fprintf(stderr, "WARNING: path for %s not found: no child of node %s has mutations %s (path %s)\n", clade.c_str(), node->id.c_str(),
+                        el.c_str(), line.c_str());
+                failed = true; failed_n++;
+                break;
+            }
+            node = kid;
+        }
+        if (failed) continue;
+        if (node->clade_annotations[na - 1] != "")
+            fprintf(stderr, "WARNING: Assigning clade %s to node %s for path %s failed as the node is already assigned to clade %s!\n", clade.c_str(),
+                    node->id.c_str(), w[1].c_str(), node->clade_annotations[na - 1].c_str());
+        else node->clade_annotations[na - 1] = clade;
+        done.insert(clade);
+        found++;
+    }
+    fprintf(stderr, "\nAnnotated %d clades; failed to find paths for %d clades\n", found, failed_n);
+}
+
+void parse_clade_mutations(const std::string &fname, std::map<std::string, std::vector<uh::Mutation>> &out,
+                           const std::unordered_set<std::string> &done) {   // :208-299
+    std::ifstream in(fname);
+    if (!in) { fprintf(stderr, "ERROR: Could not open the clade mutations file: %s!\n", fname.c_str()); exit(1); }
+    std::map<std::string, std::vector<uh::Mutation>> all;
+    fprintf(stderr, "Reading clade mutations file %s.\n", fname.c_str());
+    bool got_error = false;
+    std::string line;
+    while (std::getline(in, line)) {
+        if (!line.empty() && line[0] == '#') continue;
+        std::vector<std::string> w;
+        split_delim(line, '\t', w);
+        if (w.size() == 1 && !line.empty() && line.back() == '\t') w.push_back("");
+        if (w.size() != 2) {
+            fprintf(stderr, "ERROR: Incorrect format for clade mutations file: %s!  Expected 2 tab-separated words, got %ld (%s)\n", fname.c_str(),
+                    (long)w.size(), line.c_str());
+            got_error = true;
+            continue;
+        }
+        const std::string clade = w[0];
+        if (all.count(clade)) { fprintf(stderr, "ERROR: clade %s is defined on multiple lines\n", clade.c_str()); got_error = true; continue; }
+        uh::Node node;
+        std::vector<std::string> mw;
+        split_ws(w[1], mw);
+        if (!mw.empty()) {
+            auto it = all.find(mw[0]);
+            if (it != all.end()) { node.mutations = it->second; mw.erase(mw.begin()); }
+        }
+        for (const std::string &el : mw) {
+            if (el.empty() || el == ">") continue;
+            std::vector<std::string> ms;
+            split_delim(el, ',', ms);
+            for (const std::string &s : ms) {
+                if (s.empty()) continue;
+                uh::Mutation m;
+                if (!mutation_from_string(s, m)) {
+                    fprintf(stderr, "Unable to parse mutation '%s' for %s element %s\n", s.c_str(), clade.c_str(), el.c_str());
+                    got_error = true;
+                } else if (!node.add_mutation(m)) {
+                    exit(1);
+                }
+            }
+        }
+        all[clade] = node.mutations;
+    }
+    for (const auto &kv : all) if (!done.count(kv.first)) out[kv.first] = kv.second;
+    if (got_error) { fprintf(stderr, "Encountered errors -- exiting.\n"); exit(1); }
+}
+
+struct NodeFreq {   // Node_freq, :544-557
+    size_t best_j;
+    float freq, overlap, freq_clipped;
+    NodeFreq(size_t a, float b, float c, float clip) : best_j(a), freq(b), overlap(c), freq_clipped(b > clip ? clip : b) {}
+    bool operator<(const NodeFreq &n) const { return (freq_clipped * overlap * overlap) > (n.freq_clipped * n.overlap * n.overlap); }
+};
+struct CladeAssignment {   // Clade_Assignments, :559-583
+    std::string clade_name;
+    size_t clade_size;
+    std::vector<NodeFreq> best_node_frequencies;
+    std::vector<uh::Mutation> mutations;
+    CladeAssignment(std::string name, size_t sz, std::vector<uh::Mutation> muts) : clade_name(std::move(name)), clade_size(sz), mutations(std::move(muts)) {}
+    bool operator<(const CladeAssignment &c) const {
+        if (clade_size == 0 && c.clade_size > 0) return true;
+        if (clade_size > 0 && c.clade_size == 0) return false;
+        return best_node_frequencies.size() < c.best_node_frequencies.size() ||
+               (best_node_frequencies.size() == c.best_node_frequencies.size() && clade_size > c.clade_size);
+    }
+};
+
+[[noreturn]] void lib_fail(const char *what) {
+    fprintf(stderr, "ERROR: %s: %s\n", what, ugp_last_error());
+    exit(1);
+}
+
+// assignLineages(T, clade_names, clade_mutations, clade_paths, ...), :483-806; the searches and counts on the device
+void lineages(uh::Tree &T, const std::string &fnames, const std::string &fmuts, const std::string &fpaths, float min_freq, float mask_freq,
+              float set_overlap, float clip, bool clear, const std::string &fmutsout, const std::string &fdetails, int device) {
+    const std::vector<uh::Node *> dfs = T.dfs();
+    const size_t N = dfs.size();
+    FILE *mf = nullptr, *df = nullptr;
+    if (!fmutsout.empty()) {
+        fprintf(stderr, "Writing clade root node mutations to file %s\n", fmutsout.c_str());
+        mf = must_open(fmutsout, "w");
+        fprintf(mf, "clade\tmutations\n");
+    }
+    if (!fdetails.empty()) {
+        fprintf(stderr, "Writing details to file %s\n", fdetails.c_str());
+        df = must_open(fdetails, "w");
+        fprintf(df, "clade\tmutations\tmasked_mutations\tnode:freq:overlap\talready_assigned\tfinal_overlap\texemplar_count\tbest_node_path\n");
+    }
+    fprintf(stderr, "Initializing annotations.\n");
+    init_annotations(dfs, clear);
+    const size_t na = T.num_annotations();
+    // the tree as breadth-first arrays (the C ABI's numbering); dfs_idx = position in `dfs`
+    const std::vector<uh::Node *> bfs = T.bfs();
+    std::unordered_map<const uh::Node *, uint32_t> bfs_idx, dfs_idx;
+    for (size_t j = 0; j < N; j++) { bfs_idx[bfs[j]] = (uint32_t)j; dfs_idx[dfs[j]] = (uint32_t)j; }
+    std::vector<uint32_t> parent(N);
+    std::vector<uint64_t> mut_off(N + 1, 0);
+    std::vector<int32_t> pos;
+    std::vector<uint8_t> ref, par, nuc;
+    std::vector<const uh::Mutation *> ent;
+    for (size_t j = 0; j < N; j++) {
+        parent[j] = bfs[j]->parent ? bfs_idx[bfs[j]->parent] : UINT32_MAX;
+        for (const auto &m : bfs[j]->mutations) {
+            pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
+            ent.push_back(&m);
+        }
+        mut_off[j + 1] = pos.size();
+    }
+    // leaves below each node (get_num_leaves), by depth-first position
+    std::vector<size_t> leaves(N, 0);
+    for (size_t k = N; k-- > 0;) {
+        if (dfs[k]->is_leaf()) leaves[k] = 1;
+        if (dfs[k]->parent) leaves[dfs_idx[dfs[k]->parent]] += leaves[k];
+    }
+
+    std::unordered_set<std::string> done;
+    if (!fpaths.empty()) lineages_from_paths(T, fpaths, done);
+    std::map<std::string, std::vector<uh::Mutation>> clade_muts;
+    std::map<std::string, std::vector<uh::Node *>> clade_map;   // exemplars, as nodes of T (looked up by the copy's names)
+    if (!fmuts.empty()) parse_clade_mutations(fmuts, clade_muts, done);
+
+    ugp_mat *h = nullptr;
+    const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+    auto device_up = [&]() {
+        if (h) return;
+        if (ugp_mat_create(&desc, device, &h) != UGP_OK) lib_fail("ugp_mat_create");
+        if (ugp_annotate_attach(h, &desc) != UGP_OK) lib_fail("ugp_annotate_attach");
+    };
+
+    std::map<std::string, std::vector<uint32_t>> clade_copy_dfs;   // exemplars as depth-first positions of the copy (= of T)
+    std::map<std::string, std::vector<std::string>> clade_names;   // ... and their names in the copy
+    if (!fnames.empty()) {
+        fprintf(stderr, "Copying tree with uncondensed leaves.\n");
+        uh::Tree U;
+        std::string err;
+        if (!uh::copy_tree(T, U, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); exit(1); }
+        if (!U.condensed_nodes.empty()) U.uncondense_leaves();
+        const std::vector<uh::Node *> udfs = U.dfs();
+        if (udfs.size() != N) { fprintf(stderr, "ERROR: the tree copy has a different node count\n"); exit(1); }
+        std::unordered_map<const uh::Node *, uint32_t> udfs_idx;
+        for (size_t k = 0; k < N; k++) udfs_idx[udfs[k]] = (uint32_t)k;
+        std::ifstream in(fnames);
+        if (!in) { fprintf(stderr, "ERROR: Could not open the clade assignment file: %s!\n", fnames.c_str()); exit(1); }
+        fprintf(stderr, "Reading clade assignment file %s.\n", fnames.c_str());
+        std::string line;
+        while (std::getline(in, line)) {
+            std::vector<std::string> w;
+            split_delim(line, '\t', w);
+            if (w.size() > 2 || w.size() == 1) {
+                fprintf(stderr, "ERROR: Incorrect format for clade assignment file: %s!  Expected 2 tab-separated words, got %ld\n", fnames.c_str(), (long)w.size());
+                exit(1);
+            }
+            if (w.size() != 2) continue;
+            if (clade_muts.count(w[0]) || done.count(w[0])) continue;
+            uh::Node *n = U.get_node(w[1]);
+            if (!n) { fprintf(stderr, "WARNING: Sample %s not found in input MAT!\n", w[1].c_str()); continue; }
+            clade_copy_dfs[w[0]].push_back(udfs_idx[n]);
+            clade_names[w[0]].push_back(n->id);
+        }
+        // the mutations of each clade's exemplars (:355-390): one device call for all clades
+        std::vector<uint64_t> coff(1, 0);
+        std::vector<uint32_t> xs;
+        std::vector<uint32_t> dfs2bfs(N);
+        for (size_t k = 0; k < N; k++) dfs2bfs[k] = bfs_idx[dfs[k]];
+        for (const auto &kv : clade_copy_dfs) {
+            for (uint32_t d : kv.second) xs.push_back(dfs2bfs[d]);
+            coff.push_back(xs.size());
+        }
+        const uint64_t nc = clade_copy_dfs.size();
+        std::vector<uint64_t> ooff(nc + 1);
+        uint64_t cap = std::max<uint64_t>(1024, 8 * xs.size()), n_out = 0;
+        std::vector<uint32_t> oe, oc;
+        if (nc) {
+            device_up();
+            for (;;) {
+                oe.resize(cap); oc.resize(cap);
+                if (ugp_clade_alleles(h, coff.data(), xs.data(), nc, ooff.data(), oe.data(), oc.data(), cap, &n_out) != UGP_OK) lib_fail("ugp_clade_alleles");
+                if (n_out <= cap) break;
+                cap = n_out;
+            }
+        }
+        size_t c = 0;
+        for (const auto &kv : clade_copy_dfs) {
+            const std::string &clade = kv.first;
+            fprintf(stderr, "Finding mutations in clade %s samples.\n", clade.c_str());
+            std::map<std::string, int> counts;
+            for (uint64_t k = ooff[c]; k < ooff[c + 1]; k++) {
+                const uh::Mutation &m = *ent[oe[k]];
+                counts[T.chroms[m.chrom] + "\t" + std::to_string(m.ref_nuc) + "\t" + std::to_string(m.position) + "\t" + std::to_string(m.mut_nuc)] += (int)oc[k];
+            }
+            std::vector<uh::Mutation> rows;
+            const size_t k_ex = kv.second.size();
+            for (const auto &mc : counts) {
+                const float f = static_cast<float>(mc.second) / k_ex;
+                if (!(f >= min_freq) && !(f >= mask_freq)) continue;
+                std::vector<std::string> w;
+                split_ws(mc.first, w);
+                uh::Mutation m;
+                m.chrom = T.chrom_id(w.size() == 4 ? w[0] : std::string());
+                const size_t o = w.size() == 4 ? 1 : 0;
+                m.ref_nuc = (int8_t)std::stoi(w[o]);
+                m.par_nuc = m.ref_nuc;
+                m.position = std::stoi(w[o + 1]);
+                m.mut_nuc = f >= min_freq ? (int8_t)std::stoi(w[o + 2]) : uh::nuc_id('N');
+                rows.push_back(m);
+            }
+            clade_muts[clade] = rows;
+            // get_freq_overlap looks the exemplars up in T by the copy's names (:470, :675)
+            std::vector<uh::Node *> &ex = clade_map[clade];
+            for (const std::string &id : clade_names[clade]) {
+                uh::Node *n = T.get_node(id);
+                if (!n) {
+                    fprintf(stderr, "ERROR: exemplar %s of clade %s names no node of the input MAT after the tree copy renumbered its internal "
+                            "nodes\n", id.c_str(), clade.c_str());
+                    exit(1);
+                }
+                ex.push_back(n);
+            }
+            c++;
+        }
+    }
+
+    // the searches (:611-638), UGP_ORDER_DFS over every node; one batched call for the packed rows, the literal one for the rest
+    std::vector<std::string> order;
+    std::vector<std::vector<uh::Mutation>> rows_of;
+    for (auto &kv : clade_muts) {
+        std::sort(kv.second.begin(), kv.second.end(), by_position);   // :586
+        order.push_back(kv.first);
+        rows_of.push_back(kv.second);
+    }
+    const size_t nc = order.size();
+    std::vector<int32_t> best(nc, 0);
+    std::vector<std::vector<uint32_t>> ties(nc);
+    if (nc) {
+        device_up();
+        std::vector<size_t> packed, literal;
+        for (size_t i = 0; i < nc; i++) {
+            bool awk = rows_of[i].empty();
+            for (size_t k = 0; k < rows_of[i].size(); k++)
+                awk = awk || rows_of[i][k].position < 0 || (k && rows_of[i][k].position == rows_of[i][k - 1].position);
+            (awk ? literal : packed).push_back(i);
+        }
+        auto batch = [&](const std::vector<size_t> &which, std::vector<uint64_t> &off, std::vector<int32_t> &qp, std::vector<uint8_t> &qr,
+                         std::vector<uint8_t> &qn, std::vector<uint8_t> &qm) {
+            off.assign(1, 0); qp.clear(); qr.clear(); qn.clear();
+            for (size_t i : which) {
+                for (const auto &m : rows_of[i]) { qp.push_back(m.position); qr.push_back((uint8_t)m.ref_nuc); qn.push_back((uint8_t)m.mut_nuc); }
+                off.push_back(qp.size());
+            }
+            qm.assign(qp.size(), 0);   // the reference never sets is_missing on these rows (:397, :407); 0 as mutation_from_string gives
+            return ugp_queries{which.size(), off.data(), qp.data(), qr.data(), qn.data(), qm.data()};
+        };
+        std::vector<uint64_t> off;
+        std::vector<int32_t> qp;
+        std::vector<uint8_t> qr, qn, qm;
+        for (int pass = 0; pass < 2; pass++) {
+            const std::vector<size_t> &which = pass ? literal : packed;
+            if (which.empty()) continue;
+            const ugp_queries q = batch(which, off, qp, qr, qn, qm);
+            uint32_t cap = 64;
+            std::vector<uint32_t> tj((size_t)which.size() * cap), tc(which.size());
+            std::vector<int32_t> sb(which.size());
+            if (pass == 0) {
+                ugp_place_opts o{UGP_ORDER_DFS, nullptr, nullptr, nullptr, nullptr};
+                std::vector<ugp_result> res(which.size());
+                std::vector<uint8_t> hu(tj.size());
+                if (ugp_place_batch_ex(h, &q, &o, res.data()) != UGP_OK) lib_fail("ugp_place_batch_ex");
+                if (ugp_tied_nodes_ex(h, &q, &o, cap, tj.data(), hu.data(), tc.data()) != UGP_OK) lib_fail("ugp_tied_nodes_ex");
+                for (size_t k = 0; k < which.size(); k++) sb[k] = res[k].best_set_difference;
+            } else if (ugp_annotate_search(h, &q, cap, sb.data(), tj.data(), tc.data()) != UGP_OK) {
+                lib_fail("ugp_annotate_search");
+            }
+            for (size_t k = 0; k < which.size(); k++) {
+                const size_t i = which[k];
+                best[i] = sb[k];
+                if (tc[k] <= cap) { ties[i].assign(tj.begin() + k * cap, tj.begin() + k * cap + tc[k]); continue; }
+                // more ties than the cap: this clade again with room for all of them
+                const std::vector<size_t> one{i};
+                std::vector<uint64_t> o1; std::vector<int32_t> p1; std::vector<uint8_t> r1, n1, m1;
+                const ugp_queries q1 = batch(one, o1, p1, r1, n1, m1);
+                const uint32_t big = tc[k];
+                std::vector<uint32_t> t1(big), c1(1);
+                std::vector<int32_t> b1(1);
+                if (pass == 0) {
+                    ugp_place_opts o{UGP_ORDER_DFS, nullptr, nullptr, nullptr, nullptr};
+                    std::vector<uint8_t> hu(big);
+                    if (ugp_tied_nodes_ex(h, &q1, &o, big, t1.data(), hu.data(), c1.data()) != UGP_OK) lib_fail("ugp_tied_nodes_ex");
+                } else if (ugp_annotate_search(h, &q1, big, b1.data(), t1.data(), c1.data()) != UGP_OK) {
+                    lib_fail("ugp_annotate_search");
+                }
+                ties[i].assign(t1.begin(), t1.begin() + std::min(big, c1[0]));
+            }
+            if (pass == 0) for (size_t i : which) std::sort(ties[i].begin(), ties[i].end());
+        }
+    }
+
+    // get_freq_overlap (:466-481) for every tie and each of its ancestors, one device call
+    std::vector<uint64_t> coffT(1, 0);
+    std::vector<uint32_t> xsT, pc, pn;
+    std::vector<size_t> cm_index(nc, SIZE_MAX);
+    for (size_t i = 0; i < nc; i++) {
+        auto cm = clade_map.find(order[i]);
+        if (cm == clade_map.end()) continue;
+        cm_index[i] = coffT.size() - 1;
+        for (uh::Node *n : cm->second) xsT.push_back(bfs_idx[n]);
+        coffT.push_back(xsT.size());
+    }
+    std::map<std::pair<size_t, uint32_t>, uint32_t> num_desc;
+    {
+        for (size_t i = 0; i < nc; i++) {
+            if (cm_index[i] == SIZE_MAX) continue;
+            for (uint32_t j : ties[i])
+                for (uh::Node *a = dfs[j]; a; a = a->parent) { pc.push_back((uint32_t)cm_index[i]); pn.push_back(bfs_idx[a]); }
+        }
+        std::vector<uint32_t> out(pc.size());
+        if (!pc.empty()) {
+            device_up();
+            if (ugp_clade_descendants(h, coffT.data(), xsT.data(), coffT.size() - 1, pc.data(), pn.data(), pc.size(), out.data()) != UGP_OK)
+                lib_fail("ugp_clade_descendants");
+        }
+        for (size_t k = 0; k < pc.size(); k++) num_desc[{pc[k], pn[k]}] = out[k];
+    }
+    if (h) ugp_mat_destroy(h);
+
+    std::vector<CladeAssignment> cas;
+    for (size_t i = 0; i < nc; i++) {
+        const std::string &clade = order[i];
+        std::vector<uh::Mutation> &cmuts = rows_of[i];
+        fprintf(stderr, "Mutations above the specified frequency in clade %s: ", clade.c_str());
+        write_mutations(stderr, cmuts, true, true);
+        fputc('\n', stderr);
+        if (mf) { fprintf(mf, "%s\t", clade.c_str()); write_mutations(mf, cmuts, true, false); fputc('\n', mf); }
+        fprintf(stderr, "Finding best node for clade %s.\n", clade.c_str());
+        fprintf(stderr, "Parsimony score at the best node: %d\n", best[i]);
+        // mapper2_body's winner (usher_mapper.cpp:483-486): more leaves, then the larger index
+        size_t win = 0;
+        for (size_t k = 0; k < ties[i].size(); k++)
+            if (k == 0 || leaves[ties[i][k]] > leaves[ties[i][win]] || (leaves[ties[i][k]] == leaves[ties[i][win]] && ties[i][k] > ties[i][win])) win = k;
+        for (size_t k = 0; k < ties[i].size(); k++) {
+            const uh::Node *node = dfs[ties[i][k]];
+            fprintf(stderr, "%s\t%d\t%c\t%s\t%s\n", clade.c_str(), best[i], k == win ? '*' : '-', node->id.c_str(), path_to_node(node).c_str());
+        }
+        if (ties[i].size() > 1) fprintf(stderr, "WARNING: found %zu possible assignments\n", ties[i].size());
+        auto cm = clade_map.find(clade);
+        if (cm != clade_map.end()) {
+            const size_t csize = cm->second.size();
+            cas.emplace_back(clade, csize, cmuts);
+            float best_freq = -1.0f;
+            for (uint32_t j : ties[i]) {   // already ascending: the stable_sort of :663
+                for (uh::Node *a = dfs[j]; a; a = a->parent) {
+                    const size_t nd = num_desc[{cm_index[i], bfs_idx[a]}];
+                    const float freq = static_cast<float>(nd) / leaves[dfs_idx[a]];
+                    const float overlap = static_cast<float>(nd) / csize;
+                    if (freq >= best_freq && overlap >= set_overlap) {
+                        cas.back().best_node_frequencies.emplace_back(dfs_idx[a], freq, overlap, clip);
+                        best_freq = freq;
+                    } else {
+                        break;
+                    }
+                }
+            }
+            if (cas.back().best_node_frequencies.empty()) {
+                fprintf(stderr, "WARNING: %s: no placement node or ancestor passed thresholds.\n", clade.c_str());
+                for (uint32_t j : ties[i]) {
+                    const size_t nd = num_desc[{cm_index[i], bfs_idx[dfs[j]]}];
+                    fprintf(stderr, "fail node\t%s\t%s\t%f\t%f\n", clade.c_str(), dfs[j]->id.c_str(), static_cast<float>(nd) / leaves[j],
+                            static_cast<float>(nd) / csize);
+                }
+            }
+            std::stable_sort(cas.back().best_node_frequencies.begin(), cas.back().best_node_frequencies.end());
+        } else {
+            cas.emplace_back(clade, 0, cmuts);
+            if (best[i] == 0) {
+                size_t bj = 0, most = 0;
+                for (uint32_t j : ties[i]) if (leaves[j] > most) { bj = j; most = leaves[j]; }
+                cas.back().best_node_frequencies.emplace_back(bj, 1, 1, clip);
+            } else {
+                fprintf(stderr, "WARNING: skipping clade %s because the parsimony score is %d\n", clade.c_str(), best[i]);
+            }
+        }
+    }
+    fprintf(stderr, "Sorting clades by the number of best nodes \n");
+    std::sort(cas.begin(), cas.end());
+    fprintf(stderr, "Now assigning clades to nodes \n");
+    for (const CladeAssignment &c : cas) {
+        bool assigned = false;
+        const NodeFreq *an = nullptr;
+        std::string already;
+        for (const NodeFreq &n : c.best_node_frequencies) {
+            uh::Node *node = dfs[n.best_j];
+            if (node->clade_annotations[na - 1] == "") {
+                fprintf(stderr, "\nAssigning %s to node %s\n", c.clade_name.c_str(), node->id.c_str());
+                if (c.clade_size > 0)
+                    fprintf(stderr, "%f fraction of %zu clade %s samples are descendants of the assigned node %s\n", n.overlap, c.clade_size,
+                            c.clade_name.c_str(), node->id.c_str());
+                node->clade_annotations[na - 1] = c.clade_name;
+                assigned = true;
+                an = &n;
+                break;
+            }
+            fprintf(stderr, "\nNode %s already assigned to %s, cannot assign to %s.\n", node->id.c_str(), node->clade_annotations[na - 1].c_str(),
+                    c.clade_name.c_str());
+            if (!already.empty()) already += ", ";
+            already += node->id + ":" + node->clade_annotations[na - 1];
+        }
+        if (!assigned) {
+            if (!c.best_node_frequencies.empty())
+                fprintf(stderr, "\nWARNING: Could not assign a node to clade %s with %zu samples since all possible nodes were already assigned some other clade!\n",
+                        c.clade_name.c_str(), c.clade_size);
+            else
+                fprintf(stderr, "\nWARNING: Could not assign a node to clade %s with %zu samples since placement node(s) did not overlap with enough clade samples!\n",
+                        c.clade_name.c_str(), c.clade_size);
+        }
+        if (df) {
+            fprintf(df, "%s\t", c.clade_name.c_str());
+            write_mutations(df, c.mutations, true, false);
+            fputc('\t', df);
+            write_mutations(df, c.mutations, false, true);
+            fputc('\t', df);
+            if (c.best_node_frequencies.empty()) fprintf(df, "n/a");
+            for (size_t k = 0; k < c.best_node_frequencies.size(); k++) {
+                if (k) fprintf(df, ", ");
+                const NodeFreq &b = c.best_node_frequencies[k];
+                fprintf(df, "%s:%f:%f", dfs[b.best_j]->id.c_str(), b.freq, b.overlap);
+            }
+            fprintf(df, already.empty() ? "\tn/a" : "\t%s", already.c_str());
+            fprintf(df, "\t%f", assigned ? an->overlap : 0.0);
+            fprintf(df, "\t%lu", (unsigned long)c.clade_size);
+            std::string path = "n/a";
+            if (assigned) path = path_to_node(dfs[an->best_j]);
+            else if (!c.best_node_frequencies.empty()) path = path_to_node(dfs[c.best_node_frequencies[0].best_j]);
+            fprintf(df, "\t%s\n", path.c_str());
+        }
+    }
+    if (mf) fclose(mf);
+    if (df) fclose(df);
+}
+
+int annotate(int argc, char **argv) {   // annotate_main, :94-156
+    std::string in_mat, out_mat, fnames, fnid, fpaths, fmuts, fmutsout, fdetails, dir = "./";
+    float min_freq = 0.8f, mask_freq = 0.2f, set_overlap = 0.6f, clip = 0.1f;
+    bool clear = false;
+    int device = 0;
+    for (int i = 0; i < argc; i++) {
+        const std::string a = argv[i];
+        auto val = [&](std::string &dst) -> bool {
+            if (i + 1 >= argc) { fprintf(stderr, "ERROR: %s needs a value\n", a.c_str()); annotate_usage(stderr); return false; }
+            dst = argv[++i];
+            return true;
+        };
+        auto fval = [&](float &dst) -> bool {
+            std::string t;
+            if (!val(t)) return false;
+            char *end = nullptr;
+            dst = strtof(t.c_str(), &end);
+            if (t.empty() || *end) { fprintf(stderr, "ERROR: bad value %s for %s\n", t.c_str(), a.c_str()); annotate_usage(stderr); return false; }
+            return true;
+        };
+        std::string tmp;
+        bool ok = true;
+        if (a == "-i" || a == "--input-mat") ok = val(in_mat);
+        else if (a == "-o" || a == "--output-mat") ok = val(out_mat);
+        else if (a == "-c" || a == "--clade-names") ok = val(fnames);
+        else if (a == "-C" || a == "--clade-to-nid") ok = val(fnid);
+        else if (a == "-P" || a == "--clade-paths") ok = val(fpaths);
+        else if (a == "-M" || a == "--clade-mutations") ok = val(fmuts);
+        else if (a == "-f" || a == "--allele-frequency") ok = fval(min_freq);
+        else if (a == "-m" || a == "--mask-frequency") ok = fval(mask_freq);
+        else if (a == "-s" || a == "--set-overlap") ok = fval(set_overlap);
+        else if (a == "-p" || a == "--clip-sample-frequency") ok = fval(clip);
+        else if (a == "-l" || a == "--clear-current") clear = true;
+        else if (a == "-d" || a == "--output-directory") ok = val(dir);
+        else if (a == "-u" || a == "--write-mutations") ok = val(fmutsout);
+        else if (a == "-D" || a == "--write-details") ok = val(fdetails);
+        else if (a == "-T" || a == "--threads") ok = val(tmp);
+        else if (a == "--device") { ok = val(tmp); device = atoi(tmp.c_str()); }
+        else if (a == "-h" || a == "--help") { annotate_usage(stderr); return 0; }
+        else { fprintf(stderr, "ERROR: unknown option %s\n", a.c_str()); annotate_usage(stderr); return 1; }
+        if (!ok) return 1;
+    }
+    if (in_mat.empty() || out_mat.empty()) {
+        fprintf(stderr, "ERROR: the option '--%s' is required but missing\n", in_mat.empty() ? "input-mat" : "output-mat");
+        annotate_usage(stderr);
+        return 1;
+    }
+    // make_out_dir / add_out_dir (:65-84)
+    struct stat sb;
+    if (stat(dir.c_str(), &sb) != 0) {
+        fprintf(stderr, "Creating output directory %s.\n\n", dir.c_str());
+        mkdir(dir.c_str(), 0777);
+    }
+    char *canon = realpath(dir.c_str(), nullptr);
+    if (!canon) { fprintf(stderr, "ERROR: cannot resolve the output directory %s\n", dir.c_str()); return 1; }
+    const std::string prefix = canon;
+    free(canon);
+    auto add_out = [&](const std::string &f) { return (!f.empty() && f[0] != '/') ? prefix + "/" + f : f; };
+    out_mat = add_out(out_mat);
+    fmutsout = add_out(fmutsout);
+    fdetails = add_out(fdetails);
+    int spec = 0;
+    if (!fnames.empty() || !fmuts.empty() || !fpaths.empty()) spec++;
+    if (!fnid.empty()) spec++;
+    if (spec != 1) {
+        fprintf(stderr, "ERROR: must specify either --clade-to-nid or [--clade-names and/or --clade-mutations and/or --clade-paths]!\n");
+        return 1;
+    }
+    fprintf(stderr, "Loading input MAT file %s.\n", in_mat.c_str());
+    uh::Tree T;
+    std::string err;
+    if (!uh::load_mat(in_mat, T, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+    if (!T.condensed_nodes.empty()) T.uncondense_leaves();
+    fprintf(stderr, "Annotating Lineage Root Nodes\n");
+    if (!fnames.empty() || !fmuts.empty() || !fpaths.empty())
+        lineages(T, fnames, fmuts, fpaths, min_freq, mask_freq, set_overlap, clip, clear, fmutsout, fdetails, device);
+    else
+        lineages_from_nids(T, fnid, clear);
+    fprintf(stderr, "Recondensing leaves\n");
+    T.condense_leaves();
+    fprintf(stderr, "Saving Final Tree to %s\n", out_mat.c_str());
+    if (!uh::save_mat(T, out_mat, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
     if (argc < 2 || !strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) { usage(argc < 2 ? stderr : stdout); return argc < 2 ? 1 : 0; }
     if (!strcmp(argv[1], "uncertainty")) return uncertainty(argc - 2, argv + 2);
-    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty)\n", argv[1]);
+    if (!strcmp(argv[1], "annotate")) return annotate(argc - 2, argv + 2);
+    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate)\n", argv[1]);
     return 1;
 }

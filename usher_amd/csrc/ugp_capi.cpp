@@ -25,6 +25,7 @@
 #include "ugp_knobs.hpp"
 #include "ugp_ripples.hpp"
 #include "ugp_uncertainty.hpp"
+#include "ugp_annotate.hpp"
 #include "ugp_update.hpp"
 #include "usher_amd.h"
 
@@ -288,6 +289,7 @@ struct ugp_mat {
     } upd;
     ugp::UncState *unc = nullptr;    // matUtils uncertainty tables (ugp_uncertainty_attach), or none
     ugp::RipState *rip = nullptr;    // RIPPLES tables (ugp_ripples_attach), or none
+    ugp::AnnState *ann = nullptr;    // matUtils annotate tables (ugp_annotate_attach), or none
     hipEvent_t kb_done = nullptr;    // behind the latest k_best8 launch of this handle ...
     hipStream_t kb_done_on = nullptr;   // ... on this stream
 };
@@ -1298,6 +1300,7 @@ void ugp_mat_destroy(ugp_mat *m) {
     delete m->own_qs;
     ugp::unc_free(m->unc);
     ugp::rip_free(m->rip);
+    ugp::ann_free(m->ann);
     delete m;
 }
 
@@ -1731,6 +1734,36 @@ int ugp_uncertainty(ugp_mat *m, const uint32_t *nodes, uint64_t n, uint32_t cap,
                     uint32_t *tie_count) {
     if (!m) return fail(UGP_ERR_INVALID, "null argument");
     return ugp::unc_run(m->unc, nodes, n, cap, epps, nsize, tie_dfs, tie_count);
+}
+
+// ---- matUtils annotate (ugp_annotate.hip) --------------------------------------------------------------------------
+
+int ugp_annotate_attach(ugp_mat *m, const ugp_tree_desc *tree) {
+    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
+    const uint64_t N = m->flat.n_nodes;
+    if (m->h_parent.size() != N) return fail(UGP_ERR_INVALID, "this handle has no host topology (created from a coarse tree?)");
+    if (tree->n_nodes != N) return fail(UGP_ERR_INVALID, "the tree is not the handle's tree (node count)");
+    for (uint64_t j = 1; j < N; j++)
+        if (tree->parent[j] != m->h_parent[j]) return fail(UGP_ERR_INVALID, "the tree is not the handle's tree (parent array)");
+    try { ensure_dfs_order(m); } catch (const std::bad_alloc &) { return fail(UGP_ERR_NOMEM, "out of host memory"); }
+    return ugp::ann_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->ann);
+}
+
+int ugp_clade_alleles(ugp_mat *m, const uint64_t *clade_off, const uint32_t *nodes, uint64_t n_clades, uint64_t *out_off, uint32_t *out_ent,
+                      uint32_t *out_cnt, uint64_t cap, uint64_t *n_out) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::ann_alleles(m->ann, clade_off, nodes, n_clades, out_off, out_ent, out_cnt, cap, n_out);
+}
+
+int ugp_clade_descendants(ugp_mat *m, const uint64_t *clade_off, const uint32_t *nodes, uint64_t n_clades, const uint32_t *pair_clade,
+                          const uint32_t *pair_node, uint64_t n_pairs, uint32_t *out) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::ann_descendants(m->ann, clade_off, nodes, n_clades, pair_clade, pair_node, n_pairs, out);
+}
+
+int ugp_annotate_search(ugp_mat *m, const ugp_queries *q, uint32_t cap, int32_t *best, uint32_t *tie_dfs, uint32_t *tie_count) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::ann_search(m->ann, q, cap, best, tie_dfs, tie_count);
 }
 
 // ---- RIPPLES (ugp_ripples.hip) -----------------------------------------------------------------------------------------

@@ -280,6 +280,62 @@ class Placer:
         self._ck(self._L.ugp_uncertainty(self._h, _ptr(nodes), n, int(cap), _ptr(epps), _ptr(nsize), _ptr(ties), _ptr(cnt)))
         return epps, nsize, [ties[i, :min(int(cnt[i]), cap)].copy() for i in range(n)], cnt
 
+    # ---- matUtils annotate (ugp_annotate_attach / ugp_clade_alleles / ugp_clade_descendants / ugp_annotate_search) ------
+    def _ann_ready(self):
+        if not getattr(self, "_ann_attached", False):
+            self._ck(self._L.ugp_annotate_attach(self._h, C.byref(self._t.desc)))
+            self._ann_attached = True
+
+    @staticmethod
+    def _clades_csr(clades):
+        off = np.zeros(len(clades) + 1, np.uint64)
+        if len(clades):
+            off[1:] = np.cumsum([len(c) for c in clades])
+        nodes = np.ascontiguousarray(np.concatenate([np.asarray(c, np.uint32) for c in clades]) if int(off[-1]) else
+                                     np.zeros(0, np.uint32), dtype=np.uint32)
+        return off, nodes
+
+    def clade_alleles(self, clades):
+        """Clade allele counts of matUtils annotate (annotate.cpp:355-390): clades[c] = exemplar nodes (BFS indices, repeats
+        count).  Returns one (entries, counts) pair per clade: the tree's mutation entries (indices into the mutation CSR) that
+        the exemplars' root-path walks add, in depth-first order of their node, and how many exemplars add each."""
+        self._ann_ready()
+        off, nodes = self._clades_csr(clades)
+        n = len(clades)
+        out_off = np.zeros(n + 1, np.uint64)
+        n_out = C.c_uint64(0)
+        cap = max(1024, 8 * len(nodes))
+        while True:
+            ent = np.zeros(cap, np.uint32); cnt = np.zeros(cap, np.uint32)
+            self._ck(self._L.ugp_clade_alleles(self._h, _ptr(off), _ptr(nodes), n, _ptr(out_off), _ptr(ent), _ptr(cnt), cap,
+                                               C.byref(n_out)))
+            if n_out.value <= cap:
+                break
+            cap = int(n_out.value)
+        return [(ent[int(out_off[c]):int(out_off[c + 1])].copy(), cnt[int(out_off[c]):int(out_off[c + 1])].copy()) for c in range(n)]
+
+    def clade_descendants(self, clades, pair_clade, pair_node) -> np.ndarray:
+        """Exemplars of clade pair_clade[i] strictly below node pair_node[i] (BFS): get_freq_overlap's count (annotate.cpp:466-481)."""
+        self._ann_ready()
+        off, nodes = self._clades_csr(clades)
+        pc = np.ascontiguousarray(pair_clade, dtype=np.uint32)
+        pn = np.ascontiguousarray(pair_node, dtype=np.uint32)
+        if len(pc) != len(pn):
+            raise ValueError("pair_clade and pair_node need the same length")
+        out = np.zeros(len(pc), np.uint32)
+        self._ck(self._L.ugp_clade_descendants(self._h, _ptr(off), _ptr(nodes), len(clades), _ptr(pc), _ptr(pn), len(pc), _ptr(out)))
+        return out
+
+    def annotate_search(self, batch: QueryBatch, cap: int = 1024):
+        """annotate's search (annotate.cpp:611-638) run literally for any rows (repeated or masked positions included):
+        (best, ties, tie_count), ties[i] = the first min(cap, tie_count[i]) tied depth-first positions, ascending."""
+        self._ann_ready()
+        n = len(batch)
+        best = np.zeros(n, np.int32); cnt = np.zeros(n, np.uint32)
+        ties = np.zeros((n, max(cap, 1)), np.uint32)
+        self._ck(self._L.ugp_annotate_search(self._h, C.byref(batch.desc), int(cap), _ptr(best), _ptr(ties), _ptr(cnt)))
+        return best, [ties[i, :min(int(cnt[i]), cap)].copy() for i in range(n)], cnt
+
     RIPPLES_EVENT = np.dtype([("branch", np.uint64), ("i", np.uint32), ("j", np.uint32), ("donor", np.uint32), ("acceptor", np.uint32),
                               ("donor_count", np.uint32), ("acceptor_count", np.uint32), ("donor_score", np.int32),
                               ("acceptor_score", np.int32), ("donor_sibling", np.uint8), ("acceptor_sibling", np.uint8),
