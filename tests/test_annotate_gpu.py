@@ -9,7 +9,7 @@ from tests import annotate_ref as A
 from tests import stdorder
 from tests import synth
 from tests import uncertainty_ref as U
-from usher_amd import Placer, QueryBatch
+from usher_amd import Placer, QueryBatch, UgpError
 
 pytestmark = pytest.mark.gpu
 
@@ -114,4 +114,50 @@ def test_literal_search_agrees_with_the_packed_search():
     for i in range(len(qs)):
         assert int(best[i]) == int(res[i]["best_set_difference"])
         assert ties[i].tolist() == sorted(tj[i].tolist()) and int(cnt[i]) == int(tc[i])
+    pl.close()
+
+
+def _repeat_a_position(arrays):
+    """The arrays with one more entry on a branch: a second non-masked mutation at the position of the branch's first one,
+    after its last (so no two entries at one position are adjacent)."""
+    off = np.asarray(arrays["mut_off"], np.int64)
+    pos = np.asarray(arrays["mut_pos"])
+    j = next(v for v in range(1, arrays["n"]) if off[v + 1] - off[v] >= 2 and (pos[off[v]:off[v + 1]] >= 0).all())
+    k, at = int(off[j]), int(off[j + 1])
+    out = dict(arrays)
+    for key in arrays:
+        if key.startswith("mut_") and key != "mut_off":
+            out[key] = np.insert(np.asarray(arrays[key]), at, np.asarray(arrays[key])[k])
+    nuc, ref = int(arrays["mut_nuc"][k]), int(arrays["mut_ref"][k])
+    out["mut_nuc"][at] = next(b for b in (1, 2, 4, 8) if b not in (nuc, ref))
+    if "mut_par" in out:
+        out["mut_par"][at] = nuc
+    out["mut_off"] = (off + (np.arange(len(off)) > j)).astype(np.asarray(arrays["mut_off"]).dtype)
+    return out
+
+
+@pytest.mark.parametrize("annotate_first", [False, True])
+def test_attach_with_two_mutations_at_one_position_on_one_branch(annotate_first):
+    """Uncertainty and annotate share the handle's depth-first tables.  On a tree with two non-masked mutations at one position
+    on one branch, both literal searches refuse it, and the clade walk still works, whichever attached first."""
+    arrays = _repeat_a_position(synth.make_case(45, n_leaves=300, n_queries=1, n_sites=60, genome_len=400)[0])
+    rng = np.random.default_rng(45)
+    clades = _clades(arrays, rng, 6)
+    rows = _awkward_rows(arrays, rng, 0)
+    pl = Placer(arrays)
+
+    def refused(call):
+        with pytest.raises(UgpError) as e:
+            call()
+        assert e.value.code == -2   # UGP_ERR_UNSUPPORTED
+
+    def alleles():
+        for c, (ent, cnt) in zip(clades, pl.clade_alleles(clades)):
+            assert dict(zip(ent.tolist(), cnt.tolist())) == A.alleles_literal(arrays, c)
+
+    if annotate_first:
+        alleles()
+    refused(lambda: pl.uncertainty(np.array([1, 2])))
+    alleles()
+    refused(lambda: pl.annotate_search(QueryBatch([rows])))
     pl.close()

@@ -9,10 +9,13 @@
 
 namespace ugp {
 
+struct DfsTables;
 struct AnnState;
 
-// Host tables of `tree` in the depth-first expansion `dfs2bfs` (+ inverse), uploaded to `device`.  *out is replaced.
-int ann_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device, AnnState **out);
+// A state on `device` that reads the handle's depth-first tables *tables (ugp_dense.hpp; built from `tree` in the expansion
+// `dfs2bfs` (+ inverse) when there are none yet).  *out is replaced.
+int ann_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
+               DfsTables **tables, AnnState **out);
 void ann_free(AnnState *s);
 // Outputs as ugp_clade_alleles / ugp_clade_descendants / ugp_annotate_search document them.
 int ann_alleles(AnnState *s, const uint64_t *clade_off, const uint32_t *nodes, uint64_t n_clades, uint64_t *out_off, uint32_t *out_ent,

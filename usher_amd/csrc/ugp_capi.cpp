@@ -19,6 +19,7 @@
 #include <unistd.h>
 
 #include "ugp_bound3.hpp"
+#include "ugp_dense.hpp"
 #include "ugp_tuner.hpp"
 #include "ugp_flatten.hpp"
 #include "ugp_kernels.hpp"
@@ -290,6 +291,7 @@ struct ugp_mat {
     ugp::UncState *unc = nullptr;    // matUtils uncertainty tables (ugp_uncertainty_attach), or none
     ugp::RipState *rip = nullptr;    // RIPPLES tables (ugp_ripples_attach), or none
     ugp::AnnState *ann = nullptr;    // matUtils annotate tables (ugp_annotate_attach), or none
+    ugp::DfsTables *dfs = nullptr;   // the depth-first tables uncertainty and annotate share (their first attach), or none
     hipEvent_t kb_done = nullptr;    // behind the latest k_best8 launch of this handle ...
     hipStream_t kb_done_on = nullptr;   // ... on this stream
 };
@@ -1301,6 +1303,7 @@ void ugp_mat_destroy(ugp_mat *m) {
     ugp::unc_free(m->unc);
     ugp::rip_free(m->rip);
     ugp::ann_free(m->ann);
+    ugp::dfs_tables_free(m->dfs);
     delete m;
 }
 
@@ -1719,15 +1722,21 @@ int ugp_subtree_mask(ugp_mat *m, uint32_t order, uint32_t root_j, uint32_t max_l
 
 // ---- matUtils uncertainty (ugp_uncertainty.hip) ----------------------------------------------------------------------
 
-int ugp_uncertainty_attach(ugp_mat *m, const ugp_tree_desc *tree) {
-    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
+// The attach calls take the handle's own tree (same parent array) and its depth-first expansion.
+static int check_handle_tree(ugp_mat *m, const ugp_tree_desc *tree) {
     const uint64_t N = m->flat.n_nodes;
     if (m->h_parent.size() != N) return fail(UGP_ERR_INVALID, "this handle has no host topology (created from a coarse tree?)");
     if (tree->n_nodes != N) return fail(UGP_ERR_INVALID, "the tree is not the handle's tree (node count)");
     for (uint64_t j = 1; j < N; j++)
         if (tree->parent[j] != m->h_parent[j]) return fail(UGP_ERR_INVALID, "the tree is not the handle's tree (parent array)");
     try { ensure_dfs_order(m); } catch (const std::bad_alloc &) { return fail(UGP_ERR_NOMEM, "out of host memory"); }
-    return ugp::unc_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->unc);
+    return UGP_OK;
+}
+
+int ugp_uncertainty_attach(ugp_mat *m, const ugp_tree_desc *tree) {
+    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
+    if (int rc = check_handle_tree(m, tree)) return rc;
+    return ugp::unc_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->unc);
 }
 
 int ugp_uncertainty(ugp_mat *m, const uint32_t *nodes, uint64_t n, uint32_t cap, uint32_t *epps, uint32_t *nsize, uint32_t *tie_dfs,
@@ -1740,13 +1749,8 @@ int ugp_uncertainty(ugp_mat *m, const uint32_t *nodes, uint64_t n, uint32_t cap,
 
 int ugp_annotate_attach(ugp_mat *m, const ugp_tree_desc *tree) {
     if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
-    const uint64_t N = m->flat.n_nodes;
-    if (m->h_parent.size() != N) return fail(UGP_ERR_INVALID, "this handle has no host topology (created from a coarse tree?)");
-    if (tree->n_nodes != N) return fail(UGP_ERR_INVALID, "the tree is not the handle's tree (node count)");
-    for (uint64_t j = 1; j < N; j++)
-        if (tree->parent[j] != m->h_parent[j]) return fail(UGP_ERR_INVALID, "the tree is not the handle's tree (parent array)");
-    try { ensure_dfs_order(m); } catch (const std::bad_alloc &) { return fail(UGP_ERR_NOMEM, "out of host memory"); }
-    return ugp::ann_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->ann);
+    if (int rc = check_handle_tree(m, tree)) return rc;
+    return ugp::ann_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->ann);
 }
 
 int ugp_clade_alleles(ugp_mat *m, const uint64_t *clade_off, const uint32_t *nodes, uint64_t n_clades, uint64_t *out_off, uint32_t *out_ent,
@@ -1770,12 +1774,8 @@ int ugp_annotate_search(ugp_mat *m, const ugp_queries *q, uint32_t cap, int32_t 
 
 int ugp_ripples_attach(ugp_mat *m, const ugp_tree_desc *tree, const uint32_t *name_rank) {
     if (!m || !tree || !tree->parent || !name_rank) return fail(UGP_ERR_INVALID, "null argument");
-    const uint64_t N = m->flat.n_nodes;
-    if (m->h_parent.size() != N) return fail(UGP_ERR_INVALID, "this handle has no host topology (created from a coarse tree?)");
-    if (tree->n_nodes != N) return fail(UGP_ERR_INVALID, "the tree is not the handle's tree (node count)");
-    for (uint64_t j = 1; j < N; j++)
-        if (tree->parent[j] != m->h_parent[j]) return fail(UGP_ERR_INVALID, "the tree is not the handle's tree (parent array)");
-    return ugp::rip_attach(tree, name_rank, m->device, &m->rip);
+    if (int rc = check_handle_tree(m, tree)) return rc;
+    return ugp::rip_attach(tree, name_rank, m->h_bfs2dfs, m->device, &m->rip);
 }
 
 int ugp_ripples(ugp_mat *m, const ugp_ripples_opts *opts, const uint32_t *branches, uint64_t n, ugp_ripples_event *out, uint64_t cap,

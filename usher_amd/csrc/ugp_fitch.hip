@@ -50,6 +50,7 @@
 #include <string>
 #include <vector>
 
+#include "ugp_dense.hpp"
 #include "usher_amd.h"
 
 namespace ugp {
@@ -643,12 +644,6 @@ struct ugp_fitch {
     std::vector<uint8_t> par, nuc;
 };
 
-#define FS_TRY(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) return ugp::set_error(UGP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 extern "C" int ugp_fitch_sankoff(int device, uint64_t n_nodes, const uint32_t *parent, const ugp_sites *sites, ugp_fitch **out) {
     if (!out) return ugp::set_error(UGP_ERR_INVALID, "null output handle");
     *out = nullptr;
@@ -679,7 +674,7 @@ extern "C" int ugp_fitch_sankoff(int device, uint64_t n_nodes, const uint32_t *p
     if (!res) return ugp::set_error(UGP_ERR_NOMEM, "out of host memory");
     struct Guard { ugp_fitch *r; ~Guard() { delete r; } } guard{res};
 
-    FS_TRY(hipSetDevice(device));
+    UGP_HIP_TRY(hipSetDevice(device));
     hipStream_t stream = nullptr;
     FsPool &P = *fs_pool(device);
     std::lock_guard<std::mutex> pool_lock(P.mu);   // (calls on one device take turns: they share the pooled buffers)
@@ -687,21 +682,21 @@ extern "C" int ugp_fitch_sankoff(int device, uint64_t n_nodes, const uint32_t *p
     // ---- topology, on the device: run heads of parent[] -> first child / child count / internal nodes in level order.  The level
     // boundaries themselves are a handful of binary searches in the caller's array (a level is an index range; its children are
     // the nodes whose parent lies in it), meaningful once the device has confirmed the order.
-    FS_TRY(d_parent.upload(parent, N, stream));
-    FS_TRY(d_nchild.alloc(N)); FS_TRY(d_inodes.alloc((size_t)N + 8)); FS_TRY(P.d_heads.alloc(N)); FS_TRY(P.d_flag.alloc(N));
-    FS_TRY(P.d_ifirst.alloc((size_t)N + 8)); FS_TRY(P.d_inch.alloc((size_t)N + 8));   // (+8: the forward sweep reads whole groups)
-    FS_TRY(P.d_small.alloc(16));   // [0] order violated, [1] run heads, [2] cell flags, [3] polytomies
+    UGP_HIP_TRY(d_parent.upload(parent, N, stream));
+    UGP_HIP_TRY(d_nchild.alloc(N)); UGP_HIP_TRY(d_inodes.alloc((size_t)N + 8)); UGP_HIP_TRY(P.d_heads.alloc(N)); UGP_HIP_TRY(P.d_flag.alloc(N));
+    UGP_HIP_TRY(P.d_ifirst.alloc((size_t)N + 8)); UGP_HIP_TRY(P.d_inch.alloc((size_t)N + 8));   // (+8: the forward sweep reads whole groups)
+    UGP_HIP_TRY(P.d_small.alloc(16));   // [0] order violated, [1] run heads, [2] cell flags, [3] polytomies
     const uint32_t wide_cap = N / (FS_WIDE + 1) + 1;   // (more nodes with more than FS_WIDE children each do not fit in N)
-    FS_TRY(P.d_wide.alloc(3 * (size_t)wide_cap));
-    FS_TRY(hipMemsetAsync(P.d_small.p, 0, 8 * sizeof(uint32_t), stream));
-    FS_TRY(hipMemsetAsync(d_nchild.p, 0, (size_t)N * 4, stream));
+    UGP_HIP_TRY(P.d_wide.alloc(3 * (size_t)wide_cap));
+    UGP_HIP_TRY(hipMemsetAsync(P.d_small.p, 0, 8 * sizeof(uint32_t), stream));
+    UGP_HIP_TRY(hipMemsetAsync(d_nchild.p, 0, (size_t)N * 4, stream));
     hipLaunchKernelGGL(k_fs_heads, dim3((N + 255) / 256), dim3(256), 0, stream, d_parent.p, N, P.d_flag.p, P.d_small.p);
     {
         size_t sel_bytes = 0;
         rocprim::counting_iterator<uint32_t> idx(0);
-        FS_TRY(rocprim::select(nullptr, sel_bytes, idx, P.d_flag.p, P.d_heads.p, P.d_small.p + 1, (size_t)N, stream));
-        FS_TRY(P.d_sel_tmp.alloc(sel_bytes));
-        FS_TRY(rocprim::select(P.d_sel_tmp.p, sel_bytes, idx, P.d_flag.p, P.d_heads.p, P.d_small.p + 1, (size_t)N, stream));
+        UGP_HIP_TRY(rocprim::select(nullptr, sel_bytes, idx, P.d_flag.p, P.d_heads.p, P.d_small.p + 1, (size_t)N, stream));
+        UGP_HIP_TRY(P.d_sel_tmp.alloc(sel_bytes));
+        UGP_HIP_TRY(rocprim::select(P.d_sel_tmp.p, sel_bytes, idx, P.d_flag.p, P.d_heads.p, P.d_small.p + 1, (size_t)N, stream));
     }
     hipLaunchKernelGGL(k_fs_topo, dim3((N + 255) / 256), dim3(256), 0, stream, d_parent.p, N, P.d_heads.p, P.d_small.p + 1, d_nchild.p, d_inodes.p,
                        P.d_ifirst.p, P.d_inch.p, P.d_small.p + 3, P.d_wide.p, wide_cap);
@@ -715,8 +710,8 @@ extern "C" int ugp_fitch_sankoff(int device, uint64_t n_nodes, const uint32_t *p
     }
     if (lvl_off.back() != N) {
         uint32_t bad = 0;
-        FS_TRY(hipMemcpyAsync(&bad, P.d_small.p, 4, hipMemcpyDeviceToHost, stream));
-        FS_TRY(hipStreamSynchronize(stream));
+        UGP_HIP_TRY(hipMemcpyAsync(&bad, P.d_small.p, 4, hipMemcpyDeviceToHost, stream));
+        UGP_HIP_TRY(hipStreamSynchronize(stream));
         if (bad || N > 1) {
             return ugp::set_error(UGP_ERR_INVALID, "tree arrays are not in breadth-first order");
         }
@@ -726,15 +721,15 @@ extern "C" int ugp_fitch_sankoff(int device, uint64_t n_nodes, const uint32_t *p
     uint32_t n_wide = 0;
     {
         // (the level tables have a buffer of their own, sized by the tree -- a caterpillar has as many levels as nodes)
-        FS_TRY(P.d_levels.alloc(3 * (size_t)(n_levels + 1)));   // (level begins, internal-node ranks, and -- below -- the forward sweep's groups)
+        UGP_HIP_TRY(P.d_levels.alloc(3 * (size_t)(n_levels + 1)));   // (level begins, internal-node ranks, and -- below -- the forward sweep's groups)
         uint32_t *d_lvl = P.d_levels.p, *d_ilvl = P.d_levels.p + (n_levels + 1);
-        FS_TRY(hipMemcpyAsync(d_lvl, lvl_off.data(), (n_levels + 1) * 4, hipMemcpyHostToDevice, stream));
+        UGP_HIP_TRY(hipMemcpyAsync(d_lvl, lvl_off.data(), (n_levels + 1) * 4, hipMemcpyHostToDevice, stream));
         hipLaunchKernelGGL(k_fs_level_ranks, dim3((n_levels + 1 + 63) / 64), dim3(64), 0, stream, P.d_heads.p, P.d_small.p + 1, d_lvl, n_levels, d_ilvl);
         uint32_t bad = 0;
-        FS_TRY(hipMemcpyAsync(ilvl_off.data(), d_ilvl, (n_levels + 1) * 4, hipMemcpyDeviceToHost, stream));
-        FS_TRY(hipMemcpyAsync(&bad, P.d_small.p, 4, hipMemcpyDeviceToHost, stream));
-        FS_TRY(hipMemcpyAsync(&n_wide, P.d_small.p + 3, 4, hipMemcpyDeviceToHost, stream));
-        FS_TRY(hipStreamSynchronize(stream));
+        UGP_HIP_TRY(hipMemcpyAsync(ilvl_off.data(), d_ilvl, (n_levels + 1) * 4, hipMemcpyDeviceToHost, stream));
+        UGP_HIP_TRY(hipMemcpyAsync(&bad, P.d_small.p, 4, hipMemcpyDeviceToHost, stream));
+        UGP_HIP_TRY(hipMemcpyAsync(&n_wide, P.d_small.p + 3, 4, hipMemcpyDeviceToHost, stream));
+        UGP_HIP_TRY(hipStreamSynchronize(stream));
         if (bad) return ugp::set_error(UGP_ERR_INVALID, "tree arrays are not in breadth-first order");
     }
     // Polytomies (more than FS_WIDE children): sorted by node = by level, their children cut into chunks of FS_CHUNK rows.  One table
@@ -745,8 +740,8 @@ extern "C" int ugp_fitch_sankoff(int device, uint64_t n_nodes, const uint32_t *p
     if (n_wide) {
         if (n_wide > wide_cap) return ugp::set_error(UGP_ERR_INVALID, "tree arrays are not in breadth-first order");
         std::vector<uint32_t> raw(3 * (size_t)n_wide);
-        FS_TRY(hipMemcpyAsync(raw.data(), P.d_wide.p, raw.size() * 4, hipMemcpyDeviceToHost, stream));
-        FS_TRY(hipStreamSynchronize(stream));
+        UGP_HIP_TRY(hipMemcpyAsync(raw.data(), P.d_wide.p, raw.size() * 4, hipMemcpyDeviceToHost, stream));
+        UGP_HIP_TRY(hipStreamSynchronize(stream));
         std::vector<uint32_t> ord(n_wide);
         for (uint32_t i = 0; i < n_wide; i++) ord[i] = i;
         std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return raw[3 * (size_t)a] < raw[3 * (size_t)b]; });
@@ -762,9 +757,9 @@ extern "C" int ugp_fitch_sankoff(int device, uint64_t n_nodes, const uint32_t *p
         }
         while (L < n_levels) { L++; wl_off[L] = n_wide; cl_off[L] = ci; }
         for (uint32_t l = 0; l < n_levels; l++) max_level_chunks = std::max(max_level_chunks, cl_off[l + 1] - cl_off[l]);
-        FS_TRY(P.d_wtab.alloc(tab.size()));
-        FS_TRY(hipMemcpyAsync(P.d_wtab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, stream));
-        FS_TRY(hipStreamSynchronize(stream));   // (`tab` goes out of scope)
+        UGP_HIP_TRY(P.d_wtab.alloc(tab.size()));
+        UGP_HIP_TRY(hipMemcpyAsync(P.d_wtab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, stream));
+        UGP_HIP_TRY(hipStreamSynchronize(stream));   // (`tab` goes out of scope)
         d_chunk_first = P.d_wtab.p; d_chunk_rows = d_chunk_first + n_chunks; d_wide_node = d_chunk_rows + n_chunks;
         d_wide_nc = d_wide_node + n_wide; d_wide_chunk0 = d_wide_nc + n_wide;
     }
@@ -774,7 +769,7 @@ extern "C" int ugp_fitch_sankoff(int device, uint64_t n_nodes, const uint32_t *p
     for (uint32_t L = 0; L < n_levels; L++) goff[L + 1] = goff[L] + (ilvl_off[L + 1] - ilvl_off[L] + FS_FN - 1) / FS_FN;
     const uint32_t n_groups = goff[n_levels];
     const uint32_t *d_ilvl = P.d_levels.p + (n_levels + 1), *d_goff = P.d_levels.p + 2 * (size_t)(n_levels + 1);
-    FS_TRY(hipMemcpyAsync(P.d_levels.p + 2 * (size_t)(n_levels + 1), goff.data(), (n_levels + 1) * 4, hipMemcpyHostToDevice, stream));
+    UGP_HIP_TRY(hipMemcpyAsync(P.d_levels.p + 2 * (size_t)(n_levels + 1), goff.data(), (n_levels + 1) * 4, hipMemcpyHostToDevice, stream));
     t_topo = lap();
 
     // sites per pass: F takes N * W * 4 bytes.  Passes of up to 16 GiB (or half of the free HBM if that is less; UGP_FITCH_BYTES
@@ -782,7 +777,7 @@ extern "C" int ugp_fitch_sankoff(int device, uint64_t n_nodes, const uint32_t *p
     // four of each (18.9 -> 15.0 ms per call, round 6) -- and the buffer is pooled, and mostly untouched: rows that are never
     // stored (below) are never written either.
     size_t free_b = 0, total_b = 0;
-    FS_TRY(hipMemGetInfo(&free_b, &total_b));
+    UGP_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     uint64_t budget = std::min<uint64_t>((free_b + P.d_F.cap * 4) / 2, 16ull << 30);
     if (const char *e = getenv("UGP_FITCH_BYTES")) budget = strtoull(e, nullptr, 10);
     budget = std::min<uint64_t>(budget, 16ull << 30);   // (k_fs_forward addresses F in 32-bit words)
@@ -794,10 +789,10 @@ extern "C" int ugp_fitch_sankoff(int device, uint64_t n_nodes, const uint32_t *p
     auto &d_vnuc = P.d_vnuc; auto &d_oval = P.d_oval; auto &d_oval2 = P.d_oval2; auto &d_tmp = P.d_tmp;
     auto &d_okey = P.d_okey; auto &d_okey2 = P.d_okey2; auto &d_voff = P.d_voff;
     auto &d_cnt = P.d_cnt; auto &d_segb = P.d_segb;
-    FS_TRY(d_F.alloc(((size_t)N + 1) * W_pass));
-    FS_TRY(d_refw.alloc(W_pass));
-    FS_TRY(d_cnt.alloc((size_t)FS_SEG * 8 + 8));
-    FS_TRY(d_segb.alloc(FS_SEG + 1));
+    UGP_HIP_TRY(d_F.alloc(((size_t)N + 1) * W_pass));
+    UGP_HIP_TRY(d_refw.alloc(W_pass));
+    UGP_HIP_TRY(d_cnt.alloc((size_t)FS_SEG * 8 + 8));
+    UGP_HIP_TRY(d_segb.alloc(FS_SEG + 1));
     std::vector<uint32_t> refw(W_pass), vnode;
     std::vector<uint8_t> vnuc;
     std::vector<uint64_t> voff;
@@ -830,37 +825,37 @@ extern "C" int ugp_fitch_sankoff(int device, uint64_t n_nodes, const uint32_t *p
         unsigned long long seg_cap = 0;
         const uint64_t npad = ((uint64_t)N + 63) & ~63ull;
         const size_t bm_words = (size_t)(npad / 32 * gy) + 4;   // (tile-major, whole 64-bit words per tile: k_fs_init takes one per wave)
-        FS_TRY(P.d_mark8.alloc((size_t)npad * gy));
-        FS_TRY(P.d_stored.alloc(bm_words));
-        FS_TRY(P.d_desc.alloc((size_t)n_groups * gy));
-        if (max_level_chunks) FS_TRY(P.d_part.alloc((size_t)max_level_chunks * gy * 8 * 64));
+        UGP_HIP_TRY(P.d_mark8.alloc((size_t)npad * gy));
+        UGP_HIP_TRY(P.d_stored.alloc(bm_words));
+        UGP_HIP_TRY(P.d_desc.alloc((size_t)n_groups * gy));
+        if (max_level_chunks) UGP_HIP_TRY(P.d_part.alloc((size_t)max_level_chunks * gy * 8 * 64));
         auto grid = [&](uint64_t nodes, int per_wave) { return dim3((unsigned)((nodes + 4ull * per_wave - 1) / (4ull * per_wave) * gy)); };
         for (int attempt = 0; attempt < 2; attempt++) {
-            FS_TRY(hipMemcpyAsync(d_refw.p, refw.data(), (size_t)W * 4, hipMemcpyHostToDevice, stream));
-            FS_TRY(hipMemcpyAsync(d_F.p + (size_t)N * W, refw.data(), (size_t)W * 4, hipMemcpyHostToDevice, stream));   // (row N: what a missing row reads as)
-            FS_TRY(d_voff.upload(voff.data(), voff.size(), stream));
-            FS_TRY(d_vnode.alloc(n_cells)); FS_TRY(d_vnuc.alloc(n_cells));
-            FS_TRY(hipMemsetAsync(P.d_mark8.p, 0, (size_t)npad * gy, stream));
-            FS_TRY(hipMemsetAsync(P.d_small.p + 2, 0, 4, stream));
+            UGP_HIP_TRY(hipMemcpyAsync(d_refw.p, refw.data(), (size_t)W * 4, hipMemcpyHostToDevice, stream));
+            UGP_HIP_TRY(hipMemcpyAsync(d_F.p + (size_t)N * W, refw.data(), (size_t)W * 4, hipMemcpyHostToDevice, stream));   // (row N: what a missing row reads as)
+            UGP_HIP_TRY(d_voff.upload(voff.data(), voff.size(), stream));
+            UGP_HIP_TRY(d_vnode.alloc(n_cells)); UGP_HIP_TRY(d_vnuc.alloc(n_cells));
+            UGP_HIP_TRY(hipMemsetAsync(P.d_mark8.p, 0, (size_t)npad * gy, stream));
+            UGP_HIP_TRY(hipMemsetAsync(P.d_small.p + 2, 0, 4, stream));
             // (round 6) Only the (node, tile) items that hold a cell get a row: mark them, initialise those, then drop the cells in.  The
             // cells are grouped by site, i.e. by tile: they go up in pieces of whole tiles on a stream of their own, and the kernels of a
             // piece run while the next piece crosses PCIe (68 MB from pageable memory are 1.3 ms, the kernels 1.7).
             uint32_t n_piece = (n_cells >= (1u << 20) && gy >= 2) ? std::min<uint32_t>(gy, FS_PIECES) : 1u;
             if (const char *e = getenv("UGP_FITCH_PIECES")) n_piece = (uint32_t)std::max(1, std::min<int>(atoi(e), (int)std::min<uint32_t>(gy, FS_PIECES)));   // (tests: small inputs in pieces)
             if (n_piece > 1 && !P.copy) {
-                FS_TRY(hipStreamCreateWithFlags(&P.copy, hipStreamNonBlocking));
-                for (int k = 0; k < FS_PIECES; k++) FS_TRY(hipEventCreateWithFlags(&P.up[k], hipEventDisableTiming));
+                UGP_HIP_TRY(hipStreamCreateWithFlags(&P.copy, hipStreamNonBlocking));
+                for (int k = 0; k < FS_PIECES; k++) UGP_HIP_TRY(hipEventCreateWithFlags(&P.up[k], hipEventDisableTiming));
             }
             for (uint32_t k = 0; k < n_piece; k++) {
                 const uint32_t y0 = (uint32_t)((uint64_t)gy * k / n_piece), y1 = (uint32_t)((uint64_t)gy * (k + 1) / n_piece), ny = y1 - y0;
                 const uint64_t c0 = voff[std::min<uint64_t>((uint64_t)y0 * 512, n_s)], c1 = voff[std::min<uint64_t>((uint64_t)y1 * 512, n_s)];
                 if (c1 > c0) {
                     hipStream_t up_on = n_piece > 1 ? P.copy : stream;
-                    FS_TRY(hipMemcpyAsync(d_vnode.p + c0, cell_node + c0, (c1 - c0) * 4, hipMemcpyHostToDevice, up_on));
-                    FS_TRY(hipMemcpyAsync(d_vnuc.p + c0, cell_nuc + c0, c1 - c0, hipMemcpyHostToDevice, up_on));
+                    UGP_HIP_TRY(hipMemcpyAsync(d_vnode.p + c0, cell_node + c0, (c1 - c0) * 4, hipMemcpyHostToDevice, up_on));
+                    UGP_HIP_TRY(hipMemcpyAsync(d_vnuc.p + c0, cell_nuc + c0, c1 - c0, hipMemcpyHostToDevice, up_on));
                     if (n_piece > 1) {
-                        FS_TRY(hipEventRecord(P.up[k], P.copy));
-                        FS_TRY(hipStreamWaitEvent(stream, P.up[k], 0));
+                        UGP_HIP_TRY(hipEventRecord(P.up[k], P.copy));
+                        UGP_HIP_TRY(hipStreamWaitEvent(stream, P.up[k], 0));
                     }
                     hipLaunchKernelGGL(k_fs_mark, dim3((unsigned)((c1 - c0 + 255) / 256)), dim3(256), 0, stream, d_voff.p, n_s, d_vnode.p, c0, c1, npad, N,
                                        P.d_mark8.p);
@@ -874,17 +869,17 @@ extern "C" int ugp_fitch_sankoff(int device, uint64_t n_nodes, const uint32_t *p
                     hipLaunchKernelGGL(k_fs_scatter, dim3((unsigned)((c1 - c0 + 255) / 256)), dim3(256), 0, stream, d_F.p, d_refw.p, d_nchild.p, d_voff.p, n_s,
                                        d_vnode.p, d_vnuc.p, c0, c1, W, N, P.d_small.p + 2);
             }
-            FS_TRY(hipMemsetAsync(d_cnt.p, 0, ((size_t)FS_SEG * 8 + 8) * sizeof(unsigned long long), stream));
+            UGP_HIP_TRY(hipMemsetAsync(d_cnt.p, 0, ((size_t)FS_SEG * 8 + 8) * sizeof(unsigned long long), stream));
             // room for the listed changes: without cells on internal nodes a site has at most (cells + 1) of
             // them, and usually far fewer; anything beyond the guess is handled by the exact pass below
             seg_cap = (n_cells + n_s) / FS_SEG * 3 / 2 + 256;
             if (const char *e = getenv("UGP_FITCH_EMIT_CAP")) seg_cap = strtoull(e, nullptr, 10);
-            FS_TRY(d_okey.alloc(seg_cap * FS_SEG));
-            FS_TRY(d_oval.alloc(seg_cap * FS_SEG));
+            UGP_HIP_TRY(d_okey.alloc(seg_cap * FS_SEG));
+            UGP_HIP_TRY(d_oval.alloc(seg_cap * FS_SEG));
             uint32_t cell_flags = 0;
             if (n_cells) {
-                FS_TRY(hipMemcpyAsync(&cell_flags, P.d_small.p + 2, 4, hipMemcpyDeviceToHost, stream));
-                FS_TRY(hipStreamSynchronize(stream));   // (the upload buffers of the caller may be reused / the verdict is needed)
+                UGP_HIP_TRY(hipMemcpyAsync(&cell_flags, P.d_small.p + 2, 4, hipMemcpyDeviceToHost, stream));
+                UGP_HIP_TRY(hipStreamSynchronize(stream));   // (the upload buffers of the caller may be reused / the verdict is needed)
             }
             if (cell_flags & 1u) return ugp::set_error(UGP_ERR_INVALID, "variant node index out of range");
             if (cell_flags & 2u) return ugp::set_error(UGP_ERR_INVALID, "variant allele mask must be 1..15");
@@ -926,9 +921,9 @@ extern "C" int ugp_fitch_sankoff(int device, uint64_t n_nodes, const uint32_t *p
             hipLaunchKernelGGL(k_fs_backward, grid(cnt, FS_NB), dim3(256), 0, stream, d_F.p, d_refw.p, d_parent.p, d_nchild.p, lvl_off[L], lvl_off[L + 1],
                                W, gy, npad, (uint32_t)s0, d_cnt.p, seg_cap, d_okey.p, d_oval.p, P.d_stored.p);
         }
-        FS_TRY(hipGetLastError());
-        FS_TRY(hipMemcpyAsync(h_cnt.data(), d_cnt.p, h_cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-        FS_TRY(hipStreamSynchronize(stream));
+        UGP_HIP_TRY(hipGetLastError());
+        UGP_HIP_TRY(hipMemcpyAsync(h_cnt.data(), d_cnt.p, h_cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+        UGP_HIP_TRY(hipStreamSynchronize(stream));
         unsigned long long n_mut = 0;
         bool overflow = false;
         for (uint32_t g = 0; g < FS_SEG; g++) {
@@ -939,42 +934,42 @@ extern "C" int ugp_fitch_sankoff(int device, uint64_t n_nodes, const uint32_t *p
         h_segb[FS_SEG] = n_mut;
         t_kern += lap();
         if (n_mut == 0) continue;
-        FS_TRY(d_okey2.alloc(n_mut));
-        FS_TRY(d_oval2.alloc(n_mut));
+        UGP_HIP_TRY(d_okey2.alloc(n_mut));
+        UGP_HIP_TRY(d_oval2.alloc(n_mut));
         if (overflow) {   // the guess was too small for some segment: list again, exactly
             hipLaunchKernelGGL(k_fs_emit, grid(N, 1), dim3(256), 0, stream, d_F.p, d_refw.p, d_parent.p, d_nchild.p, N, W, gy, npad, (uint32_t)s0,
                                d_cnt.p + (size_t)FS_SEG * 8, n_mut, d_okey2.p, d_oval2.p, P.d_stored.p);
         } else {
-            FS_TRY(hipMemcpyAsync(d_segb.p, h_segb.data(), h_segb.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+            UGP_HIP_TRY(hipMemcpyAsync(d_segb.p, h_segb.data(), h_segb.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
             hipLaunchKernelGGL(k_fs_compact, dim3(FS_SEG), dim3(256), 0, stream, d_okey.p, d_oval.p, d_segb.p, seg_cap, d_okey2.p, d_oval2.p);
         }
-        FS_TRY(hipGetLastError());
-        FS_TRY(hipStreamSynchronize(stream));   // (d_okey / d_oval are about to become the sort's output)
-        FS_TRY(d_okey.alloc(n_mut));
-        FS_TRY(d_oval.alloc(n_mut));
+        UGP_HIP_TRY(hipGetLastError());
+        UGP_HIP_TRY(hipStreamSynchronize(stream));   // (d_okey / d_oval are about to become the sort's output)
+        UGP_HIP_TRY(d_okey.alloc(n_mut));
+        UGP_HIP_TRY(d_oval.alloc(n_mut));
         // deterministic order: by site, then breadth-first node index
         // (key = site << 32 | node: a stable sort by the node's bits, then by the site's -- the radix passes over the empty bits between
         // the two fields and above the site are not run: 35 of 64 bits at 10 M nodes x 2 048 sites)
         auto bits_of = [](uint64_t n) { unsigned b = 1; while (b < 32 && (n >> b)) b++; return b; };
         const unsigned nb_bits = bits_of(N), sb_bits = bits_of(s1 > 0 ? s1 - 1 : 0);
         size_t tmp_bytes = 0, tmp2 = 0;
-        FS_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_okey2.p, d_okey.p, d_oval2.p, d_oval.p, (size_t)n_mut, 0u, nb_bits, stream));
-        FS_TRY(rocprim::radix_sort_pairs(nullptr, tmp2, d_okey.p, d_okey2.p, d_oval.p, d_oval2.p, (size_t)n_mut, 32u, 32u + sb_bits, stream));
+        UGP_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_okey2.p, d_okey.p, d_oval2.p, d_oval.p, (size_t)n_mut, 0u, nb_bits, stream));
+        UGP_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp2, d_okey.p, d_okey2.p, d_oval.p, d_oval2.p, (size_t)n_mut, 32u, 32u + sb_bits, stream));
         tmp_bytes = std::max(tmp_bytes, tmp2);
-        FS_TRY(d_tmp.alloc(tmp_bytes));
-        FS_TRY(rocprim::radix_sort_pairs(d_tmp.p, tmp_bytes, d_okey2.p, d_okey.p, d_oval2.p, d_oval.p, (size_t)n_mut, 0u, nb_bits, stream));
-        FS_TRY(rocprim::radix_sort_pairs(d_tmp.p, tmp_bytes, d_okey.p, d_okey2.p, d_oval.p, d_oval2.p, (size_t)n_mut, 32u, 32u + sb_bits, stream));
+        UGP_HIP_TRY(d_tmp.alloc(tmp_bytes));
+        UGP_HIP_TRY(rocprim::radix_sort_pairs(d_tmp.p, tmp_bytes, d_okey2.p, d_okey.p, d_oval2.p, d_oval.p, (size_t)n_mut, 0u, nb_bits, stream));
+        UGP_HIP_TRY(rocprim::radix_sort_pairs(d_tmp.p, tmp_bytes, d_okey.p, d_okey2.p, d_oval.p, d_oval2.p, (size_t)n_mut, 32u, 32u + sb_bits, stream));
         // the four arrays of the result are made on the device and land in the handle's vectors directly
-        FS_TRY(P.d_osite.alloc(n_mut)); FS_TRY(P.d_onode.alloc(n_mut)); FS_TRY(P.d_opar.alloc(n_mut)); FS_TRY(P.d_onuc.alloc(n_mut));
+        UGP_HIP_TRY(P.d_osite.alloc(n_mut)); UGP_HIP_TRY(P.d_onode.alloc(n_mut)); UGP_HIP_TRY(P.d_opar.alloc(n_mut)); UGP_HIP_TRY(P.d_onuc.alloc(n_mut));
         hipLaunchKernelGGL(k_fs_split, dim3((unsigned)((n_mut + 255) / 256)), dim3(256), 0, stream, d_okey2.p, d_oval2.p, (uint64_t)n_mut, P.d_osite.p,
                            P.d_onode.p, P.d_opar.p, P.d_onuc.p);
         const size_t base = res->site.size();
         res->site.resize(base + n_mut); res->node.resize(base + n_mut); res->par.resize(base + n_mut); res->nuc.resize(base + n_mut);
-        FS_TRY(hipMemcpyAsync(res->site.data() + base, P.d_osite.p, n_mut * 4, hipMemcpyDeviceToHost, stream));
-        FS_TRY(hipMemcpyAsync(res->node.data() + base, P.d_onode.p, n_mut * 4, hipMemcpyDeviceToHost, stream));
-        FS_TRY(hipMemcpyAsync(res->par.data() + base, P.d_opar.p, n_mut, hipMemcpyDeviceToHost, stream));
-        FS_TRY(hipMemcpyAsync(res->nuc.data() + base, P.d_onuc.p, n_mut, hipMemcpyDeviceToHost, stream));
-        FS_TRY(hipStreamSynchronize(stream));
+        UGP_HIP_TRY(hipMemcpyAsync(res->site.data() + base, P.d_osite.p, n_mut * 4, hipMemcpyDeviceToHost, stream));
+        UGP_HIP_TRY(hipMemcpyAsync(res->node.data() + base, P.d_onode.p, n_mut * 4, hipMemcpyDeviceToHost, stream));
+        UGP_HIP_TRY(hipMemcpyAsync(res->par.data() + base, P.d_opar.p, n_mut, hipMemcpyDeviceToHost, stream));
+        UGP_HIP_TRY(hipMemcpyAsync(res->nuc.data() + base, P.d_onuc.p, n_mut, hipMemcpyDeviceToHost, stream));
+        UGP_HIP_TRY(hipStreamSynchronize(stream));
         t_out += lap();
     }
     if (getenv("UGP_FITCH_VERBOSE"))

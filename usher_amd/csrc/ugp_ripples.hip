@@ -32,16 +32,12 @@
 #include <unordered_set>
 #include <vector>
 
+#include "ugp_dense.hpp"
 #include "ugp_ripples.hpp"
 
 namespace ugp {
-int set_error(int code, const std::string &msg);
-}
-
 namespace {
 
-constexpr uint32_t kBlock = 256;
-constexpr uint32_t kNone = UINT32_MAX;
 constexpr uint64_t kKeyMax = ~0ull;
 constexpr uint64_t kCountBudget = 1ull << 29;   // bytes of bucket prefix sums per candidate chunk
 constexpr uint64_t kSlabBudget = 1ull << 28;    // bytes of per-block top-3 partials
@@ -50,43 +46,7 @@ constexpr uint32_t kTileMax = 64;
 // flags of a candidate
 constexpr uint8_t kElig = 1, kHasUnique = 2, kUnder = 4, kLeaf = 8;
 
-#define RIP_TRY(expr)                                                                                         \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess) return ugp::set_error(UGP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <typename T>
-struct DBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    DBuf() = default;
-    DBuf(const DBuf &) = delete;
-    DBuf &operator=(const DBuf &) = delete;
-    ~DBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t count) {
-        if (count <= n && p) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; n = 0; }
-        hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) n = count;
-        return e;
-    }
-    hipError_t upload(const T *v, size_t count, hipStream_t st) {
-        hipError_t e = alloc(count);
-        if (e != hipSuccess || !count) return e;
-        return hipMemcpyAsync(p, v, count * sizeof(T), hipMemcpyHostToDevice, st);
-    }
-    hipError_t upload(const std::vector<T> &v, hipStream_t st) { return upload(v.data(), v.size(), st); }
-};
-
-// Entry bits: mutated base | ref << 8 | parent state (0 = none on the root path) << 16
-__device__ __forceinline__ uint32_t b_nuc(uint32_t b) { return b & 0xffu; }
-__device__ __forceinline__ uint32_t b_ref(uint32_t b) { return (b >> 8) & 0xffu; }
-__device__ __forceinline__ uint32_t b_anc(uint32_t b) { return (b >> 16) & 0xffu; }
-__device__ __forceinline__ uint32_t lowbit4(uint32_t a) {
-    for (uint32_t b = 0; b < 4; b++) if (a & (1u << b)) return 1u << b;
-    return 0;
-}
+// Entry bits (b_nuc / b_ref / b_anc of ugp_dense.hpp): mutated base | ref << 8 | parent state (0 = none on the root path) << 16
 
 struct Tree {   // device tables, BFS-indexed
     uint32_t n, tp;
@@ -132,7 +92,7 @@ __global__ void __launch_bounds__(kBlock) k_count(Tree t, Branch b) {
     for (uint32_t x = 0; x < b.nb; x++) col[(x + 1) * st] = b.base0[x];
     int E = b.base0[b.nb];
     // the parent's genotype: every mutation strictly above k, against the state it replaced
-    for (uint32_t v = t.parent[k]; v != kNone; v = t.parent[v]) {
+    for (uint32_t v = t.parent[k]; v != kNil; v = t.parent[v]) {
         for (uint32_t e = t.moff[v]; e < t.moff[v + 1]; e++) {
             const int32_t p = t.mpos[e];
             if (p < 0) continue;
@@ -208,7 +168,7 @@ struct Pairs {
 // One thread per pair, the candidates of a tile in LDS; each block folds its tiles into its slab row.
 __global__ void __launch_bounds__(kBlock) k_pairs(Tree t, Branch b, Pairs pr) {
     // [(nb + 1) rows of tile + 1] bucket sums (the padding puts rows 2j and 2i + 1 of one candidate in different banks), then
-    // [tile] rank (kNone: not a candidate here)
+    // [tile] rank (kNil: not a candidate here)
     extern __shared__ int32_t lds[];
     const uint32_t T = pr.tile, TP = T + 1, W = b.nb + 1;
     uint32_t *lrank = (uint32_t *)(lds + (size_t)W * TP);
@@ -220,7 +180,7 @@ __global__ void __launch_bounds__(kBlock) k_pairs(Tree t, Branch b, Pairs pr) {
             lds[row * TP + c] = c < cn ? b.S[(size_t)row * b.Cc + c0 + c] : 0;
         }
         for (uint32_t c = threadIdx.x; c < T; c += blockDim.x) {
-            uint32_t r = kNone;
+            uint32_t r = kNil;
             if (c < cn && !(b.flags[b.c0 + c0 + c] & kUnder)) r = t.rank[b.cand[b.c0 + c0 + c]];
             lrank[c] = r;
         }
@@ -232,7 +192,7 @@ __global__ void __launch_bounds__(kBlock) k_pairs(Tree t, Branch b, Pairs pr) {
             const int32_t *hi = lds + (size_t)(2 * j) * TP, *lo = lds + (size_t)(2 * i + 1) * TP, *tot = lds + (size_t)(W - 1) * TP;
             for (uint32_t c = 0; c < cn; c++) {
                 const uint32_t r = lrank[c];
-                if (r == kNone) continue;
+                if (r == kNil) continue;
                 const int32_t in = hi[c] - lo[c], out = tot[c] - in;
                 if (in <= pr.B) ins3(d0, d1, d2, (uint64_t)(uint32_t)in << 32 | r);
                 if (out <= pr.B) ins3(a0, a1, a2, (uint64_t)(uint32_t)out << 32 | r);
@@ -265,8 +225,6 @@ __global__ void k_fetch(const uint32_t *idx, uint32_t n, const int32_t *score, c
 
 }  // namespace
 
-namespace ugp {
-
 struct RipState {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -278,7 +236,7 @@ struct RipState {
     DBuf<int32_t> d_mpos;
     DBuf<uint8_t> d_leaf;
     // candidates of the last num_descendants
-    uint32_t cand_nd = kNone;
+    uint32_t cand_nd = kNil;
     std::vector<uint32_t> cand;
     DBuf<uint32_t> d_cand;
     // per-branch workspace
@@ -298,10 +256,11 @@ void rip_free(RipState *s) {
     delete s;
 }
 
-int rip_attach(const ugp_tree_desc *tree, const uint32_t *name_rank, int device, RipState **out) {
+int rip_attach(const ugp_tree_desc *tree, const uint32_t *name_rank, const std::vector<uint32_t> &bfs2dfs, int device, RipState **out) {
     if (!tree || !out || !tree->parent || !tree->mut_off || !name_rank) return set_error(UGP_ERR_INVALID, "null argument");
     const uint64_t N = tree->n_nodes;
     if (N == 0 || N >= (1ull << 31)) return set_error(UGP_ERR_INVALID, "node count out of range");
+    if (bfs2dfs.size() != N) return set_error(UGP_ERR_INVALID, "tree does not match the handle");
     const uint64_t Mu = tree->mut_off[N];
     if (Mu >= (1ull << 32)) return set_error(UGP_ERR_UNSUPPORTED, "more than 2^32 mutation entries");
     if (Mu && (!tree->mut_pos || !tree->mut_ref || !tree->mut_nuc)) return set_error(UGP_ERR_INVALID, "null mutation arrays");
@@ -311,13 +270,13 @@ int rip_attach(const ugp_tree_desc *tree, const uint32_t *name_rank, int device,
         S->device = device;
         S->n = (uint32_t)N;
         S->parent.assign(tree->parent, tree->parent + N);
-        S->parent[0] = kNone;
+        S->parent[0] = kNil;
         for (uint64_t j = 1; j < N; j++)
             if (S->parent[j] >= j) { delete S; return set_error(UGP_ERR_INVALID, "parent[] is not in breadth-first order"); }
         S->rank.assign(name_rank, name_rank + N);
-        S->inv_rank.assign(N, kNone);
+        S->inv_rank.assign(N, kNil);
         for (uint64_t j = 0; j < N; j++) {
-            if (S->rank[j] >= N || S->inv_rank[S->rank[j]] != kNone) { delete S; return set_error(UGP_ERR_INVALID, "name_rank is not a permutation"); }
+            if (S->rank[j] >= N || S->inv_rank[S->rank[j]] != kNil) { delete S; return set_error(UGP_ERR_INVALID, "name_rank is not a permutation"); }
             S->inv_rank[S->rank[j]] = (uint32_t)j;
         }
         S->moff.resize(N + 1);
@@ -332,19 +291,12 @@ int rip_attach(const ugp_tree_desc *tree, const uint32_t *name_rank, int device,
         }
         if (maxpos >= (1 << 28)) { delete S; return set_error(UGP_ERR_UNSUPPORTED, "mutation position above 2^28"); }
         S->tp = (uint32_t)(maxpos + 1);
-        // subtree sizes (tree_num_leaves of main.cpp:280-289: nodes, self included), leaves, a preorder for "under nid"
-        std::vector<uint32_t> sz(N, 1), dfs(N), dend(N);
+        // subtree sizes (tree_num_leaves of main.cpp:280-289: nodes, self included), leaves, the handle's preorder for "under nid"
+        const std::vector<uint32_t> &dfs = bfs2dfs;
+        std::vector<uint32_t> sz(N, 1), dend(N);
         std::vector<uint8_t> leaf(N, 1);
         for (uint64_t j = N; j-- > 1;) { sz[S->parent[j]] += sz[j]; leaf[S->parent[j]] = 0; }
-        {
-            std::vector<uint32_t> next(N, 0);   // next free preorder slot below each node
-            dfs[0] = 0; next[0] = 1;
-            for (uint64_t j = 1; j < N; j++) {   // BFS: a parent is placed before its children, siblings in index order
-                const uint32_t pa = S->parent[j];
-                dfs[j] = next[pa]; next[pa] += sz[j]; next[j] = dfs[j] + 1;
-            }
-            for (uint64_t j = 0; j < N; j++) dend[j] = dfs[j] + sz[j];
-        }
+        for (uint64_t j = 0; j < N; j++) dend[j] = dfs[j] + sz[j];
         S->size = sz;
         // parent state of every non-masked entry: the nearest entry above it at its position (per position, entries in preorder)
         {
@@ -405,7 +357,7 @@ int rip_run(RipState *S, const ugp_ripples_opts *o, const uint32_t *branches, ui
     for (uint64_t i = 0; i < n; i++) if (branches[i] >= S->n) return set_error(UGP_ERR_INVALID, "branch index out of range");
     *n_out = 0;
     if (!n) return UGP_OK;
-    RIP_TRY(hipSetDevice(S->device));
+    UGP_HIP_TRY(hipSetDevice(S->device));
     hipStream_t st = S->stream;
     const uint32_t N = S->n;
     // UGP_RIPPLES_LIMITS="count_bytes,slab_bytes,lds_ints" lowers the workspace limits (a test hook: small trees then take the
@@ -421,10 +373,10 @@ int rip_run(RipState *S, const ugp_ripples_opts *o, const uint32_t *branches, ui
     }
     if (S->cand_nd != o->num_descendants) {
         S->cand.clear();
-        S->cand_of.assign(N, kNone);
+        S->cand_of.assign(N, kNil);
         for (uint32_t k = 0; k < N; k++)
             if (S->size[k] >= o->num_descendants) { S->cand_of[k] = (uint32_t)S->cand.size(); S->cand.push_back(k); }
-        RIP_TRY(S->d_cand.upload(S->cand, st));
+        UGP_HIP_TRY(S->d_cand.upload(S->cand, st));
         S->cand_nd = o->num_descendants;
     }
     const uint32_t C = (uint32_t)S->cand.size();
@@ -446,7 +398,7 @@ int rip_run(RipState *S, const ugp_ripples_opts *o, const uint32_t *branches, ui
         const int B = orig - o->parsimony_improvement;
         // Pruned_Sample of the root path (main.cpp:68-90, 317-325): the lowest occurrence of a position wins
         rows.clear(); seen.clear();
-        for (uint32_t v = nid; v != kNone; v = S->parent[v])
+        for (uint32_t v = nid; v != kNil; v = S->parent[v])
             for (uint32_t e = S->moff[v]; e < S->moff[v + 1]; e++) {
                 const int32_t p = S->mpos[e];
                 const uint8_t nuc = (uint8_t)(S->mbits[e] & 0xffu), ref = (uint8_t)((S->mbits[e] >> 8) & 0xffu);
@@ -481,11 +433,11 @@ int rip_run(RipState *S, const ugp_ripples_opts *o, const uint32_t *branches, ui
                 btab[p] = 2 * lb + ((lb < M && rows[lb].pos == (int32_t)p) ? 1u : 0u);
             }
         }
-        RIP_TRY(S->qpos.upload(qpos, st)); RIP_TRY(S->qnuc.upload(qnuc, st));
-        RIP_TRY(S->btab.upload(btab, st)); RIP_TRY(S->srow.upload(srow, st));
-        RIP_TRY(S->base0.upload(base0, st)); RIP_TRY(S->ij.upload(ij, st));
-        RIP_TRY(S->score.alloc(C)); RIP_TRY(S->flags.alloc(C)); RIP_TRY(S->minE.alloc(1));
-        RIP_TRY(hipMemsetD32Async((hipDeviceptr_t)S->minE.p, INT_MAX, 1, st));
+        UGP_HIP_TRY(S->qpos.upload(qpos, st)); UGP_HIP_TRY(S->qnuc.upload(qnuc, st));
+        UGP_HIP_TRY(S->btab.upload(btab, st)); UGP_HIP_TRY(S->srow.upload(srow, st));
+        UGP_HIP_TRY(S->base0.upload(base0, st)); UGP_HIP_TRY(S->ij.upload(ij, st));
+        UGP_HIP_TRY(S->score.alloc(C)); UGP_HIP_TRY(S->flags.alloc(C)); UGP_HIP_TRY(S->minE.alloc(1));
+        UGP_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)S->minE.p, INT_MAX, 1, st));
         if (48ull * P > kSlabBudget) return set_error(UGP_ERR_UNSUPPORTED, "a branch has more than 5,592,405 valid breakpoint pairs");
         const uint32_t Cc = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(C, lim.count / (4ull * (nb + 1))));
         const uint32_t fit = (uint32_t)(lim.lds / (nb + 1)), tile = fit >= 2 ? std::min(kTileMax, fit - 1) : 1u;
@@ -493,9 +445,9 @@ int rip_run(RipState *S, const ugp_ripples_opts *o, const uint32_t *branches, ui
         if (lds > 64 * 1024) return set_error(UGP_ERR_UNSUPPORTED, "too many sample rows for one LDS tile");
         const uint32_t tiles_all = (C + tile - 1) / tile;
         const uint32_t nblk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({1024, tiles_all, lim.slab / (48ull * P)}));
-        RIP_TRY(S->S.alloc((size_t)(nb + 1) * Cc));
-        RIP_TRY(S->slab.alloc((size_t)nblk * P * 6)); RIP_TRY(S->top.alloc((size_t)P * 6));
-        RIP_TRY(hipMemsetAsync(S->slab.p, 0xff, (size_t)nblk * P * 6 * sizeof(uint64_t), st));
+        UGP_HIP_TRY(S->S.alloc((size_t)(nb + 1) * Cc));
+        UGP_HIP_TRY(S->slab.alloc((size_t)nblk * P * 6)); UGP_HIP_TRY(S->top.alloc((size_t)P * 6));
+        UGP_HIP_TRY(hipMemsetAsync(S->slab.p, 0xff, (size_t)nblk * P * 6 * sizeof(uint64_t), st));
         Pairs pr{P, tile, 0, B, S->ij.p, S->slab.p};
         for (uint32_t c0 = 0; c0 < C; c0 += Cc) {
             const uint32_t cc = std::min(Cc, C - c0);
@@ -506,12 +458,12 @@ int rip_run(RipState *S, const ugp_ripples_opts *o, const uint32_t *branches, ui
             k_pairs<<<std::min(nblk, pr.ntiles), kBlock, lds, st>>>(t, b, pr);
         }
         k_merge<<<(P + kBlock - 1) / kBlock, kBlock, 0, st>>>(pr, nblk, S->top.p);
-        RIP_TRY(hipGetLastError());
+        UGP_HIP_TRY(hipGetLastError());
         top.resize((size_t)P * 6);
         int32_t minE = 0;
-        RIP_TRY(hipMemcpyAsync(top.data(), S->top.p, top.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        RIP_TRY(hipMemcpyAsync(&minE, S->minE.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        RIP_TRY(hipStreamSynchronize(st));
+        UGP_HIP_TRY(hipMemcpyAsync(top.data(), S->top.p, top.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        UGP_HIP_TRY(hipMemcpyAsync(&minE, S->minE.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        UGP_HIP_TRY(hipStreamSynchronize(st));
         // the donor-acceptor choice (:594-606) on the top-3 lists: nid removed, the first two of each list decide
         ev.clear(); fidx.clear();
         const uint32_t nid_rank = S->rank[nid];
@@ -539,13 +491,13 @@ int rip_run(RipState *S, const ugp_ripples_opts *o, const uint32_t *branches, ui
         }
         if (ev.empty()) continue;
         const uint32_t nf = (uint32_t)fidx.size();
-        RIP_TRY(S->fidx.upload(fidx, st)); RIP_TRY(S->fscore.alloc(nf)); RIP_TRY(S->fflags.alloc(nf));
+        UGP_HIP_TRY(S->fidx.upload(fidx, st)); UGP_HIP_TRY(S->fscore.alloc(nf)); UGP_HIP_TRY(S->fflags.alloc(nf));
         k_fetch<<<(nf + kBlock - 1) / kBlock, kBlock, 0, st>>>(S->fidx.p, nf, S->score.p, S->flags.p, S->fscore.p, S->fflags.p);
-        RIP_TRY(hipGetLastError());
+        UGP_HIP_TRY(hipGetLastError());
         fscore.resize(nf); fflags.resize(nf);
-        RIP_TRY(hipMemcpyAsync(fscore.data(), S->fscore.p, nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        RIP_TRY(hipMemcpyAsync(fflags.data(), S->fflags.p, nf, hipMemcpyDeviceToHost, st));
-        RIP_TRY(hipStreamSynchronize(st));
+        UGP_HIP_TRY(hipMemcpyAsync(fscore.data(), S->fscore.p, nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        UGP_HIP_TRY(hipMemcpyAsync(fflags.data(), S->fflags.p, nf, hipMemcpyDeviceToHost, st));
+        UGP_HIP_TRY(hipStreamSynchronize(st));
         // is_sibling: a leaf, or one of the final ties (eligible, set difference = the minimum) that has a unique mutation
         auto sib = [&](uint32_t x) {
             const uint8_t f = fflags[x];
