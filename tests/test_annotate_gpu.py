@@ -6,6 +6,7 @@ import pytest
 
 from oracle import capi
 from tests import annotate_ref as A
+from tests.dense_cases import awkward_rows as _awkward_rows
 from tests import stdorder
 from tests import synth
 from tests import uncertainty_ref as U
@@ -51,31 +52,6 @@ def test_alleles_and_descendants(which):
     d = pl.clade_descendants(clades, pc, pn)
     assert d.tolist() == [A.descendants(arrays, clades[c], v) for c, v in zip(pc, pn)]
     pl.close()
-
-
-def _awkward_rows(arrays, rng, k):
-    """Rows at tree positions with a repeated position (G and N, two N rows) and masked rows, sorted by position."""
-    pos = np.asarray(arrays["mut_pos"])
-    sites = np.unique(pos[pos > 0])
-    take = rng.choice(sites, size=min(len(sites), 12), replace=False)
-    rows = []
-    for p in take:
-        i = int(np.flatnonzero(pos == p)[0])
-        r, m = int(arrays["mut_ref"][i]), int(arrays["mut_nuc"][i])
-        rows.append((int(p), r, m if rng.random() < 0.7 else 15))
-    dup = take[k % len(take)]
-    i = int(np.flatnonzero(pos == dup)[0])
-    r = int(arrays["mut_ref"][i])
-    rows.append((int(dup), r, 15))
-    if k % 2:
-        rows.append((int(dup), r, 15))
-        rows.append((int(dup), r, [1, 2, 4, 8][k % 4]))
-    rows.append((-int(rng.integers(1, 50)), 8, 15))
-    if k % 3 == 0:
-        rows.append((-int(rng.integers(1, 50)), 2, 1))
-    rows.sort(key=lambda t: t[0])
-    return {"pos": np.asarray([t[0] for t in rows], np.int32), "ref": np.asarray([t[1] for t in rows], np.int8),
-            "nuc": np.asarray([t[2] for t in rows], np.int8), "is_missing": np.zeros(len(rows), np.int8)}
 
 
 @pytest.mark.parametrize("which", [0, 1, 2])
