@@ -248,6 +248,34 @@ int ugp_clade_descendants(ugp_mat *mat, const uint64_t *clade_off, const uint32_
                           const uint32_t *pair_clade, const uint32_t *pair_node /* BFS */, uint64_t n_pairs, uint32_t *out);
 int ugp_annotate_search(ugp_mat *mat, const ugp_queries *q, uint32_t cap, int32_t *best /* [n_queries] */, uint32_t *tie_dfs /* [n_queries * cap] */,
                         uint32_t *tie_count /* [n_queries] */);
+/* matUtils extract's "k nearest samples" (get_nearby, matUtils/select.cpp:206-276) for a batch of queries.  ugp_nearest_attach makes
+ * the depth-first tables of `tree` (the handle's tree: same parent array; arrays are copied) and a leaf prefix table, once per handle.
+ * ugp_nearest_k: query i is a node (BFS index; any node, not only a leaf) and its own k[i] > 0.  As the reference: climbing from the
+ * node itself, last_anc is the last ancestor with <= k leaves (the node to begin with) and anc the first with more; the result is
+ * the leaves of last_anc in depth-first order, then the leaves under anc that are not strict descendants of last_anc (is_ancestor
+ * starts at the parent: a leaf last_anc is a candidate of its own search and may be listed twice, as in the reference), ascending by
+ * the number of mutation entries -- masked ones included -- between the leaf and anc, until k are held.  Two rules follow from
+ * the reference's loop and are kept: NO ancestor with more than k leaves -> an EMPTY result (count 0, anc UINT32_MAX); a node
+ * with more than k leaves of its own -> anc == last_anc == the node and ALL its leaves (count > k; the first min(count,
+ * out_stride) are written).  One deviation: the reference orders equal distances by whatever its unstable std::sort leaves; here
+ * ties come in depth-first order (a stable sort).  The reference's set is therefore unique only when n_at_cut equals the number
+ * of entries at distance cut_dist in the result.
+ * Row i of out_nodes (BFS indices) / out_dist (distance to anc) has out_stride slots, the first min(count, out_stride) written;
+ * out_stride >= the largest k.  An out-of-range node, k = 0 or a smaller out_stride is UGP_ERR_INVALID before anything is written.
+ * Queries run in chunks of bounded device workspace; ugp_nearest_k_chunked (test hook) sets the queries per chunk (0: default). */
+typedef struct ugp_nearest_info {
+    uint32_t count;      /* size of the reference's result                                                        */
+    uint32_t anc;        /* BFS index of the first ancestor with more than k leaves; UINT32_MAX: none             */
+    uint32_t last_anc;   /* BFS index of the last ancestor with at most k leaves                                  */
+    uint32_t cut_dist;   /* d*: the largest distance among the candidates taken (0 when none is taken)            */
+    uint32_t n_at_cut;   /* candidates at distance d* (0 when none is taken)                                      */
+} ugp_nearest_info;
+int ugp_nearest_attach(ugp_mat *mat, const ugp_tree_desc *tree);
+int ugp_nearest_k(ugp_mat *mat, uint64_t n_queries, const uint32_t *nodes /* BFS */, const uint32_t *k, uint32_t out_stride,
+                  uint32_t *out_nodes /* [n_queries * out_stride] */, uint32_t *out_dist /* [n_queries * out_stride] */,
+                  ugp_nearest_info *info /* [n_queries] */);
+int ugp_nearest_k_chunked(ugp_mat *mat, uint64_t n_queries, const uint32_t *nodes, const uint32_t *k, uint32_t out_stride,
+                          uint32_t *out_nodes, uint32_t *out_dist, ugp_nearest_info *info, uint32_t chunk_queries);
 /* RIPPLES (ripples/main.cpp): the options of :22-44 that the search reads.  branch_len >= 1 and parsimony_improvement >= 0
  * (UGP_ERR_INVALID otherwise: the reference's size_t arithmetic of :445-453 is not reproduced for negative values). */
 typedef struct ugp_ripples_opts {

@@ -84,6 +84,9 @@ SYMBOLS = {
     "ugp_clade_alleles": (C.c_int, [P, P, P, C.c_uint64, P, P, P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ugp_clade_descendants": (C.c_int, [P, P, P, C.c_uint64, P, P, C.c_uint64, P]),
     "ugp_annotate_search": (C.c_int, [P, C.POINTER(ugp_queries), C.c_uint32, P, P, P]),
+    "ugp_nearest_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc)]),
+    "ugp_nearest_k": (C.c_int, [P, C.c_uint64, P, P, C.c_uint32, P, P, P]),
+    "ugp_nearest_k_chunked": (C.c_int, [P, C.c_uint64, P, P, C.c_uint32, P, P, P, C.c_uint32]),
     "ugp_ripples_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc), P]),
     "ugp_ripples": (C.c_int, [P, C.POINTER(ugp_ripples_opts), P, C.c_uint64, P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ugp_subtree_mask": (C.c_int, [P, C.c_uint32, C.c_uint32, C.c_uint32, P]),

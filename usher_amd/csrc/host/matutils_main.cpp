@@ -2,12 +2,15 @@
 //
 //   matutils-amd uncertainty -i tree.pb -s samples.txt [-e epps.tsv] [-o placements.tsv] [-T n] [--device k]
 //   matutils-amd annotate -i tree.pb -o out.pb [-c | -M | -P | -C file ...] [-f -m -s -p -l -d -u -D -T] [--device k]
+//   matutils-amd extract -i tree.pb [-s samples.txt] [-k sample:k] [-Y y] [-a -b -P n] [-u -t -o file] [-d dir] [--reference-ties]
 //
 // uncertainty_main / findEPPs_wrapper (uncertainty.cpp:279-339, 541-560): load the MAT, uncondense its leaves, read the sample
 // names, and for every sample report its equally parsimonious placements and neighborhood size (-e) and the candidate parents
 // (-o), in the reference's file formats.  The per-sample searches run on the device as one batch (ugp_uncertainty).
 // annotate_main (annotate.cpp:94-156): clade roots from exemplar samples, mutation sets, paths or node ids, written into the
 // .pb metadata.  Exemplar allele counts, the searches and the overlap counts run on the device (ugp_annotate.hip).
+// extract_main (extract.cpp:149-640): sample selection by name, nearest-k context (-k, -Y: get_nearby, one batched ugp_nearest_k
+// call) and the three linear filters, written as a sample list, a newick tree or a .pb of the induced subtree.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -37,7 +40,8 @@ void usage(FILE *f) {
             "  -o, --record-placements  two-column tsv of potential parents for each sample\n"
             "  -T, --threads            accepted for compatibility (the searches run on the device)\n"
             "      --device             HIP device ordinal [0]\n"
-            "  (-d / --dropout-mutations is not supported)\n");
+            "  (-d / --dropout-mutations is not supported)\n"
+            "       matutils-amd annotate --help | matutils-amd extract --help\n");
 }
 
 int uncertainty(int argc, char **argv) {
@@ -864,12 +868,341 @@ int annotate(int argc, char **argv) {   // annotate_main, :94-156
     return 0;
 }
 
+
+// ---- extract (extract.cpp, select.cpp) ----------------------------------------------------------------------------
+
+void extract_usage(FILE *f) {
+    fprintf(f,
+            "Usage: matutils-amd extract -i tree.pb [-s samples.txt] [-k sample:k] [-Y y] [-a n] [-b n] [-P n] [-u used.txt] [-t tree.nh]\n"
+            "       [-o out.pb] [-d dir] [-T n] [--device k] [--reference-ties]\n"
+            "  -i, --input-mat          input mutation-annotated tree [REQUIRED]\n"
+            "  -s, --samples            select samples by explicitly naming them, one per line\n"
+            "  -k, --nearest-k          select a sample and the nearest k samples to it, formatted as sample:k\n"
+            "  -Y, --select-nearest     add the y nearest samples to each selected sample, without duplicates\n"
+            "  -a, --max-parsimony      select samples with at most this many mutations on their terminal branch\n"
+            "  -b, --max-branch-length  select samples with no longer branch than this in their ancestry\n"
+            "  -P, --max-path-length    select samples with a total path length of at most this\n"
+            "  -u, --used-samples       write a text file of the selected sample ids\n"
+            "  -t, --write-tree         write a newick tree of the selected samples\n"
+            "  -o, --write-mat          write the selected tree as a new protobuf\n"
+            "  -d, --output-directory   directory of the output files [./]\n"
+            "  -T, --threads            accepted for compatibility (the searches run on the device)\n"
+            "      --device             HIP device ordinal [0]\n"
+            "      --reference-ties     order equal distances as the reference's std::sort does (host, slow)\n");
+}
+
+std::vector<std::string> read_sample_names(const std::string &fname) {   // select.cpp:8-36
+    std::vector<std::string> names;
+    std::ifstream in(fname);
+    if (!in) { fprintf(stderr, "ERROR: Could not open the file: %s!\n", fname.c_str()); exit(1); }
+    std::string line;
+    bool warned = false;
+    while (std::getline(in, line)) {
+        std::vector<std::string> w;
+        split_ws(line, w);
+        if (w.size() > 1 && !warned) {
+            fprintf(stderr, "WARNING: Input file %s contains excess columns; ignoring\n", fname.c_str());
+            warned = true;
+        } else if (w.empty()) {
+            fprintf(stderr, "WARNING: Empty line in input file %s; ignoring\n", fname.c_str());
+            continue;
+        }
+        std::string name = w[0];
+        if (name.back() == '\r') name.pop_back();
+        names.push_back(name);
+    }
+    return names;
+}
+
+std::vector<std::string> leaf_ids(const uh::Tree &T) {   // get_leaves_ids
+    std::vector<std::string> ids;
+    for (const uh::Node *n : T.leaves()) ids.push_back(n->id);
+    return ids;
+}
+
+uh::Node *must_get(const uh::Tree &T, const std::string &id) {   // (the reference dereferences the null pointer)
+    uh::Node *n = T.get_node(id);
+    if (!n) { fprintf(stderr, "ERROR: %s is not present in the tree!\n", id.c_str()); exit(1); }
+    return n;
+}
+
+std::vector<std::string> get_parsimony_samples(const uh::Tree &T, std::vector<std::string> check, int max_parsimony) {   // select.cpp:113-127
+    if (check.empty()) check = leaf_ids(T);
+    std::vector<std::string> good;
+    for (const std::string &s : check) {
+        const uh::Node *n = must_get(T, s);
+        if (n->mutations.size() <= static_cast<size_t>(max_parsimony)) good.push_back(n->id);
+    }
+    return good;
+}
+
+std::vector<std::string> get_short_steppers(const uh::Tree &T, std::vector<std::string> check, int max_mutations) {   // select.cpp:278-307
+    std::vector<std::string> good;
+    if (check.empty()) check = leaf_ids(T);
+    for (const std::string &s : check) {
+        uh::Node *n = must_get(T, s);
+        if (n->mutations.size() > static_cast<size_t>(max_mutations)) continue;
+        bool bad = false;
+        for (const uh::Node *a : T.rsearch(n, false))
+            if (a->mutations.size() > static_cast<size_t>(max_mutations)) { bad = true; break; }
+        if (!bad) good.push_back(s);
+    }
+    return good;
+}
+
+std::vector<std::string> get_short_paths(const uh::Tree &T, const std::vector<std::string> &check, int max_path) {   // select.cpp:309-335
+    std::vector<std::string> good;
+    const std::unordered_set<std::string> set(check.begin(), check.end());
+    std::unordered_map<const uh::Node *, size_t> len;
+    for (const uh::Node *n : T.dfs()) {
+        if (!n->is_leaf()) {
+            len[n] = n->is_root() ? 0 : len[n->parent] + n->mutations.size();
+        } else if (n->parent && len[n->parent] + n->mutations.size() <= static_cast<size_t>(max_path)) {
+            if (check.empty() || set.count(n->id)) good.push_back(n->id);
+        }
+    }
+    return good;
+}
+
+// get_nearby (select.cpp:206-276) for a batch of (sample, k): the searches on the device (ugp_nearest_k), names out.
+struct NearestSearch {
+    uh::Tree &T;
+    int device;
+    bool reference_ties;
+    std::vector<uh::Node *> bfs;
+    ugp_mat *h = nullptr;
+    NearestSearch(uh::Tree &t, int dev, bool ties) : T(t), device(dev), reference_ties(ties) {}
+    ~NearestSearch() { if (h) ugp_mat_destroy(h); }
+    void up() {
+        if (h) return;
+        bfs = T.bfs();
+        const uint64_t N = bfs.size();
+        for (uint64_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
+        std::vector<uint32_t> parent(N);
+        std::vector<uint64_t> mut_off(N + 1, 0);
+        std::vector<int32_t> pos;
+        std::vector<uint8_t> ref, par, nuc;
+        for (uint64_t j = 0; j < N; j++) {
+            parent[j] = bfs[j]->parent ? bfs[j]->parent->flat_index : UINT32_MAX;
+            for (const auto &m : bfs[j]->mutations) {
+                pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
+            }
+            mut_off[j + 1] = pos.size();
+        }
+        const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+        if (ugp_mat_create(&desc, device, &h) != UGP_OK) lib_fail("ugp_mat_create");
+        if (ugp_nearest_attach(h, &desc) != UGP_OK) lib_fail("ugp_nearest_attach");
+    }
+    // The literal sort of one query between the device's anc and last_anc: Tree::get_leaves' order into std::sort.
+    std::vector<std::string> literal(uh::Node *anc, uh::Node *last, size_t k) const {
+        std::vector<std::string> keep;
+        for (const uh::Node *l : T.leaves(last)) keep.push_back(l->id);
+        struct NodeDist { const uh::Node *node; uint32_t num_mut; };
+        std::vector<NodeDist> dist;
+        for (const uh::Node *l : T.leaves(anc)) {
+            if (T.is_ancestor(last, l)) continue;
+            uint32_t d = 0;
+            for (const uh::Node *a = l; a != anc; a = a->parent) d += (uint32_t)a->mutations.size();
+            dist.push_back({l, d});
+        }
+        std::sort(dist.begin(), dist.end(), [](const NodeDist &a, const NodeDist &b) { return a.num_mut < b.num_mut; });
+        for (const NodeDist &n : dist) { if (keep.size() == k) break; keep.push_back(n.node->id); }
+        return keep;
+    }
+    std::vector<std::vector<std::string>> run(const std::vector<uh::Node *> &nodes, size_t k) {
+        up();
+        const size_t n = nodes.size();
+        std::vector<std::vector<std::string>> out(n);
+        if (!n) return out;
+        if (k > bfs.size()) k = bfs.size();   // more than every leaf: the same (empty) answer
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<uint32_t> qn(n), qk(n, (uint32_t)k), on, od;
+        std::vector<ugp_nearest_info> info(n);
+        for (size_t i = 0; i < n; i++) qn[i] = nodes[i]->flat_index;
+        // rows of k slots, a bounded number of them per call
+        const size_t per = std::max<size_t>(1, (size_t(1) << 24) / k);
+        for (size_t i0 = 0; i0 < n; i0 += per) {
+            const size_t m = std::min(per, n - i0);
+            on.resize(m * k); od.resize(m * k);
+            if (ugp_nearest_k(h, m, qn.data() + i0, qk.data() + i0, (uint32_t)k, on.data(), od.data(), info.data() + i0) != UGP_OK) lib_fail("ugp_nearest_k");
+            for (size_t i = 0; i < m; i++) {
+                const ugp_nearest_info &f = info[i0 + i];
+                if (f.anc == UINT32_MAX) continue;
+                if (f.count > k) {   // the sample is an internal node with more than k leaves: all of them (the reference's loop)
+                    for (const uh::Node *l : T.leaves(bfs[f.last_anc])) out[i0 + i].push_back(l->id);
+                    continue;
+                }
+                if (reference_ties) { out[i0 + i] = literal(bfs[f.anc], bfs[f.last_anc], k); continue; }
+                for (uint32_t s = 0; s < f.count; s++) out[i0 + i].push_back(bfs[on[i * k + s]]->id);
+            }
+        }
+        fprintf(stderr, "Nearest-k search of %zu samples: %.1f msec\n", n,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        return out;
+    }
+};
+
+int extract(int argc, char **argv) {   // extract_main, extract.cpp:149-640, 867-888 for the options of extract_usage
+    std::string in_mat, fsamples, nearest_k, fused, ftree, fmat, dir = "./";
+    int max_parsimony = -1, max_branch = -1, max_path = -1, device = 0;
+    size_t select_nearest = 0;
+    bool reference_ties = false;
+    static const char *const unsupported[] = {
+        "-K", "--nearest-k-batch", "-v", "--write-vcf", "-j", "--write-json", "-c", "--clade", "-m", "--mutation", "-H", "--match",
+        "-V", "--closest-relatives", "-q", "--break-ties", "--within-distance", "--distance-threshold", "-z", "--set-size", "-W", "--add-random",
+        "-Z", "--limit-to-lca", "-y", "--reroot", "--write-reroot-reference", "-R", "--resolve-polytomies", "-e", "--max-epps",
+        "--max-mutation-density", "-I", "--get-internal-descendents", "-U", "--from-mrca", "-r", "--get-representative", "-p", "--prune",
+        "-S", "--sample-paths", "-C", "--clade-paths", "-A", "--all-paths", "--write-diff", "-n", "--no-genotypes", "-O", "--collapse-tree",
+        "-l", "--write-taxodium", "-G", "--x-scale", "-B", "--title", "-D", "--description", "-J", "--include-nt", "-F", "--extra-fields",
+        "-E", "--retain-branch-length", "-N", "--minimum-subtrees-size", "-X", "--usher-single-subtree-size", "-x", "--usher-minimum-subtrees-size",
+        "--usher-clades-txt", "--usher-anchor-samples", "-Q", "--dump-metadata", "-L", "--whitelist", "--load-all-metadata", "-M", "--metadata",
+        "-g", "--input-gtf", "-f", "--input-fasta"};
+    for (int i = 0; i < argc; i++) {
+        const std::string a = argv[i];
+        auto val = [&](std::string &dst) -> bool {
+            if (i + 1 >= argc) { fprintf(stderr, "ERROR: %s needs a value\n", a.c_str()); extract_usage(stderr); return false; }
+            dst = argv[++i];
+            return true;
+        };
+        auto ival = [&](long &dst) -> bool {
+            std::string t;
+            if (!val(t)) return false;
+            char *end = nullptr;
+            dst = strtol(t.c_str(), &end, 10);
+            if (t.empty() || *end) { fprintf(stderr, "ERROR: bad value %s for %s\n", t.c_str(), a.c_str()); extract_usage(stderr); return false; }
+            return true;
+        };
+        std::string tmp;
+        long v = 0;
+        bool ok = true;
+        if (a == "-i" || a == "--input-mat") ok = val(in_mat);
+        else if (a == "-s" || a == "--samples") ok = val(fsamples);
+        else if (a == "-k" || a == "--nearest-k") ok = val(nearest_k);
+        else if (a == "-Y" || a == "--select-nearest") { ok = ival(v); if (ok && v < 0) { fprintf(stderr, "ERROR: bad value %ld for %s\n", v, a.c_str()); return 1; } select_nearest = (size_t)v; }
+        else if (a == "-a" || a == "--max-parsimony") { ok = ival(v); max_parsimony = (int)v; }
+        else if (a == "-b" || a == "--max-branch-length") { ok = ival(v); max_branch = (int)v; }
+        else if (a == "-P" || a == "--max-path-length") { ok = ival(v); max_path = (int)v; }
+        else if (a == "-u" || a == "--used-samples") ok = val(fused);
+        else if (a == "-t" || a == "--write-tree") ok = val(ftree);
+        else if (a == "-o" || a == "--write-mat") ok = val(fmat);
+        else if (a == "-d" || a == "--output-directory") ok = val(dir);
+        else if (a == "-T" || a == "--threads") ok = val(tmp);
+        else if (a == "--device") { ok = val(tmp); device = atoi(tmp.c_str()); }
+        else if (a == "--reference-ties") reference_ties = true;
+        else if (a == "-h" || a == "--help") { extract_usage(stderr); return 0; }
+        else {
+            for (const char *u : unsupported)
+                if (a == u) {
+                    fprintf(stderr, "ERROR: %s is not supported by matutils-amd extract (use the reference matUtils)\n", a.c_str());
+                    return 1;
+                }
+            fprintf(stderr, "ERROR: unknown option %s\n", a.c_str());
+            extract_usage(stderr);
+            return 1;
+        }
+        if (!ok) return 1;
+    }
+    if (in_mat.empty()) { fprintf(stderr, "ERROR: the option '--input-mat' is required but missing\n"); extract_usage(stderr); return 1; }
+    struct stat sb;
+    if (stat(dir.c_str(), &sb) != 0) {
+        fprintf(stderr, "Creating output directory.\n\n");
+        mkdir(dir.c_str(), 0777);
+    }
+    char *canon = realpath(dir.c_str(), nullptr);
+    if (!canon) { fprintf(stderr, "ERROR: cannot resolve the output directory %s\n", dir.c_str()); return 1; }
+    const std::string prefix = std::string(canon) + "/";
+    free(canon);
+    if (fused.empty() && ftree.empty() && fmat.empty()) { fprintf(stderr, "ERROR: No output files requested!\n"); return 1; }
+    std::string sample_id;
+    int nk = 0;
+    if (!nearest_k.empty()) {   // :272-284 (checked before the load here: the messages are the reference's)
+        const size_t split = nearest_k.find(":");
+        if (split == std::string::npos) {
+            fprintf(stderr, "ERROR: Invalid formatting of -k argument. Requires input in the form of 'sample_id:k' to get k nearest samples to sample_id\n");
+            return 1;
+        }
+        sample_id = nearest_k.substr(0, split);
+        nk = atoi(nearest_k.substr(split + 1).c_str());
+        if (nk <= 0) { fprintf(stderr, "ERROR: Invalid neighborhood size. Please choose a positive nonzero integer.\n"); return 1; }
+    }
+    fprintf(stderr, "Loading input MAT file %s.\n", in_mat.c_str());
+    if (in_mat.find(".pb") == std::string::npos) { fprintf(stderr, "ERROR: Input file ending not recognized. Must be .pb (.json is not supported by matutils-amd)\n"); return 1; }
+    uh::Tree T;
+    std::string err;
+    if (!uh::load_mat(in_mat, T, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+    T.uncondense_leaves();
+    fprintf(stderr, "Checking for and applying sample selection arguments\n");
+    const char *none = "ERROR: No samples fulfill selected criteria. Change arguments and try again\n";
+    std::vector<std::string> samples;
+    if (!fsamples.empty()) {
+        samples = read_sample_names(fsamples);
+        if (samples.empty()) { fprintf(stderr, "ERROR: Sample file is empty or unparseable!"); return 1; }
+    }
+    NearestSearch near(T, device, reference_ties);
+    if (!nearest_k.empty()) {   // :285-293
+        const std::vector<std::string> nks = near.run({must_get(T, sample_id)}, (size_t)nk)[0];
+        if (nks.empty()) {   // the reference's assert (nk_samples.size() > 0)
+            fprintf(stderr, "ERROR: no ancestor of %s has more than %d leaves: the nearest-k selection is empty\n", sample_id.c_str(), nk);
+            return 1;
+        }
+        if (samples.empty()) samples = nks;
+        else {   // sample_intersect: the -s samples that are among the nearest
+            const std::unordered_set<std::string> set(nks.begin(), nks.end());
+            std::vector<std::string> inter;
+            for (const std::string &s : samples) if (set.count(s)) inter.push_back(s);
+            samples = inter;
+        }
+    }
+    if (max_parsimony >= 0) { samples = get_parsimony_samples(T, samples, max_parsimony); if (samples.empty()) { fputs(none, stderr); return 1; } }
+    if (max_branch >= 0) { samples = get_short_steppers(T, samples, max_branch); if (samples.empty()) { fputs(none, stderr); return 1; } }
+    if (max_path >= 0) { samples = get_short_paths(T, samples, max_path); if (samples.empty()) { fputs(none, stderr); return 1; } }
+    if (select_nearest > 0) {   // :429-440; the union in depth-first order (the reference: an unordered_set's)
+        fprintf(stderr, "Selecting context samples...\n");
+        std::vector<uh::Node *> qs;
+        for (const std::string &s : samples) qs.push_back(must_get(T, s));
+        std::unordered_set<std::string> set;
+        for (const auto &names : near.run(qs, select_nearest)) set.insert(names.begin(), names.end());
+        samples.clear();
+        for (const uh::Node *n : T.dfs()) if (set.count(n->id)) samples.push_back(n->id);
+    }
+    // :590-606: nothing selected = the whole tree
+    uh::Tree sub;
+    uh::Tree *out = &T;
+    if (samples.empty()) {
+        fprintf(stderr, "No sample selection arguments passed; using full input tree for further output.\n");
+        samples = leaf_ids(T);
+    } else {
+        fprintf(stderr, "Extracting subtree of %zu samples.\n", samples.size());
+        if (!uh::get_subtree(T, samples, sub, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+        out = &sub;
+    }
+    if (!fused.empty()) {
+        fprintf(stderr, "Dumping selected samples to file...\n");
+        std::ofstream f(prefix + fused, std::ios::binary);
+        for (const std::string &s : samples) f << s << "\n";
+        if (!f) { fprintf(stderr, "ERROR: could not write %s\n", (prefix + fused).c_str()); return 1; }
+    }
+    if (!ftree.empty()) {
+        fprintf(stderr, "Generating Newick file of final tree\n");
+        FILE *f = must_open(prefix + ftree, "w");
+        fprintf(f, "%s\n", uh::newick(*out, out->root, true, true).c_str());
+        fclose(f);
+    }
+    if (!fmat.empty()) {
+        fprintf(stderr, "Saving output MAT file %s.\n", (prefix + fmat).c_str());
+        out->condense_leaves();
+        if (!uh::save_mat(*out, prefix + fmat, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
     if (argc < 2 || !strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) { usage(argc < 2 ? stderr : stdout); return argc < 2 ? 1 : 0; }
     if (!strcmp(argv[1], "uncertainty")) return uncertainty(argc - 2, argv + 2);
     if (!strcmp(argv[1], "annotate")) return annotate(argc - 2, argv + 2);
-    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate)\n", argv[1]);
+    if (!strcmp(argv[1], "extract")) return extract(argc - 2, argv + 2);
+    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate, extract)\n", argv[1]);
     return 1;
 }

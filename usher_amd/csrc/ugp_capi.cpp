@@ -27,6 +27,7 @@
 #include "ugp_ripples.hpp"
 #include "ugp_uncertainty.hpp"
 #include "ugp_annotate.hpp"
+#include "ugp_nearest.hpp"
 #include "ugp_update.hpp"
 #include "usher_amd.h"
 
@@ -291,6 +292,7 @@ struct ugp_mat {
     ugp::UncState *unc = nullptr;    // matUtils uncertainty tables (ugp_uncertainty_attach), or none
     ugp::RipState *rip = nullptr;    // RIPPLES tables (ugp_ripples_attach), or none
     ugp::AnnState *ann = nullptr;    // matUtils annotate tables (ugp_annotate_attach), or none
+    ugp::NearState *near = nullptr;  // matUtils extract nearest-k tables (ugp_nearest_attach), or none
     ugp::DfsTables *dfs = nullptr;   // the depth-first tables uncertainty and annotate share (their first attach), or none
     hipEvent_t kb_done = nullptr;    // behind the latest k_best8 launch of this handle ...
     hipStream_t kb_done_on = nullptr;   // ... on this stream
@@ -1303,6 +1305,7 @@ void ugp_mat_destroy(ugp_mat *m) {
     ugp::unc_free(m->unc);
     ugp::rip_free(m->rip);
     ugp::ann_free(m->ann);
+    ugp::nk_free(m->near);
     ugp::dfs_tables_free(m->dfs);
     delete m;
 }
@@ -1768,6 +1771,25 @@ int ugp_clade_descendants(ugp_mat *m, const uint64_t *clade_off, const uint32_t 
 int ugp_annotate_search(ugp_mat *m, const ugp_queries *q, uint32_t cap, int32_t *best, uint32_t *tie_dfs, uint32_t *tie_count) {
     if (!m) return fail(UGP_ERR_INVALID, "null argument");
     return ugp::ann_search(m->ann, q, cap, best, tie_dfs, tie_count);
+}
+
+// ---- matUtils extract: k nearest samples (ugp_nearest.hip) -----------------------------------------------------------
+
+int ugp_nearest_attach(ugp_mat *m, const ugp_tree_desc *tree) {
+    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
+    if (int rc = check_handle_tree(m, tree)) return rc;
+    return ugp::nk_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->near);
+}
+
+int ugp_nearest_k_chunked(ugp_mat *m, uint64_t n_queries, const uint32_t *nodes, const uint32_t *k, uint32_t out_stride, uint32_t *out_nodes,
+                          uint32_t *out_dist, ugp_nearest_info *info, uint32_t chunk_queries) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::nk_run(m->near, n_queries, nodes, k, out_stride, out_nodes, out_dist, info, chunk_queries);
+}
+
+int ugp_nearest_k(ugp_mat *m, uint64_t n_queries, const uint32_t *nodes, const uint32_t *k, uint32_t out_stride, uint32_t *out_nodes,
+                  uint32_t *out_dist, ugp_nearest_info *info) {
+    return ugp_nearest_k_chunked(m, n_queries, nodes, k, out_stride, out_nodes, out_dist, info, 0);
 }
 
 // ---- RIPPLES (ugp_ripples.hip) -----------------------------------------------------------------------------------------

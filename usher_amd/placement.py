@@ -336,6 +336,29 @@ class Placer:
         self._ck(self._L.ugp_annotate_search(self._h, C.byref(batch.desc), int(cap), _ptr(best), _ptr(ties), _ptr(cnt)))
         return best, [ties[i, :min(int(cnt[i]), cap)].copy() for i in range(n)], cnt
 
+    NEAREST_INFO = np.dtype([("count", np.uint32), ("anc", np.uint32), ("last_anc", np.uint32), ("cut_dist", np.uint32),
+                             ("n_at_cut", np.uint32)])
+
+    def nearest_k(self, nodes, k, out_stride: Optional[int] = None, chunk_queries: int = 0):
+        """matUtils extract's k nearest samples (ugp_nearest_k, select.cpp:206-276) for tree nodes given by BFS index; k is a
+        scalar or one value per query.  Returns (out_nodes, out_dist, info): row i holds min(info[i].count, out_stride) leaves
+        (BFS indices) and their distances to info[i].anc -- the leaves of last_anc in depth-first order, then the nearest others,
+        ties in depth-first order; info is a NEAREST_INFO array.  out_stride defaults to the largest k; chunk_queries (test hook)
+        sets the queries per workspace chunk.  The tables are made on the first call (ugp_nearest_attach)."""
+        if not getattr(self, "_near_ready", False):
+            self._ck(self._L.ugp_nearest_attach(self._h, C.byref(self._t.desc)))
+            self._near_ready = True
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
+        n = len(nodes)
+        ks = np.ascontiguousarray(np.broadcast_to(np.asarray(k, dtype=np.uint32), (n,)))
+        stride = int(out_stride) if out_stride is not None else (int(ks.max()) if n else 1)
+        out_nodes = np.full((n, max(stride, 1)), 0xFFFFFFFF, np.uint32)
+        out_dist = np.full((n, max(stride, 1)), 0xFFFFFFFF, np.uint32)
+        info = np.zeros(n, self.NEAREST_INFO)
+        self._ck(self._L.ugp_nearest_k_chunked(self._h, n, _ptr(nodes), _ptr(ks), stride, _ptr(out_nodes), _ptr(out_dist), _ptr(info),
+                                               int(chunk_queries)))
+        return out_nodes, out_dist, info
+
     RIPPLES_EVENT = np.dtype([("branch", np.uint64), ("i", np.uint32), ("j", np.uint32), ("donor", np.uint32), ("acceptor", np.uint32),
                               ("donor_count", np.uint32), ("acceptor_count", np.uint32), ("donor_score", np.int32),
                               ("acceptor_score", np.int32), ("donor_sibling", np.uint8), ("acceptor_sibling", np.uint8),
