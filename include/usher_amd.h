@@ -276,6 +276,41 @@ int ugp_nearest_k(ugp_mat *mat, uint64_t n_queries, const uint32_t *nodes /* BFS
                   ugp_nearest_info *info /* [n_queries] */);
 int ugp_nearest_k_chunked(ugp_mat *mat, uint64_t n_queries, const uint32_t *nodes, const uint32_t *k, uint32_t out_stride,
                           uint32_t *out_nodes, uint32_t *out_dist, ugp_nearest_info *info, uint32_t chunk_queries);
+/* matUtils extract -v (make_vcf / r_add_genotypes, matUtils/convert.cpp:53-292): the VCF site table and genotype codes of a selection
+ * of nodes.  ugp_genotypes_attach shares the depth-first tables of `tree` (the handle's tree; arrays are copied; mut_par is needed,
+ * and mut_nuc / mut_par of non-masked mutations must lie in 1 .. 15, UGP_ERR_UNSUPPORTED otherwise), once per handle.
+ * The handle's depth-first tables are shared with the uncertainty, annotate and nearest attaches and are built by the first of them: when
+ * they exist, `tree` must carry the mutation arrays they were built from (compared entry by entry; UGP_ERR_INVALID otherwise, nothing
+ * changed) -- a handle takes one set of mutation arrays for its whole life.
+ * ugp_genotype_select: the selection is a set of nodes (BFS indices; any node; one given twice counts once; NULL or n = 0: all
+ * leaves).  Columns are the selected nodes in depth-first order.  Masked mutations (mut_pos < 0) are skipped everywhere.  At a
+ * position p a column is COVERED when a node of its root path (itself included) has a mutation at p; its allele is mut_nuc of the
+ * deepest such node (the last stored one when that node has several at p).  REF is mut_par AS STORED of the first stored mutation
+ * at p of the first node, in depth-first order, that has one and a selected node in its subtree.  The alternates are the distinct
+ * alleles != REF of the covered columns in ascending numeric order of their 4-bit code (ambiguous codes are alleles like any
+ * other); ac[] counts their columns, AN is n_cols.  A position where no column is covered, or every covered column carries REF, is
+ * no site.  Sites come in ascending position.  A genotype code is 0 for an uncovered column or REF, else 1 + the index of the
+ * allele in alt[].  The selection, its counts and the site table stay on the device until the next select of the handle.
+ * ugp_genotype_columns: the columns' nodes.  ugp_genotype_sites: rows [lo, hi) of the site table.  ugp_genotype_rows: the codes of
+ * sites [lo, hi), row-major with stride n_cols; they are computed in windows of bounded device workspace, and
+ * ugp_genotype_rows_chunked (test hook) sets the cells per window (0: default; a window smaller than a row is a part of one row,
+ * in steps of 16 columns).  An out-of-range node, lo > hi, hi > n_sites, or sites / rows / columns before a select are
+ * UGP_ERR_INVALID before anything is written. */
+typedef struct ugp_gt_site {
+    int32_t pos;
+    uint8_t ref, n_alt;
+    uint8_t alt[14];     /* ascending 4-bit codes                                  */
+    uint32_t ac[14];     /* covered columns with alt[k]                            */
+    uint32_t covered;    /* covered columns (those with REF included)              */
+} ugp_gt_site;
+int ugp_genotypes_attach(ugp_mat *mat, const ugp_tree_desc *tree);
+int ugp_genotype_select(ugp_mat *mat, const uint32_t *nodes /* BFS; NULL: all leaves */, uint64_t n, uint32_t *n_cols, uint64_t *n_sites);
+int ugp_genotype_columns(ugp_mat *mat, uint32_t *nodes /* [n_cols] BFS, depth-first order */);
+int ugp_genotype_sites(ugp_mat *mat, uint64_t lo, uint64_t hi, ugp_gt_site *out /* [hi - lo] */);
+int ugp_genotype_rows(ugp_mat *mat, uint64_t lo, uint64_t hi, uint8_t *codes /* [(hi - lo) * n_cols] */);
+int ugp_genotype_rows_chunked(ugp_mat *mat, uint64_t lo, uint64_t hi, uint8_t *codes, uint64_t chunk_cells);
+/* Bench hook: milliseconds of device time of the row kernel alone over sites [lo, hi), without the copy to the host; mean of `reps` runs. */
+int ugp_genotype_rows_time(ugp_mat *mat, uint64_t lo, uint64_t hi, uint32_t reps, double *ms);
 /* RIPPLES (ripples/main.cpp): the options of :22-44 that the search reads.  branch_len >= 1 and parsimony_improvement >= 0
  * (UGP_ERR_INVALID otherwise: the reference's size_t arithmetic of :445-453 is not reproduced for negative values). */
 typedef struct ugp_ripples_opts {

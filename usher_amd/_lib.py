@@ -87,6 +87,13 @@ SYMBOLS = {
     "ugp_nearest_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc)]),
     "ugp_nearest_k": (C.c_int, [P, C.c_uint64, P, P, C.c_uint32, P, P, P]),
     "ugp_nearest_k_chunked": (C.c_int, [P, C.c_uint64, P, P, C.c_uint32, P, P, P, C.c_uint32]),
+    "ugp_genotypes_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc)]),
+    "ugp_genotype_select": (C.c_int, [P, P, C.c_uint64, P, P]),
+    "ugp_genotype_columns": (C.c_int, [P, P]),
+    "ugp_genotype_sites": (C.c_int, [P, C.c_uint64, C.c_uint64, P]),
+    "ugp_genotype_rows": (C.c_int, [P, C.c_uint64, C.c_uint64, P]),
+    "ugp_genotype_rows_chunked": (C.c_int, [P, C.c_uint64, C.c_uint64, P, C.c_uint64]),
+    "ugp_genotype_rows_time": (C.c_int, [P, C.c_uint64, C.c_uint64, C.c_uint32, P]),
     "ugp_ripples_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc), P]),
     "ugp_ripples": (C.c_int, [P, C.POINTER(ugp_ripples_opts), P, C.c_uint64, P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ugp_subtree_mask": (C.c_int, [P, C.c_uint32, C.c_uint32, C.c_uint32, P]),

@@ -2,7 +2,8 @@
 //
 //   matutils-amd uncertainty -i tree.pb -s samples.txt [-e epps.tsv] [-o placements.tsv] [-T n] [--device k]
 //   matutils-amd annotate -i tree.pb -o out.pb [-c | -M | -P | -C file ...] [-f -m -s -p -l -d -u -D -T] [--device k]
-//   matutils-amd extract -i tree.pb [-s samples.txt] [-k sample:k] [-Y y] [-a -b -P n] [-u -t -o file] [-d dir] [--reference-ties]
+//   matutils-amd extract -i tree.pb [-s samples.txt] [-k sample:k] [-Y y] [-a -b -P n] [-u -t -o -v file] [-n] [-d dir] [--reference-ties]
+//                        [--host-genotypes]
 //
 // uncertainty_main / findEPPs_wrapper (uncertainty.cpp:279-339, 541-560): load the MAT, uncondense its leaves, read the sample
 // names, and for every sample report its equally parsimonious placements and neighborhood size (-e) and the candidate parents
@@ -10,8 +11,11 @@
 // annotate_main (annotate.cpp:94-156): clade roots from exemplar samples, mutation sets, paths or node ids, written into the
 // .pb metadata.  Exemplar allele counts, the searches and the overlap counts run on the device (ugp_annotate.hip).
 // extract_main (extract.cpp:149-640): sample selection by name, nearest-k context (-k, -Y: get_nearby, one batched ugp_nearest_k
-// call) and the three linear filters, written as a sample list, a newick tree or a .pb of the induced subtree.
+// call) and the three linear filters, written as a sample list, a newick tree, a .pb of the induced subtree or its VCF (-v:
+// make_vcf, convert.cpp:14-320; site table and genotype codes from ugp_genotypes.hip, formatted here chunk by chunk).
+#include <hip/hip_runtime_api.h>
 #include <sys/stat.h>
+#include <zlib.h>
 
 #include <algorithm>
 #include <chrono>
@@ -19,7 +23,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <future>
 #include <map>
+#include <set>
 #include <sstream>
 #include <string>
 #include <unordered_map>
@@ -874,7 +880,7 @@ int annotate(int argc, char **argv) {   // annotate_main, :94-156
 void extract_usage(FILE *f) {
     fprintf(f,
             "Usage: matutils-amd extract -i tree.pb [-s samples.txt] [-k sample:k] [-Y y] [-a n] [-b n] [-P n] [-u used.txt] [-t tree.nh]\n"
-            "       [-o out.pb] [-d dir] [-T n] [--device k] [--reference-ties]\n"
+            "       [-o out.pb] [-v out.vcf] [-n] [-d dir] [-T n] [--device k] [--reference-ties] [--host-genotypes]\n"
             "  -i, --input-mat          input mutation-annotated tree [REQUIRED]\n"
             "  -s, --samples            select samples by explicitly naming them, one per line\n"
             "  -k, --nearest-k          select a sample and the nearest k samples to it, formatted as sample:k\n"
@@ -885,10 +891,13 @@ void extract_usage(FILE *f) {
             "  -u, --used-samples       write a text file of the selected sample ids\n"
             "  -t, --write-tree         write a newick tree of the selected samples\n"
             "  -o, --write-mat          write the selected tree as a new protobuf\n"
+            "  -v, --write-vcf          write a VCF of the selected samples (gzip when the name contains .gz)\n"
+            "  -n, --no-genotypes       leave the genotype columns out of the VCF\n"
             "  -d, --output-directory   directory of the output files [./]\n"
             "  -T, --threads            accepted for compatibility (the searches run on the device)\n"
             "      --device             HIP device ordinal [0]\n"
-            "      --reference-ties     order equal distances as the reference's std::sort does (host, slow)\n");
+            "      --reference-ties     order equal distances as the reference's std::sort does (host, slow)\n"
+            "      --host-genotypes     build the VCF with the reference's serial tree walk on the host (slow)\n");
 }
 
 std::vector<std::string> read_sample_names(const std::string &fname) {   // select.cpp:8-36
@@ -1042,17 +1051,238 @@ struct NearestSearch {
     }
 };
 
+// ---- extract -v (make_vcf, convert.cpp:14-320) ----------------------------------------------------------------------
+
+struct VcfFile {   // plain, or gzip when the name contains ".gz" (convert.cpp:305)
+    FILE *f = nullptr;
+    gzFile g = nullptr;
+    bool ok = true;
+    explicit VcfFile(const std::string &path) {
+        if (path.find(".gz") != std::string::npos) g = gzopen(path.c_str(), "wb");
+        else f = fopen(path.c_str(), "wb");
+        if (!f && !g) { fprintf(stderr, "ERROR: could not open %s\n", path.c_str()); exit(1); }
+    }
+    void put(const std::string &s) {
+        for (size_t o = 0; o < s.size() && ok;) {
+            const size_t n = std::min<size_t>(s.size() - o, 1u << 30);
+            ok = g ? gzwrite(g, s.data() + o, (unsigned)n) == (int)n : fwrite(s.data() + o, 1, n, f) == n;
+            o += n;
+        }
+    }
+    bool close() {
+        if (g) ok = gzclose(g) == Z_OK && ok;
+        if (f) ok = fclose(f) == 0 && ok;
+        g = nullptr; f = nullptr;
+        return ok;
+    }
+};
+
+// One row (VCF_Line_Writer, :195-251): `codes` = the genotype code per column, or null without genotypes.
+void vcf_row(std::string &out, const std::string &chrom, const ugp_gt_site &s, uint32_t n_cols, const uint8_t *codes) {
+    const std::string pos = std::to_string(s.pos);
+    const char ref = uh::nuc_char((int8_t)s.ref);
+    std::string id, alt, ac;
+    for (uint32_t k = 0; k < s.n_alt; k++) {
+        if (k) { id += ","; alt += ","; ac += ","; }
+        id += ref; id += pos; id += uh::nuc_char((int8_t)s.alt[k]);
+        alt += uh::nuc_char((int8_t)s.alt[k]);
+        ac += std::to_string(s.ac[k]);
+    }
+    out += chrom; out += '\t'; out += pos; out += '\t'; out += id; out += '\t'; out += ref; out += '\t'; out += alt;
+    out += "\t.\t.\tAC="; out += ac; out += ";AN="; out += std::to_string(n_cols);
+    if (codes) {
+        out += "\tGT";
+        for (uint32_t c = 0; c < n_cols; c++) {
+            const uint8_t v = codes[c];
+            out += '\t';
+            if (v >= 10) out += (char)('0' + v / 10);
+            out += (char)('0' + v % 10);
+        }
+    }
+    out += '\n';
+}
+
+// r_add_genotypes and write_vcf_rows (:53-102, 267-292) literally, on the host.
+struct HostGenotypes {
+    struct LeafGenotype { uint32_t leaf_ix; int8_t genotype; };
+    struct PosData { std::vector<LeafGenotype> leaf_genotypes; uint8_t ref = 0; };
+    std::unordered_map<uint32_t, PosData> info;
+    const std::set<std::string> &use;
+    explicit HostGenotypes(const std::set<std::string> &u) : use(u) {}
+    uint32_t add(const uh::Node *node, uint32_t leaf_ix, std::vector<const uh::Mutation *> &mut_stack) {
+        size_t pushed = 0;
+        for (const auto &mut : node->mutations) {
+            if (mut.masked()) continue;
+            mut_stack.push_back(&mut);
+            pushed++;
+        }
+        if (use.find(node->id) != use.end()) {
+            for (const uh::Mutation *mut : mut_stack) {
+                auto res = info.insert(std::make_pair((uint32_t)mut->position, PosData()));
+                PosData &pi = res.first->second;
+                if (res.second) pi.ref = (uint8_t)mut->par_nuc;
+                if (pi.leaf_genotypes.empty() || pi.leaf_genotypes.back().leaf_ix < leaf_ix) pi.leaf_genotypes.push_back({leaf_ix, mut->mut_nuc});
+                else pi.leaf_genotypes.back().genotype = mut->mut_nuc;
+            }
+            leaf_ix++;
+        }
+        for (const uh::Node *child : node->children) leaf_ix = add(child, leaf_ix, mut_stack);
+        mut_stack.resize(mut_stack.size() - pushed);
+        return leaf_ix;
+    }
+    size_t write(VcfFile &vcf, const std::string &chrom, uint32_t leaf_count, bool print_genotypes) {   // returns the rows written
+        size_t written = 0;
+        std::vector<uint32_t> order;
+        for (const auto &kv : info) order.push_back(kv.first);
+        std::sort(order.begin(), order.end());
+        std::string line;
+        std::vector<uint8_t> codes(leaf_count);
+        for (uint32_t pos : order) {
+            const PosData &pi = info[pos];
+            std::map<int8_t, uint32_t> counts;   // count_alleles, then make_alts' std::map: ascending allele
+            for (const LeafGenotype &g : pi.leaf_genotypes) counts[g.genotype]++;
+            counts.erase((int8_t)pi.ref);
+            if (counts.empty()) { fprintf(stderr, "WARNING: no-alternative site encountered in vcf output; skipping\n"); continue; }
+            ugp_gt_site s{};
+            s.pos = (int32_t)pos; s.ref = pi.ref; s.covered = (uint32_t)pi.leaf_genotypes.size();
+            int al_codes[256] = {0};
+            for (const auto &kv : counts) {
+                if (s.n_alt >= 14) { fprintf(stderr, "ERROR: more than 14 alternate alleles at position %u\n", pos); exit(1); }
+                s.alt[s.n_alt] = (uint8_t)kv.first; s.ac[s.n_alt] = kv.second;
+                al_codes[(uint8_t)kv.first] = ++s.n_alt;
+            }
+            if (print_genotypes) {
+                std::fill(codes.begin(), codes.end(), 0);
+                for (const LeafGenotype &g : pi.leaf_genotypes) codes[g.leaf_ix] = (uint8_t)al_codes[(uint8_t)g.genotype];
+            }
+            line.clear();
+            vcf_row(line, chrom, s, leaf_count, print_genotypes ? codes.data() : nullptr);
+            vcf.put(line);
+            written++;
+        }
+        return written;
+    }
+};
+
+int make_vcf(uh::Tree &T, const std::string &path, bool no_genotypes, const std::vector<std::string> &samples_vec, int device, bool on_host) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::set<std::string> use(samples_vec.begin(), samples_vec.end());
+    if (use.empty()) for (const std::string &s : leaf_ids(T)) use.insert(s);
+    const std::vector<uh::Node *> dfs = T.dfs();
+    // one chromosome: the reference writes them in the iteration order of an unordered_map
+    std::string chrom;
+    bool any = false;
+    for (const uh::Node *n : dfs)
+        for (const auto &m : n->mutations) {
+            if (m.masked()) continue;
+            const std::string &c = T.chroms[m.chrom];
+            if (any && c != chrom) {
+                fprintf(stderr, "ERROR: the tree's mutations name more than one chromosome (%s, %s): matutils-amd extract -v writes one\n", chrom.c_str(), c.c_str());
+                return 1;
+            }
+            chrom = c; any = true;
+        }
+    VcfFile vcf(path);
+    std::string head = "##fileformat=VCFv4.2\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO";
+    if (!no_genotypes) {
+        head += "\tFORMAT";
+        for (const uh::Node *n : dfs) if (use.count(n->id)) { head += '\t'; head += n->id; }
+    }
+    head += '\n';
+    vcf.put(head);
+    size_t n_sites = 0;
+    uint32_t n_cols = 0;
+    if (on_host) {
+        HostGenotypes hg(use);
+        std::vector<const uh::Mutation *> mut_stack;
+        n_cols = (uint32_t)use.size();
+        hg.add(T.root, 0, mut_stack);
+        n_sites = hg.write(vcf, chrom, n_cols, !no_genotypes);
+    } else {
+        // the tree as arrays: the handle takes the bare topology, the genotype tables the mutations as they are stored
+        const std::vector<uh::Node *> bfs = T.bfs();
+        const uint64_t N = bfs.size();
+        for (uint64_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
+        std::vector<uint32_t> parent(N), sel;
+        std::vector<uint64_t> mut_off(N + 1, 0), no_off(N + 1, 0);
+        std::vector<int32_t> pos;
+        std::vector<uint8_t> ref, par, nuc;
+        for (uint64_t j = 0; j < N; j++) {
+            parent[j] = bfs[j]->parent ? bfs[j]->parent->flat_index : UINT32_MAX;
+            for (const auto &m : bfs[j]->mutations) {
+                pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
+            }
+            mut_off[j + 1] = pos.size();
+            if (use.count(bfs[j]->id)) sel.push_back((uint32_t)j);
+        }
+        if (pos.empty()) { pos.push_back(0); ref.push_back(0); par.push_back(0); nuc.push_back(0); }   // (never read: no null arrays)
+        const ugp_tree_desc bare{N, parent.data(), no_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+        const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+        ugp_mat *h = nullptr;
+        if (ugp_mat_create(&bare, device, &h) != UGP_OK) lib_fail("ugp_mat_create");
+        if (ugp_genotypes_attach(h, &desc) != UGP_OK) lib_fail("ugp_genotypes_attach");
+        uint64_t ns = 0;
+        if (ugp_genotype_select(h, sel.data(), sel.size(), &n_cols, &ns) != UGP_OK) lib_fail("ugp_genotype_select");
+        n_sites = ns;
+        std::vector<ugp_gt_site> sites(ns);
+        if (ugp_genotype_sites(h, 0, ns, sites.data()) != UGP_OK) lib_fail("ugp_genotype_sites");
+        std::string text;
+        if (no_genotypes) {
+            for (const ugp_gt_site &s : sites) { text.clear(); vcf_row(text, chrom, s, n_cols, nullptr); vcf.put(text); }
+        } else if (ns) {
+            // rows in chunks of sites: the device fills one pinned buffer while the other is formatted
+            const uint64_t per = std::max<uint64_t>(1, (uint64_t(32) << 20) / n_cols);
+            uint8_t *buf[2] = {nullptr, nullptr};
+            for (auto &b : buf)
+                if (hipHostMalloc((void **)&b, std::min<uint64_t>(per, ns) * n_cols, hipHostMallocDefault) != hipSuccess) {
+                    fprintf(stderr, "ERROR: hipHostMalloc failed\n");
+                    for (auto &f : buf) if (f) (void)hipHostFree(f);
+                    ugp_mat_destroy(h);
+                    return 1;
+                }
+            // (the library's error text is per thread: the fetching thread brings it along)
+            auto fetch = [&](uint64_t lo, int k) -> std::string {
+                return ugp_genotype_rows(h, lo, std::min<uint64_t>(ns, lo + per), buf[k]) == UGP_OK ? std::string() : std::string("ugp_genotype_rows: ") + ugp_last_error();
+            };
+            std::future<std::string> next = std::async(std::launch::async, fetch, uint64_t(0), 0);
+            int k = 0;
+            std::string failed;
+            for (uint64_t lo = 0; lo < ns; lo += per, k ^= 1) {
+                failed = next.get();
+                if (!failed.empty()) break;
+                if (lo + per < ns) next = std::async(std::launch::async, fetch, lo + per, k ^ 1);
+                const uint64_t hi = std::min<uint64_t>(ns, lo + per);
+                text.clear();
+                for (uint64_t s = lo; s < hi; s++) vcf_row(text, chrom, sites[s], n_cols, buf[k] + (s - lo) * n_cols);
+                vcf.put(text);
+            }
+            if (!failed.empty()) {
+                fprintf(stderr, "ERROR: %s\n", failed.c_str());
+                for (auto &b : buf) (void)hipHostFree(b);
+                ugp_mat_destroy(h);
+                return 1;
+            }
+            for (auto &b : buf) (void)hipHostFree(b);
+        }
+        ugp_mat_destroy(h);
+    }
+    if (!vcf.close()) { fprintf(stderr, "ERROR: could not write %s\n", path.c_str()); return 1; }
+    fprintf(stderr, "VCF of %zu sites x %u samples (%s): %.1f msec\n", n_sites, n_cols, on_host ? "host" : "device",
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    return 0;
+}
+
 int extract(int argc, char **argv) {   // extract_main, extract.cpp:149-640, 867-888 for the options of extract_usage
-    std::string in_mat, fsamples, nearest_k, fused, ftree, fmat, dir = "./";
+    std::string in_mat, fsamples, nearest_k, fused, ftree, fmat, fvcf, dir = "./";
     int max_parsimony = -1, max_branch = -1, max_path = -1, device = 0;
     size_t select_nearest = 0;
-    bool reference_ties = false;
+    bool reference_ties = false, no_genotypes = false, host_genotypes = false;
     static const char *const unsupported[] = {
-        "-K", "--nearest-k-batch", "-v", "--write-vcf", "-j", "--write-json", "-c", "--clade", "-m", "--mutation", "-H", "--match",
+        "-K", "--nearest-k-batch", "-j", "--write-json", "-c", "--clade", "-m", "--mutation", "-H", "--match",
         "-V", "--closest-relatives", "-q", "--break-ties", "--within-distance", "--distance-threshold", "-z", "--set-size", "-W", "--add-random",
         "-Z", "--limit-to-lca", "-y", "--reroot", "--write-reroot-reference", "-R", "--resolve-polytomies", "-e", "--max-epps",
         "--max-mutation-density", "-I", "--get-internal-descendents", "-U", "--from-mrca", "-r", "--get-representative", "-p", "--prune",
-        "-S", "--sample-paths", "-C", "--clade-paths", "-A", "--all-paths", "--write-diff", "-n", "--no-genotypes", "-O", "--collapse-tree",
+        "-S", "--sample-paths", "-C", "--clade-paths", "-A", "--all-paths", "--write-diff", "-O", "--collapse-tree",
         "-l", "--write-taxodium", "-G", "--x-scale", "-B", "--title", "-D", "--description", "-J", "--include-nt", "-F", "--extra-fields",
         "-E", "--retain-branch-length", "-N", "--minimum-subtrees-size", "-X", "--usher-single-subtree-size", "-x", "--usher-minimum-subtrees-size",
         "--usher-clades-txt", "--usher-anchor-samples", "-Q", "--dump-metadata", "-L", "--whitelist", "--load-all-metadata", "-M", "--metadata",
@@ -1089,6 +1319,9 @@ int extract(int argc, char **argv) {   // extract_main, extract.cpp:149-640, 867
         else if (a == "-T" || a == "--threads") ok = val(tmp);
         else if (a == "--device") { ok = val(tmp); device = atoi(tmp.c_str()); }
         else if (a == "--reference-ties") reference_ties = true;
+        else if (a == "-v" || a == "--write-vcf") ok = val(fvcf);
+        else if (a == "-n" || a == "--no-genotypes") no_genotypes = true;
+        else if (a == "--host-genotypes") host_genotypes = true;
         else if (a == "-h" || a == "--help") { extract_usage(stderr); return 0; }
         else {
             for (const char *u : unsupported)
@@ -1112,7 +1345,7 @@ int extract(int argc, char **argv) {   // extract_main, extract.cpp:149-640, 867
     if (!canon) { fprintf(stderr, "ERROR: cannot resolve the output directory %s\n", dir.c_str()); return 1; }
     const std::string prefix = std::string(canon) + "/";
     free(canon);
-    if (fused.empty() && ftree.empty() && fmat.empty()) { fprintf(stderr, "ERROR: No output files requested!\n"); return 1; }
+    if (fused.empty() && ftree.empty() && fmat.empty() && fvcf.empty()) { fprintf(stderr, "ERROR: No output files requested!\n"); return 1; }
     std::string sample_id;
     int nk = 0;
     if (!nearest_k.empty()) {   // :272-284 (checked before the load here: the messages are the reference's)
@@ -1181,6 +1414,10 @@ int extract(int argc, char **argv) {   // extract_main, extract.cpp:149-640, 867
         std::ofstream f(prefix + fused, std::ios::binary);
         for (const std::string &s : samples) f << s << "\n";
         if (!f) { fprintf(stderr, "ERROR: could not write %s\n", (prefix + fused).c_str()); return 1; }
+    }
+    if (!fvcf.empty()) {   // :859-862, before the newick file as there
+        fprintf(stderr, "Generating VCF of final tree\n");
+        if (int rc = make_vcf(*out, prefix + fvcf, no_genotypes, samples, device, host_genotypes)) return rc;
     }
     if (!ftree.empty()) {
         fprintf(stderr, "Generating Newick file of final tree\n");

@@ -28,6 +28,7 @@
 #include "ugp_uncertainty.hpp"
 #include "ugp_annotate.hpp"
 #include "ugp_nearest.hpp"
+#include "ugp_genotypes.hpp"
 #include "ugp_update.hpp"
 #include "usher_amd.h"
 
@@ -293,6 +294,7 @@ struct ugp_mat {
     ugp::RipState *rip = nullptr;    // RIPPLES tables (ugp_ripples_attach), or none
     ugp::AnnState *ann = nullptr;    // matUtils annotate tables (ugp_annotate_attach), or none
     ugp::NearState *near = nullptr;  // matUtils extract nearest-k tables (ugp_nearest_attach), or none
+    ugp::GtState *gt = nullptr;      // matUtils extract -v tables (ugp_genotypes_attach), or none
     ugp::DfsTables *dfs = nullptr;   // the depth-first tables uncertainty and annotate share (their first attach), or none
     hipEvent_t kb_done = nullptr;    // behind the latest k_best8 launch of this handle ...
     hipStream_t kb_done_on = nullptr;   // ... on this stream
@@ -1306,6 +1308,7 @@ void ugp_mat_destroy(ugp_mat *m) {
     ugp::rip_free(m->rip);
     ugp::ann_free(m->ann);
     ugp::nk_free(m->near);
+    ugp::gt_free(m->gt);
     ugp::dfs_tables_free(m->dfs);
     delete m;
 }
@@ -1790,6 +1793,41 @@ int ugp_nearest_k_chunked(ugp_mat *m, uint64_t n_queries, const uint32_t *nodes,
 int ugp_nearest_k(ugp_mat *m, uint64_t n_queries, const uint32_t *nodes, const uint32_t *k, uint32_t out_stride, uint32_t *out_nodes,
                   uint32_t *out_dist, ugp_nearest_info *info) {
     return ugp_nearest_k_chunked(m, n_queries, nodes, k, out_stride, out_nodes, out_dist, info, 0);
+}
+
+// ---- matUtils extract -v: genotypes of a selection (ugp_genotypes.hip) -------------------------------------------------
+
+int ugp_genotypes_attach(ugp_mat *m, const ugp_tree_desc *tree) {
+    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
+    if (int rc = check_handle_tree(m, tree)) return rc;
+    return ugp::gt_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->gt);
+}
+
+int ugp_genotype_select(ugp_mat *m, const uint32_t *nodes, uint64_t n, uint32_t *n_cols, uint64_t *n_sites) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::gt_select(m->gt, nodes, n, n_cols, n_sites);
+}
+
+int ugp_genotype_columns(ugp_mat *m, uint32_t *nodes) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::gt_columns(m->gt, nodes);
+}
+
+int ugp_genotype_sites(ugp_mat *m, uint64_t lo, uint64_t hi, ugp_gt_site *out) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::gt_sites(m->gt, lo, hi, out);
+}
+
+int ugp_genotype_rows_chunked(ugp_mat *m, uint64_t lo, uint64_t hi, uint8_t *codes, uint64_t chunk_cells) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::gt_rows(m->gt, lo, hi, codes, chunk_cells);
+}
+
+int ugp_genotype_rows(ugp_mat *m, uint64_t lo, uint64_t hi, uint8_t *codes) { return ugp_genotype_rows_chunked(m, lo, hi, codes, 0); }
+
+int ugp_genotype_rows_time(ugp_mat *m, uint64_t lo, uint64_t hi, uint32_t reps, double *ms) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::gt_rows_time(m->gt, lo, hi, reps, ms);
 }
 
 // ---- RIPPLES (ugp_ripples.hip) -----------------------------------------------------------------------------------------

@@ -359,6 +359,66 @@ class Placer:
                                                int(chunk_queries)))
         return out_nodes, out_dist, info
 
+    GT_SITE = np.dtype([("pos", np.int32), ("ref", np.uint8), ("n_alt", np.uint8), ("alt", np.uint8, (14,)), ("ac", np.uint32, (14,)),
+                        ("covered", np.uint32)])
+
+    def genotypes_attach(self, arrays: Optional[Dict] = None):
+        """ugp_genotypes_attach with the placer's own tree, or with other mutation arrays on the same topology (trees the
+        placement tables refuse: ambiguous alleles, a node with two mutations at one position).  The depth-first tables are
+        shared with uncertainty, annotate and nearest_k and built by the first of these calls on the handle: once they exist,
+        arrays other than theirs are refused (UgpError -1) and the handle stays as it was."""
+        t = self._t if arrays is None else _TreeArrays(arrays)
+        self._ck(self._L.ugp_genotypes_attach(self._h, C.byref(t.desc)))
+        self._gt_ready = True
+        self._gt_shape = None
+
+    def genotype_select(self, nodes=None):
+        """matUtils extract -v for a selection of tree nodes (BFS indices; None or empty: all leaves): ranks the selection, counts
+        the alleles and builds the VCF site table on the device (ugp_genotype_select, convert.cpp:53-292).  Returns
+        (n_cols, n_sites); the selection stays on the handle until the next call.  The tables are made on the first call
+        (ugp_genotypes_attach)."""
+        if not getattr(self, "_gt_ready", False):
+            self.genotypes_attach()
+        sel = np.ascontiguousarray(nodes if nodes is not None else [], dtype=np.uint32)
+        ncols, nsites = C.c_uint32(0), C.c_uint64(0)
+        self._ck(self._L.ugp_genotype_select(self._h, _ptr(sel) if len(sel) else None, len(sel), C.byref(ncols), C.byref(nsites)))
+        self._gt_shape = (int(ncols.value), int(nsites.value))
+        return self._gt_shape
+
+    def _gt_range(self, lo, hi):
+        if getattr(self, "_gt_shape", None) is None:
+            raise UgpError(-1, "no selection: call genotype_select first")
+        return int(lo), self._gt_shape[1] if hi is None else int(hi)
+
+    def genotype_columns(self):
+        """The selected nodes (BFS indices) in depth-first order: the columns of genotype_rows."""
+        self._gt_range(0, 0)
+        out = np.zeros(self._gt_shape[0], np.uint32)
+        self._ck(self._L.ugp_genotype_columns(self._h, _ptr(out)))
+        return out
+
+    def genotype_sites(self, lo=0, hi=None):
+        """Rows [lo, hi) of the site table as a GT_SITE array, ascending by position."""
+        lo, hi = self._gt_range(lo, hi)
+        out = np.zeros(max(hi - lo, 0), self.GT_SITE)
+        self._ck(self._L.ugp_genotype_sites(self._h, lo, hi, _ptr(out)))
+        return out
+
+    def genotype_rows(self, lo=0, hi=None, chunk_cells: int = 0):
+        """The genotype codes of sites [lo, hi): a uint8 array [hi - lo, n_cols].  chunk_cells (test hook) sets the cells per
+        workspace window."""
+        lo, hi = self._gt_range(lo, hi)
+        out = np.zeros((max(hi - lo, 0), self._gt_shape[0]), np.uint8)
+        self._ck(self._L.ugp_genotype_rows_chunked(self._h, lo, hi, _ptr(out), int(chunk_cells)))
+        return out
+
+    def genotype_rows_time(self, lo=0, hi=None, reps: int = 5) -> float:
+        """Bench hook: milliseconds of device time of the row kernel alone over sites [lo, hi), no copy to the host."""
+        lo, hi = self._gt_range(lo, hi)
+        ms = C.c_double(0)
+        self._ck(self._L.ugp_genotype_rows_time(self._h, lo, hi, int(reps), C.byref(ms)))
+        return float(ms.value)
+
     RIPPLES_EVENT = np.dtype([("branch", np.uint64), ("i", np.uint32), ("j", np.uint32), ("donor", np.uint32), ("acceptor", np.uint32),
                               ("donor_count", np.uint32), ("acceptor_count", np.uint32), ("donor_score", np.int32),
                               ("acceptor_score", np.int32), ("donor_sibling", np.uint8), ("acceptor_sibling", np.uint8),
