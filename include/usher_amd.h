@@ -431,8 +431,9 @@ int ugp_touched_score(ugp_mat *mat, uint32_t first_id, uint64_t first_sample);
 /* One sample again from every live record (its list held retired records only). */
 int ugp_touched_rescore(ugp_mat *mat, uint64_t sample);
 /* Results of samples [first_sample, first_sample + n): best[i] = minimum cost over the eligible live records (INT32_MAX: none),
- * count[i] = how many attain it (true count), ids / has_unique [i * cap ..] = the first min(count, cap) of them.  A record retired
- * after it entered a list is still listed: the caller knows which ids it retired. */
+ * count[i] = how many attain it (true count), ids / has_unique [i * cap ..] = min(count, cap, 64) of them -- the device keeps 64
+ * per sample, in no particular order; with cap < 64 the first `cap` of those it kept; the rest of a row is left as it was.  A
+ * record retired after it entered a list is still listed: the caller knows which ids it retired. */
 int ugp_touched_fetch(ugp_mat *mat, uint64_t first_sample, uint64_t n, uint32_t cap, int32_t *best, uint32_t *count, uint32_t *ids,
                       uint8_t *has_unique);
 

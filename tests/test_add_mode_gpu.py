@@ -9,49 +9,11 @@ import pytest
 
 from oracle import capi, refio
 from tests import synth, usher_model
+from tests.touched_cases import record_of, tree_from_arrays
 from usher_amd import Placer, QueryBatch
 
 pytestmark = pytest.mark.gpu
 INT_MAX = 2 ** 31 - 1
-
-
-def tree_from_arrays(arrays):
-    """refio.Tree with the nodes of `arrays` (names n<j>), children in index order."""
-    T = refio.Tree()
-    nodes = []
-    for j in range(int(arrays["n"])):
-        p = int(arrays["parent"][j])
-        nd = T.create_node("n%d" % j, nodes[p] if p >= 0 else None)
-        for i in range(int(arrays["mut_off"][j]), int(arrays["mut_off"][j + 1])):
-            m = refio.Mutation(int(arrays["mut_pos"][i]), int(arrays["mut_ref"][i]), int(arrays["mut_par"][i]), int(arrays["mut_nuc"][i]))
-            nd.mutations.append(m)           # (already in the stored order)
-        nodes.append(nd)
-    return T, nodes
-
-
-def record_of(node, flat_index):
-    """What the driver reports for a touched node: the parent's state wherever it is not the reference base, the own mutations in
-    front of the first masked one with their true parent state."""
-    state, ref = {}, {}
-    a = node.parent
-    chain = []
-    while a is not None:
-        chain.append(a)
-        a = a.parent
-    for a in reversed(chain):                       # root first: later mutations overwrite
-        for m in a.mutations:
-            if m.is_masked():
-                continue
-            state[m.position] = m.mut_nuc
-            ref[m.position] = m.ref_nuc
-    path = [(p, s, ref[p]) for p, s in state.items() if s != ref[p]]
-    own, masked = [], False
-    for m in node.mutations:
-        if m.is_masked():
-            masked = True
-            break
-        own.append((m.position, m.mut_nuc, state.get(m.position, m.ref_nuc), m.ref_nuc))
-    return {"flat_j": flat_index, "leaf": node.is_leaf(), "masked": masked, "path": path, "own": own}
 
 
 def merged_answer(flat_best, flat_ties, t_best, t_ties):
