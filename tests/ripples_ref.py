@@ -163,10 +163,12 @@ def _lowbit(a):
     return 0
 
 
-def closed_branch(arrays, nid, bidx, l=3, r=1000, R=10 ** 7, p=3, n_desc=10, sz=None, rank=None, anc=None):
+def closed_branch(arrays, nid, bidx, l=3, r=1000, R=10 ** 7, p=3, n_desc=10, sz=None, rank=None, anc=None, detail=None):
     """Per candidate k: the bucket counts of U_k (2M + 1 buckets: below / at / between the sample positions) from the
     parent's genotype, corrected at k's own mutations by a literal loop 1; pass-1 score and flags from the same terms;
-    then top-3 donors / acceptors per pair by (count << 32 | name rank) and the top-2 selection."""
+    then top-3 donors / acceptors per pair by (count << 32 | name rank) and the top-2 selection.
+    detail: a dict that receives what the search held -- rows, pairs, B, cand, under (the candidates below nid), best (the
+    smallest eligible set difference) and, per candidate, S (bucket prefix sums), score, elig, has_unique, nm, common."""
     par = np.asarray(arrays["parent"])
     n = len(par)
     sz = subtree_sizes(arrays) if sz is None else sz
@@ -180,6 +182,8 @@ def closed_branch(arrays, nid, bidx, l=3, r=1000, R=10 ** 7, p=3, n_desc=10, sz=
     B = orig - p
     pairs = valid_pairs(pos, l, r, R)
     cand = [k for k in range(n) if sz[k] >= n_desc]
+    if detail is not None:
+        detail.update(rows=rows, pairs=pairs, B=B, cand=cand)
     if not pairs or B < 0 or not cand:
         return []
     srow = {x[0]: (x[2], x[1]) for x in rows if x[0] >= 0}
@@ -199,7 +203,7 @@ def closed_branch(arrays, nid, bidx, l=3, r=1000, R=10 ** 7, p=3, n_desc=10, sz=
     for (q, rf, s) in rows:
         if (s & rf) == 0:
             base0[bucket(q)] += 1
-    S, score, elig, hu_of = {}, {}, {}, {}
+    S, score, elig, hu_of, nm_of, common_of = {}, {}, {}, {}, {}, {}
     off = arrays["mut_off"]
     for k in cand:
         cnt = list(base0)
@@ -257,6 +261,7 @@ def closed_branch(arrays, nid, bidx, l=3, r=1000, R=10 ** 7, p=3, n_desc=10, sz=
             (not hu and not leaf[k] and nm == common)
         score[k] = E + (0 if el else 1)
         elig[k] = el; hu_of[k] = hu and k != 0
+        nm_of[k] = nm; common_of[k] = common
         pre = [0]
         for c in cnt:
             pre.append(pre[-1] + c)
@@ -265,6 +270,10 @@ def closed_branch(arrays, nid, bidx, l=3, r=1000, R=10 ** 7, p=3, n_desc=10, sz=
     sib = lambda k: bool(leaf[k] or (elig[k] and score[k] == best and hu_of[k]))
     events = []
     keep = [k for k in cand if not is_strict_desc(par, nid, k)]
+    if detail is not None:
+        kept_set = set(keep)
+        detail.update(S=S, score=score, elig=elig, has_unique=hu_of, nm=nm_of, common=common_of, best=best,
+                      under=[k for k in cand if k not in kept_set])
     for (i, j) in pairs:
         don, acc = [], []
         for k in keep:

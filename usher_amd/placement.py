@@ -424,6 +424,17 @@ class Placer:
                               ("acceptor_score", np.int32), ("donor_sibling", np.uint8), ("acceptor_sibling", np.uint8),
                               ("pad", np.uint8, 6)])
 
+    def ripples_attach(self, name_rank, arrays: Optional[Dict] = None):
+        """Advanced / test hook; ripples() attaches by itself.  ugp_ripples_attach with the placer's own tree, or with other
+        mutation arrays on the same topology (trees the placement tables refuse: ambiguous alleles).  Arrays given here stay
+        the searched tree for the life of the handle: ripples() keeps them when it attaches again for other ranks, and
+        the placement calls go on using the handle's own tree."""
+        rank = np.ascontiguousarray(name_rank, dtype=np.uint32)
+        t = getattr(self, "_rip_t", self._t) if arrays is None else _TreeArrays(arrays)
+        self._ck(self._L.ugp_ripples_attach(self._h, C.byref(t.desc), _ptr(rank)))
+        self._rip_t = t
+        self._rip_rank = rank.copy()
+
     def ripples(self, branches, name_rank, branch_len: int = 3, min_range: int = 1000, max_range: int = 10 ** 7,
                 parsimony_improvement: int = 3, num_descendants: int = 10) -> np.ndarray:
         """RIPPLES' search (ugp_ripples, ripples/main.cpp:300-680 up to the interval refinement) for the branches given by BFS
@@ -431,8 +442,7 @@ class Placer:
         node k's name in byte order; the tables are made on the first call (ugp_ripples_attach) and kept for the same ranks."""
         rank = np.ascontiguousarray(name_rank, dtype=np.uint32)
         if getattr(self, "_rip_rank", None) is None or not np.array_equal(self._rip_rank, rank):
-            self._ck(self._L.ugp_ripples_attach(self._h, C.byref(self._t.desc), _ptr(rank)))
-            self._rip_rank = rank.copy()
+            self.ripples_attach(rank)
         br = np.ascontiguousarray(branches, dtype=np.uint32)
         opts = _lib.ugp_ripples_opts(int(branch_len), int(min_range), int(max_range), int(parsimony_improvement), int(num_descendants))
         n_out = C.c_uint64(0)
