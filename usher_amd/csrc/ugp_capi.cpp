@@ -21,6 +21,7 @@
 #include "ugp_bound3.hpp"
 #include "ugp_dense.hpp"
 #include "ugp_tuner.hpp"
+#include "ugp_plan.hpp"
 #include "ugp_flatten.hpp"
 #include "ugp_kernels.hpp"
 #include "ugp_knobs.hpp"
@@ -168,8 +169,7 @@ struct EventSet {
 
 using ugp::B3Tuner;   // (ugp_tuner.hpp: the third pruning bound, with or without, by measurement)
 
-constexpr uint32_t kMaxTilesPerLaunch = 4096;   // 262,144 samples per sub-batch
-constexpr int kMaxSets = 4;                     // workspace sets per handle = calls of ugp_place_device_overlapped that can be on the device at a time
+using ugp::kMaxSets;   // (ugp_plan.hpp: workspace sets per handle)
 
 }  // namespace
 
@@ -321,16 +321,6 @@ struct ugp_qset {
 namespace ugp { void fitch_drop_streams(int device); }   // ugp_fitch.hip
 namespace {
 
-uint32_t pick_groups(const ugp_mat *m, uint32_t n_tiles, uint32_t target_waves = 4096) {
-    if (m->knobs.target_waves) target_waves = m->knobs.target_waves;
-    uint32_t g = (target_waves + n_tiles - 1) / n_tiles;
-    if (m->knobs.groups) g = m->knobs.groups;
-    g = std::min<uint32_t>(g, m->flat.n_chunks);
-    g = std::max<uint32_t>(g, 1);
-    if (g >= 8) g &= ~7u;   // XCD-aware block mapping wants a multiple of 8
-    return g;
-}
-
 // Host part of the query checks: the CSR offsets.  The per-row checks run on the device (k_rows_prepare).
 int validate_offsets(const ugp_queries *q, uint64_t &n_ent, uint64_t &max_rows) {
     if (!q || (q->n_queries && !q->ent_off)) return fail(UGP_ERR_INVALID, "null query arrays");
@@ -368,542 +358,611 @@ struct ExDev {
     bool packed = false;   // the caller has arranged for the packed path (mask turned into exclusions; no scores)
 };
 
-// mode 0: results to d_out (device ugp_result[n_queries]);
-// mode 1: per-node scores to d_scores (device int32 [n_queries][n_nodes]);
-// mode 2: tied nodes (needs d_best_in) -- see ugp_kernels.hip.
-int run_place(ugp_mat *m, ugp_qset *qs, int mode, ugp_result *d_out, int32_t *d_scores, const int32_t *d_best_in,
-              uint32_t *d_tie_count, uint32_t *d_tie_j, uint8_t *d_tie_hu, uint32_t tie_cap, hipStream_t s, bool coarse_only = false,
-              const ExDev *ex = nullptr, int wi = 0) {
+// What a placement call is asked for: a call site sets the fields it uses.
+// mode 0: results to `out` (device ugp_result[n_queries]);
+// mode 1: per-node scores to `scores` (device int32 [n_queries][n_nodes]);
+// mode 2: tied nodes (needs best_in) -- see ugp_kernels.hip.
+struct PlaceReq {
+    int mode = 0;
+    ugp_result *out = nullptr;
+    int32_t *scores = nullptr;
+    const int32_t *best_in = nullptr;
+    uint32_t *tie_count = nullptr, *tie_j = nullptr;   // tie lists: [n_queries] counts, [n_queries][tie_cap] nodes and flags
+    uint8_t *tie_hu = nullptr;
+    uint32_t tie_cap = 0;
+    hipStream_t stream = nullptr;
+    bool coarse_only = false;
+    const ExDev *ex = nullptr;
+    int wi = 0;                  // workspace set
+};
+
+struct Finish {   // whatever way a call ends: mark the set's last use
+    ugp_mat::Work &W; hipStream_t s;
+    ~Finish() {
+        if (W.join_pending) { (void)hipStreamWaitEvent(s, W.ev_join, 0); W.join_pending = false; }   // (a call that failed between fork and join)
+        if (!W.done && hipEventCreateWithFlags(&W.done, hipEventDisableTiming) != hipSuccess) { W.done = nullptr; return; }
+        (void)hipEventRecord(W.done, s);
+        W.done_on = s;
+    }
+};
+
+// One call, as its stages see it: the request, the workspace set, and the plan of the whole call (ugp_plan.hpp).
+struct PlaceCall {
+    ugp_mat *m; ugp_qset *qs; const PlaceReq &r;
+    ugp_mat::Work &W;
+    hipStream_t s;
+    ugp_mat::Work::Gen *TG;             // the timing ring's entry of this call
+    ugp::PlanTree tree;
+    ugp::PlanCall call;
+    ugp::CallPlan cp;
+    const uint32_t *ex_skip;            // (caller order; + q0 per sub-batch)
+};
+
+// One sub-batch on its way through the stages: its plan, its ranges, and where its pieces of the zeroed buffer are.
+struct SubBatch {
+    uint64_t q0 = 0, nq = 0, e0 = 0, e1 = 0;   // samples [q0, q0 + nq), rows [e0, e1)
+    ugp::SubPlan p;
+    ugp::ZeroLayout z;
+    uint64_t table_dwords = 0, pairs = 0;
+    EventSet *es = nullptr;
+    uint32_t *d_dbottom = nullptr, *d_active = nullptr, *d_queue = nullptr, *d_list_n = nullptr, *d_nitems = nullptr, *d_cnt = nullptr, *d_key = nullptr,
+             *d_useful = nullptr;
+    const uint32_t *slot_of = nullptr, *order = nullptr;
+    ugp::Phase2Uniq uq{};
+    ugp::PlaceArgs a;      // (filled by place_args)
+    ugp::Best8Args b8;     // (filled by packed_walk, with the grid it was launched on)
+    uint32_t blocks = 0;
+};
+
+int nmask_index(const ugp_qset *qs, const ugp_mat *m) {   // which of the query set's N masks is this tree's, or -1
+    int nmi = -1;
+    for (int i = 0; i < 2; i++) if (qs->nmask_for[i] == m) nmi = i;
+    return nmi;
+}
+
+ugp::PlanTree plan_tree(const ugp_mat *m) {
+    const auto &f = m->flat;
+    ugp::PlanTree t;
+    t.n_nodes = f.n_nodes; t.n_sites = f.n_sites; t.n_chunks = f.n_chunks; t.max_chunk8_words = f.max_chunk8_words;
+    t.max_path_muts = f.max_path_muts; t.lds_slots = f.lds_slots; t.mask_not_first = f.mask_not_first;
+    t.coarse = m->coarse != nullptr; t.b3_events = m->d_b3_events.p != nullptr; t.wide_descent = m->wide_descent;
+    return t;
+}
+
+ugp::PlanCall plan_call_facts(const ugp_mat *m, const ugp_qset *qs, const PlaceReq &r) {
+    ugp::PlanCall c;
+    c.Q = qs->n_queries; c.max_rows = qs->max_rows; c.mode = r.mode; c.coarse_only = r.coarse_only; c.ties = r.tie_count != nullptr;
+    c.nmask = nmask_index(qs, m) >= 0; c.sharing = m->sharing; c.share_sets = m->share_sets;
+    if (const ExDev *ex = r.ex) {
+        c.ex.given = true; c.ex.packed = ex->packed; c.ex.mask = ex->mask != nullptr; c.ex.skip = ex->skip != nullptr;
+        c.ex.skip_chunk = ex->skip_chunk != nullptr; c.ex.scores = ex->scores != nullptr;
+    }
+    return c;
+}
+
+int run_place(ugp_mat *m, ugp_qset *qs, const PlaceReq &r);
+
+// ---- stages of a call ------------------------------------------------------------------------------------------------------
+// The timing ring: this call takes the set's oldest entry.
+int open_timing(PlaceCall &c) {
+    ugp_mat::Work &W = c.W;
+    W.cur = (W.cur + 1u) & 3u;
+    c.TG = &W.gens[W.cur];
+    if (int rc = harvest_timing(c.m, W, *c.TG)) return rc;   // (this ring entry's previous call, four uses of the set ago, before its events are recorded again)
+    c.TG->events_used = 0;
+    c.TG->last = {};
+    c.TG->timing_pending = true;
+    return UGP_OK;
+}
+
+// The side stream (see Work::aux, and can_fork in ugp_plan.hpp): made on first use; the first sub-batch's table is filled with the
+// reference bases on it, under the pre-pass (fill_ahead).
+int side_fill(PlaceCall &c) {
+    ugp_mat::Work &W = c.W;
+    if (!c.cp.can_fork) return UGP_OK;
+    if (!W.aux) {
+        HIP_TRY(hipStreamCreateWithFlags(&W.aux, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&W.ev_fork, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&W.ev_fill, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&W.ev_join, hipEventDisableTiming));
+    }
+    if (!c.cp.fill_ahead) return UGP_OK;
+    const uint64_t dw = (uint64_t)((c.call.Q + 511) / 512) * (c.cp.n_sites + ugp::TABLE_CONST_ROWS) * 64;   // (the whole call is one sub-batch)
+    HIP_TRY(W.d_table.reserve(dw));
+    HIP_TRY(hipEventRecord(W.ev_fork, c.s));
+    HIP_TRY(hipStreamWaitEvent(W.aux, W.ev_fork, 0));
+    HIP_TRY(ugp::launch_fill_table(W.d_table.p, c.m->d_site_ref.p, c.cp.n_sites, dw, W.aux));
+    HIP_TRY(hipEventRecord(W.ev_fill, W.aux));
+    return UGP_OK;
+}
+
+// The coarse pre-pass of a sorted call: every sample placed on the coarse tree, into W.d_coarse_res.
+int coarse_pass(PlaceCall &c) {
+    ugp_mat *m = c.m;
+    ugp_mat::Work &W = c.W;
+    ugp_mat::Work::Gen &TG = *c.TG;
+    HIP_TRY(W.d_coarse_res.reserve(c.call.Q));
+    if (!TG.ev_coarse[0]) { HIP_TRY(hipEventCreate(&TG.ev_coarse[0])); HIP_TRY(hipEventCreate(&TG.ev_coarse[1])); }
+    HIP_TRY(hipEventRecord(TG.ev_coarse[0], c.s));
+    // The pre-pass has no phase 2: its walk records which node set every chunk minimum (k_best8<ARG>, k_coarse_result) -- any
+    // node of minimal cost serves the sort and the descent.  (UGP_COARSE_PHASE2=1: the full phase 2 instead, i.e. the
+    // reference's tie-break winner: 0.2 ms more per 16,384 samples, the same answers.)
+    m->coarse->sharing = m->sharing; m->coarse->share_n = m->share_n; m->coarse->share_sets = m->share_sets;
+    PlaceReq cr;
+    cr.out = W.d_coarse_res.p; cr.stream = c.s; cr.wi = c.r.wi;
+    cr.coarse_only = m->coarse->d_node_pos8.p && m->coarse->flat.max_chunk8_words < 65536u && !m->knobs.coarse_phase2;
+    if (int rc = run_place(m->coarse, c.qs, cr)) return rc;
     HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipEventRecord(TG.ev_coarse[1], c.s));
+    TG.coarse_timed = true;
+    return UGP_OK;
+}
+
+// ---- stages of a sub-batch -------------------------------------------------------------------------------------------------
+// The sub-batch's plan, the tuner's word on the third bound, the buffers every path needs, the first event.
+int sub_begin(PlaceCall &c, SubBatch &sb, uint64_t q0) {
+    ugp_mat *m = c.m;
+    ugp_mat::Work &W = c.W;
+    ugp_mat::Work::Gen &TG = *c.TG;
+    const auto &f = m->flat;
+    sb.q0 = q0; sb.nq = std::min<uint64_t>(c.call.Q - q0, c.cp.sub_tiles * 64);
+    if (c.r.mode == 0 && c.r.tie_count) m->tie_sub_batches++;
+    sb.e0 = c.qs->ent_off[q0]; sb.e1 = c.qs->ent_off[q0 + sb.nq];
+    sb.p = ugp::plan_sub(c.tree, m->knobs, c.call, c.cp, sb.nq, sb.e1 - sb.e0);
+    const uint32_t n_tiles512 = sb.p.n_tiles512;
+    sb.table_dwords = (uint64_t)n_tiles512 * (c.cp.n_sites + ugp::TABLE_CONST_ROWS) * 64;
+    HIP_TRY(W.d_table.reserve(sb.table_dwords));
+    uint32_t b3_pos = 0;
+    uint64_t b3_seq = 0;
+    if (sb.p.b3_tuned) { tuner_poll(m); sb.p.b3_want = m->b3_tuner.next(sb.p.b3_class, &b3_pos, &b3_seq); }
+    sb.pairs = (uint64_t)f.n_chunks * n_tiles512 * 8;
+    sb.z = ugp::zero_layout(n_tiles512, c.cp.active_words, c.cp.useful_words, sb.p.b3_want);
+    HIP_TRY(W.d_zero.reserve(sb.z.z_end));
+    sb.d_dbottom = W.d_zero.p + sb.z.z_dbottom; sb.d_active = W.d_zero.p + sb.z.z_active; sb.d_queue = W.d_zero.p + sb.z.z_queue;
+    sb.d_list_n = W.d_zero.p + sb.z.z_list_n; sb.d_nitems = W.d_zero.p + sb.z.z_nitems; sb.d_cnt = W.d_zero.p + sb.z.z_cnt;
+    sb.d_key = W.d_zero.p + sb.z.z_key; sb.d_useful = sb.p.b3_want ? W.d_zero.p + sb.z.z_useful : nullptr;
+    if (c.cp.packed_ok) {
+        HIP_TRY(W.d_lbest.reserve((size_t)f.n_chunks * n_tiles512 * 256));
+        HIP_TRY(W.d_list.reserve((size_t)f.n_chunks * n_tiles512));
+        HIP_TRY(W.d_ub.reserve((size_t)n_tiles512 * 256));
+        if (!c.r.coarse_only) {
+            HIP_TRY(W.d_gbest.reserve((size_t)n_tiles512 * 256));
+            HIP_TRY(W.d_gbest_part.reserve((size_t)ugp::GBEST_SLICES * n_tiles512 * 256));
+            HIP_TRY(W.d_items.reserve(sb.pairs));
+        }
+    } else if (c.r.mode == 0) {
+        const size_t np = (size_t)sb.p.n_tiles * sb.p.G * 64;
+        HIP_TRY(W.d_part_best.reserve(np));
+        HIP_TRY(W.d_part_cnt.reserve(np));
+        HIP_TRY(W.d_part_key.reserve(np));
+    }
+    if (int rc = ensure_events(TG, TG.events_used + 1)) return rc;
+    EventSet &es = TG.events[TG.events_used++];
+    sb.es = &es;
+    es.b3_class = -1;   // (set behind this sub-batch's last event record: until then the events still hold their previous use)
+    es.b3_used = sb.p.b3_want; es.b3_tiles = n_tiles512; es.b3_pos = b3_pos; es.b3_seq = b3_seq; es.b3_first = m->b3_tuner.first;
+    HIP_TRY(hipEventRecord(es.ev[0], c.s));
+    return UGP_OK;
+}
+
+// Locality sort: the sub-batch's samples in the depth-first order of their coarse placements (order, slot_of).
+int locality_sort(PlaceCall &c, SubBatch &sb) {
+    ugp_mat *m = c.m;
+    ugp_mat::Work &W = c.W;
+    const uint64_t nq = sb.nq;
+    HIP_TRY(W.d_keys.reserve(nq)); HIP_TRY(W.d_keys2.reserve(nq)); HIP_TRY(W.d_idx.reserve(nq));
+    HIP_TRY(W.d_order.reserve(nq)); HIP_TRY(W.d_slot.reserve(nq)); HIP_TRY(W.d_bins.reserve(std::max<uint32_t>(m->n_coarse_bins, 1)));
+    size_t tmp_bytes = 0;
+    HIP_TRY(ugp::launch_locality_sort(nullptr, nullptr, (uint32_t)nq, W.d_keys.p, W.d_keys2.p, W.d_idx.p, W.d_order.p,
+                                      W.d_slot.p, nullptr, &tmp_bytes, nullptr, 0, nullptr, c.s));
+    HIP_TRY(W.d_sort_tmp.reserve(tmp_bytes));
+    HIP_TRY(ugp::launch_locality_sort(W.d_coarse_res.p + sb.q0, m->d_coarse2dfs.p, (uint32_t)nq, W.d_keys.p, W.d_keys2.p,
+                                      W.d_idx.p, W.d_order.p, W.d_slot.p, W.d_sort_tmp.p, &tmp_bytes, m->knobs.radix_sort ? nullptr : m->d_coarse_bin.p, m->n_coarse_bins, W.d_bins.p, c.s));
+    sb.slot_of = W.d_slot.p; sb.order = W.d_order.p;
+    return UGP_OK;
+}
+
+// The zeroed buffer and the allele tiles, by one of three builders (SubPlan::nmask, lds_build; else fill + scatter).
+int build_tiles(PlaceCall &c, SubBatch &sb) {
+    ugp_mat *m = c.m;
+    ugp_qset *qs = c.qs;
+    ugp_mat::Work &W = c.W;
+    hipStream_t s = c.s;
+    const auto &f = m->flat;
+    const uint32_t n_sites = c.cp.n_sites, active_words = c.cp.active_words, useful_words = c.cp.useful_words, n_tiles512 = sb.p.n_tiles512;
+    const uint32_t q0 = (uint32_t)sb.q0, nq = (uint32_t)sb.nq;
+    HIP_TRY(hipMemsetAsync(W.d_zero.p, 0, sb.z.z_end * sizeof(uint32_t), s));
+    if (sb.p.nmask) {
+        const int nmi = nmask_index(qs, m);
+        HIP_TRY(ugp::launch_ntiles(W.d_table.p, sb.d_active, active_words, n_tiles512, qs->d_nmask[nmi].p, qs->nmask_words[nmi], sb.order, q0, nq,
+                                   m->d_site_ref.p, n_sites, s));
+        HIP_TRY(ugp::launch_scatter_list(W.d_table.p, sb.d_dbottom, qs->d_pos.p, qs->d_ref.p, qs->d_nuc.p, qs->d_missing.p, qs->d_ent_q.p, m->d_pos2site.p,
+                                         f.max_pos, n_sites, q0, nq, sb.d_active, active_words, sb.slot_of, qs->d_plain_rows.p, qs->d_n_plain.p, qs->d_err.p,
+                                         sb.d_useful, useful_words, s));
+    } else if (sb.p.lds_build)
+        HIP_TRY(ugp::launch_build_tiles(W.d_table.p, sb.d_active, active_words, n_tiles512, qs->d_ent_off.p, q0, sb.order, nq, qs->d_pos.p,
+                                        qs->d_ref.p, qs->d_nuc.p, qs->d_missing.p, m->d_pos2site.p, m->d_site_pos.p, m->d_site_ref.p, n_sites, f.max_pos,
+                                        sb.d_dbottom, qs->d_err.p, s));
+    else {
+        const uint64_t e0 = sb.e0, e1 = sb.e1;
+        if (c.cp.fill_ahead && sb.q0 == 0) HIP_TRY(hipStreamWaitEvent(s, W.ev_fill, 0));
+        else HIP_TRY(ugp::launch_fill_table(W.d_table.p, m->d_site_ref.p, n_sites, sb.table_dwords, s));
+        HIP_TRY(ugp::launch_scatter(W.d_table.p, sb.d_dbottom, qs->d_pos.p + e0, qs->d_ref.p + e0,
+                                    qs->d_nuc.p + e0, qs->d_missing.p + e0, qs->d_ent_q.p + e0, m->d_pos2site.p,
+                                    f.max_pos, n_sites, e1 - e0, q0, sb.d_active, active_words, sb.slot_of, qs->d_err.p, sb.d_useful, useful_words, s));
+    }
+    return UGP_OK;
+}
+
+// third pruning bound: the events of every tile's useful pairs -> block tables (ugp_bound3.hip)
+int b3_tables(PlaceCall &c, SubBatch &sb) {
+    ugp_mat *m = c.m;
+    ugp_mat::Work &W = c.W;
+    hipStream_t s = c.s;
+    const uint32_t n_sites = c.cp.n_sites, n_tiles512 = sb.p.n_tiles512;
+    const uint32_t nb = ugp::b3_blocks(m->stream8_dwords), n_l1 = ugp::b3_div64(nb), n_l2 = ugp::b3_div64(n_l1), n_l3 = ugp::b3_div64(n_l2);
+    HIP_TRY(W.d_b3_pairmask.reserve((size_t)((n_tiles512 + 31) / 32) * n_sites * 4));
+    HIP_TRY(W.d_b3_over.reserve((size_t)n_tiles512 * nb)); HIP_TRY(W.d_b3_under.reserve((size_t)n_tiles512 * nb));
+    HIP_TRY(W.d_b3_l1.reserve((size_t)n_tiles512 * n_l1)); HIP_TRY(W.d_b3_l2.reserve((size_t)n_tiles512 * n_l2)); HIP_TRY(W.d_b3_l3.reserve((size_t)n_tiles512 * n_l3));
+    HIP_TRY(W.d_b3_dev.reserve(1));
+    const ugp::B3Dev hd{W.d_b3_over.p, W.d_b3_under.p, W.d_b3_l1.p, W.d_b3_l2.p, W.d_b3_l3.p, nb, n_l1, n_l2, n_l3};
+    if (memcmp(&hd, &W.b3_host, sizeof hd) != 0) {   // (pointers and sizes: they change only when a buffer grows)
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpy(W.d_b3_dev.p, &hd, sizeof hd, hipMemcpyHostToDevice));
+        W.b3_host = hd;
+    }
+    // (beside the seed descent, which needs the tiles but not the tables: the walk's launch joins the two)
+    hipStream_t on = s;
+    if (c.cp.can_fork) {
+        HIP_TRY(hipEventRecord(W.ev_fork, s));
+        HIP_TRY(hipStreamWaitEvent(W.aux, W.ev_fork, 0));
+        on = W.aux;
+    }
+    HIP_TRY(ugp::launch_b3_tables(sb.d_useful, c.cp.useful_words, n_sites, n_tiles512, m->d_b3_group_off.p, m->d_b3_events.p, nb, W.d_b3_pairmask.p,
+                                  W.d_b3_over.p, W.d_b3_under.p, W.d_b3_l1.p, W.d_b3_l2.p, W.d_b3_l3.p, on));
+    if (c.cp.can_fork) { HIP_TRY(hipEventRecord(W.ev_join, W.aux)); W.join_pending = true; }
+    return UGP_OK;
+}
+
+#ifdef UGP_EXPERIMENTS
+// (UGP_STATS with UGP_SEED_CHECK) debug: the descent's seeds against the previous call's answers, as histograms on stderr
+int seed_check_report(PlaceCall &c, SubBatch &sb) {
+    ugp_mat *m = c.m;
+    ugp_mat::Work &W = c.W;
+    const uint64_t nq = sb.nq, q0 = sb.q0;
+    std::vector<uint32_t> ref(nq), ord(nq);
+    std::vector<ugp_result> prev(nq), coarse(nq);
+    HIP_TRY(hipStreamSynchronize(c.s));
+    HIP_TRY(hipMemcpy(ref.data(), W.d_refined.p, nq * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ord.data(), sb.order, nq * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(prev.data(), W.d_prev_res.p + q0, nq * sizeof(ugp_result), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(coarse.data(), W.d_coarse_res.p + q0, nq * sizeof(ugp_result), hipMemcpyDeviceToHost));
+    uint64_t hist_r[18] = {0}, hist_c[18] = {0}, miss_anc = 0, miss_other = 0, miss_depth = 0;
+    std::vector<uint32_t> c2b(m->coarse ? m->coarse->flat.n_nodes : 0);
+    if (!c2b.empty()) HIP_TRY(hipMemcpy(c2b.data(), m->d_coarse2bfs.p, c2b.size() * 4, hipMemcpyDeviceToHost));
+    for (uint64_t k = 0; k < nq; k++) {
+        const int exact = prev[ord[k]].best_set_difference;
+        hist_r[std::min(17, std::max(0, (int)ref[k] - exact))]++;
+        hist_c[std::min(17, std::max(0, coarse[ord[k]].best_set_difference - exact))]++;
+        if ((int)ref[k] > exact && !c2b.empty() && coarse[ord[k]].best_j < c2b.size()) {   // is the coarse best node an ancestor of the true one?
+            const uint32_t j0 = c2b[coarse[ord[k]].best_j];
+            uint32_t x = prev[ord[k]].best_j, depth = 0;
+            while (x != UINT32_MAX && x != j0 && x != 0) { x = m->h_parent[x]; depth++; }
+            if (x == j0) { miss_anc++; miss_depth += depth; } else {
+                miss_other++;
+                if (miss_other <= 12) {   // a few examples: depths of j0, the true best and their lowest common ancestor
+                    auto depth_of = [&](uint32_t v) { uint32_t d = 0; while (v != 0 && v != UINT32_MAX) { v = m->h_parent[v]; d++; } return d; };
+                    uint32_t a = j0, b = prev[ord[k]].best_j;
+                    uint32_t da = depth_of(a), db = depth_of(b);
+                    const uint32_t da0 = da, db0 = db;
+                    while (da > db) { a = m->h_parent[a]; da--; }
+                    while (db > da) { b = m->h_parent[b]; db--; }
+                    while (a != b) { a = m->h_parent[a]; b = m->h_parent[b]; da--; }
+                    fprintf(stderr, "[ugp stats]   sample %llu: coarse cost %d at depth %u, exact %d (x%u) at depth %u, common ancestor at depth %u, descent %u\n",
+                            (unsigned long long)ord[k], coarse[ord[k]].best_set_difference, da0, exact, prev[ord[k]].num_best, db0, da, ref[k]);
+                }
+            }
+        }
+    }
+    fprintf(stderr, "[ugp stats] loose seeds: coarse best is an ancestor of the true best for %llu (mean distance %.1f), is not for %llu\n",
+            (unsigned long long)miss_anc, miss_anc ? (double)miss_depth / miss_anc : 0.0, (unsigned long long)miss_other);
+    fprintf(stderr, "[ugp stats] seed - exact best, descent:");
+    for (int i = 0; i < 18; i++) fprintf(stderr, " %llu", (unsigned long long)hist_r[i]);
+    fprintf(stderr, "\n[ugp stats] seed - exact best, coarse: ");
+    for (int i = 0; i < 18; i++) fprintf(stderr, " %llu", (unsigned long long)hist_c[i]);
+    fprintf(stderr, "\n");
+    return UGP_OK;
+}
+#endif
+
+// upper bounds of best(s) the pruning starts from (packed path)
+int seed_bounds(PlaceCall &c, SubBatch &sb) {
+    ugp_mat *m = c.m;
+    ugp_mat::Work &W = c.W;
+    hipStream_t s = c.s;
+    const ugp::Knobs &K = m->knobs;
+    const uint32_t n_tiles512 = sb.p.n_tiles512;
+    const uint64_t q0 = sb.q0, nq = sb.nq;
+#ifdef UGP_EXPERIMENTS
+    if (c.cp.sorted && K.seed_prev && W.d_prev_res.cap >= c.call.Q && W.prev_serial == c.qs->serial)   // (experiment: bounds = the previous call's exact answers)
+        HIP_TRY(ugp::launch_seed_ub(W.d_prev_res.p + q0, sb.order, (uint32_t)nq, n_tiles512, W.d_ub.p, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, s));
+    else
+#endif
+    if (c.cp.sorted && !K.no_seed) {
+        // the coarse pass's best costs (real costs of real nodes), tightened by a greedy descent from the coarse best node
+        // through the full tree (k_descend; it reads the sample's alleles from the tiles just built)
+        const uint32_t *refined = nullptr;
+        uint32_t *dnode = nullptr;
+        // (the descent derives D of its start node from "cost(best_j) == best", which both forms of the pre-pass's result
+        // guarantee)
+        if (m->d_node_pair.p && m->d_coarse2bfs.p && !K.no_descent) {
+            HIP_TRY(W.d_refined.reserve(nq));
+            // (round 6) the descent also says WHICH node has the cost it reports: phase 2 answers the samples whose minimum is
+            // attained by one node from it, without a walk (Phase2Uniq; plain searches of trees below 2^31 nodes)
+            if (sb.p.uniq_ok) { HIP_TRY(W.d_dnode.reserve(nq)); HIP_TRY(W.d_dres.reserve((size_t)n_tiles512 * 256)); dnode = W.d_dnode.p; }
+            HIP_TRY(ugp::launch_descend(W.d_coarse_res.p + q0, sb.order, (uint32_t)nq, m->d_coarse2bfs.p, m->d_node_pair.p,
+                                        m->d_parent.p, m->d_stream.p, W.d_table.p, c.cp.n_sites, W.d_refined.p, m->wide_descent, K.descent_max, K.descent_slack,
+                                        c.ex_skip ? c.ex_skip + q0 : nullptr, dnode, s));
+            refined = W.d_refined.p;
+#ifdef UGP_EXPERIMENTS
+            if (K.stats && K.seed_check && W.prev_serial == c.qs->serial && W.d_prev_res.cap >= c.call.Q)
+                if (int rc = seed_check_report(c, sb)) return rc;
+#endif
+        }
+        const uint32_t pad_d = ugp::seed_pad_d(c.tree, K);
+        HIP_TRY(ugp::launch_seed_ub(W.d_coarse_res.p + q0, sb.order, (uint32_t)nq, n_tiles512, W.d_ub.p, refined,
+                                    K.no_pad_fix ? nullptr : sb.d_dbottom, pad_d, c.ex_skip ? c.ex_skip + q0 : nullptr, m->d_coarse2bfs.p, dnode, dnode ? W.d_dres.p : nullptr, s));
+        if (dnode && refined) { sb.uq.dnode = dnode; sb.uq.refined = refined; sb.uq.dres = W.d_dres.p; }
+    } else
+        HIP_TRY(hipMemsetAsync(W.d_ub.p, 0x7F, (size_t)n_tiles512 * 256 * sizeof(uint32_t), s));   // 0x7F7F: above every valid cost
+    return UGP_OK;
+}
+
+// The arguments of the 32-bit kernels and of phase 2 (host only).
+void place_args(PlaceCall &c, SubBatch &sb) {
+    const ugp_mat *m = c.m;
+    const PlaceReq &r = c.r;
+    const auto &f = m->flat;
+    const uint64_t q0 = sb.q0;
+    ugp::PlaceArgs &a = sb.a;
+    memset(&a, 0, sizeof(a));
+    a.stream = m->d_stream.p; a.pre_stream = m->d_pre.p;
+    a.chunk_body_off = m->d_chunk_body.p; a.chunk_pre_off = m->d_chunk_pre.p; a.chunk_node_off = m->d_chunk_node.p;
+    a.stream_t = m->d_stream_t.p; a.chunk_t_off = m->d_chunk_t.p;
+    a.table = c.W.d_table.p; a.dbottom = sb.d_dbottom;
+    a.n_sites = c.cp.n_sites; a.n_chunks = f.n_chunks; a.n_groups = sb.p.G; a.n_tiles = sb.p.n_tiles; a.n_queries = (uint32_t)sb.nq;
+    a.part_best = c.W.d_part_best.p; a.part_cnt = c.W.d_part_cnt.p; a.part_key = c.W.d_part_key.p;
+    a.dfs2bfs = m->d_dfs2bfs.p; a.n_nodes = f.n_nodes;
+    a.scores = r.scores ? r.scores + q0 * f.n_nodes : nullptr;
+    a.best_in = r.best_in ? r.best_in + q0 : nullptr;
+    a.tie_count = r.tie_count ? r.tie_count + q0 : nullptr;
+    a.tie_j = r.tie_j ? r.tie_j + q0 * r.tie_cap : nullptr;
+    a.tie_hu = r.tie_hu ? r.tie_hu + q0 * r.tie_cap : nullptr;
+    a.tie_cap = r.tie_cap;
+    if (const ExDev *ex = r.ex) {
+        a.node_mask = ex->mask; a.skip = ex->skip ? ex->skip + q0 : nullptr; a.alt_rank = ex->alt_rank; a.out_index = ex->out_index;
+        if (r.mode == 0) a.scores = ex->scores ? ex->scores + q0 * f.n_nodes : nullptr;
+    }
+}
+
+// The packed walk (k_best8): its arguments, the tiles' regions and work units, the grid, the launch.  What is decided here is
+// ugp_plan.hpp's plan_walk and plan_grid.
+int packed_walk(PlaceCall &c, SubBatch &sb) {
+    ugp_mat *m = c.m;
+    ugp_mat::Work &W = c.W;
+    hipStream_t s = c.s;
     const auto &f = m->flat;
     const ugp::Knobs &K = m->knobs;
-    const uint64_t Q = qs->n_queries;
-    ugp_mat::Work &W = m->work[wi];
-    m->last_work = wi;
+    const bool coarse_only = c.r.coarse_only;
+    const uint32_t n_tiles512 = sb.p.n_tiles512;
+    const ugp::WalkPlan w = ugp::plan_walk(c.tree, K, c.call, c.cp, sb.p);
+    ugp::Best8Args &b = sb.b8;
+    memset(&b, 0, sizeof(b));
+    b.stream8 = m->d_stream8.p; b.pre8 = m->d_pre8.p;
+    b.chunk8_body_off = m->d_chunk8_body.p; b.chunk8_pre_off = m->d_chunk8_pre.p;
+    b.table = W.d_table.p; b.dbottom = sb.d_dbottom;
+    b.n_sites = c.cp.n_sites; b.n_chunks = f.n_chunks; b.n_groups = sb.p.G; b.n_tiles = n_tiles512;
+    b.lbest = W.d_lbest.p;
+    if (coarse_only) { HIP_TRY(W.d_lpos.reserve((size_t)f.n_chunks * n_tiles512 * 256)); b.lpos = W.d_lpos.p; }
+    b.list = W.d_list.p; b.list_n = sb.d_list_n;
+    ugp::Phase2Uniq &uq = sb.uq;
+    if (uq.dnode) {
+        HIP_TRY(W.d_luniq.reserve((size_t)f.n_chunks * n_tiles512 * 16));   // (64 bytes per record)
+        HIP_TRY(W.d_gcnt.reserve((size_t)n_tiles512 * 256)); HIP_TRY(W.d_gcnt_part.reserve((size_t)ugp::GBEST_SLICES * n_tiles512 * 256));
+        b.luniq = W.d_luniq.p; uq.luniq = W.d_luniq.p; uq.gcnt = W.d_gcnt.p; uq.gcnt_part = W.d_gcnt_part.p;
+    }
+    W.last_list_n = sb.d_list_n; W.last_list_tiles = n_tiles512; W.last_nitems = coarse_only ? nullptr : sb.d_nitems;
+    b.queue = sb.d_queue;
+    b.ub = w.bounds ? W.d_ub.p : nullptr;
+    const uint32_t *hstart = nullptr, *hlen = nullptr;
+    if (w.tile_ranges) {
+        HIP_TRY(W.d_gstart.reserve(n_tiles512)); HIP_TRY(W.d_hlen.reserve(n_tiles512));
+        HIP_TRY(ugp::launch_tile_ranges(W.d_keys2.p, (uint32_t)sb.nq, n_tiles512, m->d_chunk_node.p, f.n_chunks, w.unit_chunks, W.d_gstart.p, W.d_hlen.p, s));
+        hstart = W.d_gstart.p; hlen = W.d_hlen.p;
+    }
+    b.ub_every = w.ub_every;
+    b.freeze_ub = c.ex_skip ? 1u : 0u;   // (the chunk minima include the samples' excluded nodes: no bound may be taken from them)
+    b.refill_all_rows = K.refill_all ? 1u : 0u;
+    b.heavy_prio = K.heavy_prio;
+    b.no_pre_records = w.no_pre_records;
+    HIP_TRY(W.d_units.reserve((size_t)n_tiles512 * w.per_tile_cap * 4));
+    HIP_TRY(W.d_unit_info.reserve(32 + 96));
+    constexpr uint32_t kDynCap = 1u << 17;
+    if (!W.d_dyn.p) {
+        HIP_TRY(W.d_dyn.reserve(kDynCap));
+        W.dyn_epoch = 2047;
+    }
+    if (++W.dyn_epoch >= 2048u) { HIP_TRY(hipMemsetAsync(W.d_dyn.p, 0, (size_t)kDynCap * 8, s)); W.dyn_epoch = 1; }   // (11 bits: stale entries never alias)
+    uint32_t *dyn_ctl = W.d_unit_info.p + 32;
+    b.dyn_ctl = dyn_ctl; b.dyn_units = (unsigned long long *)W.d_dyn.p; b.dyn_cap = kDynCap; b.dyn_epoch = W.dyn_epoch;
+    b.split_cycles = w.split_cycles; b.split_heavy = w.split_heavy; b.split_dense = w.split_dense; b.split_many = w.split_many;
+    HIP_TRY(ugp::launch_build_units(hstart, hlen, n_tiles512, f.n_chunks, w.unit_chunks, w.heavy_chunks, w.grow_every, w.unit_max, w.light_order, w.per_tile_cap,
+                                    W.d_units.p, W.d_unit_info.p, W.d_unit_info.p + 8, dyn_ctl, s));
+    b.units = (const uint4 *)W.d_units.p; b.unit_base = W.d_unit_info.p; b.unit_count = W.d_unit_info.p + 8;
+    HIP_TRY(W.d_stats.reserve(96));
+    if (sb.q0 == 0) { if (K.stats) HIP_TRY(hipMemsetAsync(W.d_stats.p, 0, 96 * sizeof(uint64_t), s)); W.last_words_total = 0; }   // (the counters exist only in the statistics build: no launch for them otherwise)
+    b.stats = K.stats ? W.d_stats.p : nullptr;   // the counters are two contended atomics per skip: debug only
+    if (b.stats && !K.trace.empty() && !coarse_only) {   // per-unit records of this launch, dumped by ugp_get_timing
+        constexpr size_t kTraceCap = 1u << 20;
+        HIP_TRY(W.d_trace.reserve(8 + kTraceCap * 6));
+        HIP_TRY(hipMemsetAsync(W.d_trace.p, 0, 64, s));
+        b.trace = W.d_trace.p; b.trace_cap = kTraceCap;
+    }
+    W.last_words_total += (uint64_t)n_tiles512 * m->stream8_dwords;
+    b.max_slots = f.max_slots;
+    b.lds_slots = f.lds_slots;   // fixed when the tree was flattened (headers touching colder slots are flagged there)
+    b.lds_bits = w.lds_bits;
+    b.b3 = w.b3 ? W.d_b3_dev.p : nullptr;
+    if (b.b3) c.TG->last.bound3 = 1;
+    if (m->occ_lds != w.lds_bytes || m->occ_variant != w.variant) {
+        HIP_TRY(hipDeviceGetAttribute(&m->n_cu, hipDeviceAttributeMultiprocessorCount, m->device));
+        HIP_TRY(ugp::best8_occupancy(w.lds_bytes, w.variant, &m->occ_per_cu));
+        m->occ_lds = w.lds_bytes; m->occ_variant = w.variant;
+    }
+    const uint64_t blocks = ugp::plan_grid(c.tree, K, c.call, c.cp, sb.p, m->occ_per_cu, m->n_cu).blocks;
+    sb.blocks = (uint32_t)blocks;
+    HIP_TRY(W.d_cold.reserve((size_t)blocks * std::max<uint32_t>(f.max_slots - b.lds_slots, 1) * 512));   // 32 B per lane and cold slot
+    b.cold = W.d_cold.p;
+    b.active = sb.d_active; b.active_words = c.cp.active_words;
+    // (UGP_KBEST_EXCLUSIVE: of the two calls that may be on the device at a time, ugp_place_device, only one runs this
+    // kernel at any moment -- measured: 2.77 against 2.71 ms per step when the two persistent grids simply share the
+    // chip; the small kernels in front of the second walk are slowed by the first and become the critical path)
+    const bool exclusive = K.kbest_exclusive;
+    if (exclusive && !coarse_only && m->kb_done && m->kb_done_on != s) HIP_TRY(hipStreamWaitEvent(s, m->kb_done, 0));
+    if (W.join_pending) { HIP_TRY(hipStreamWaitEvent(s, W.ev_join, 0)); W.join_pending = false; }
+    HIP_TRY(ugp::launch_best8(b, (uint32_t)blocks, s));
+    if (exclusive && !coarse_only) {
+        if (!m->kb_done) HIP_TRY(hipEventCreateWithFlags(&m->kb_done, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(m->kb_done, s));
+        m->kb_done_on = s;
+    }
+    HIP_TRY(hipEventRecord(sb.es->ev[2], s));
+    return UGP_OK;
+}
+
+// Behind the packed walk: the excluded nodes taken out again, then the coarse result or phase 2.
+int packed_result(PlaceCall &c, SubBatch &sb) {
+    ugp_mat *m = c.m;
+    ugp_mat::Work &W = c.W;
+    hipStream_t s = c.s;
+    const PlaceReq &r = c.r;
+    const auto &f = m->flat;
+    const uint32_t n_tiles512 = sb.p.n_tiles512;
+    const uint64_t q0 = sb.q0, nq = sb.nq;
+    if (c.ex_skip && !r.coarse_only)   // the one chunk minimum per sample that its excluded node may have set, again without it
+        HIP_TRY(ugp::launch_fix_skip(sb.a, W.d_lbest.p, r.ex->skip_chunk + q0, n_tiles512, m->d_rank2bfs.p, sb.order, f.max_slots, s));
+    if (r.coarse_only)
+        HIP_TRY(ugp::launch_coarse_result(W.d_lbest.p, W.d_lpos.p, W.d_list.p, sb.d_list_n, f.n_chunks, n_tiles512, (uint32_t)nq, m->d_chunk_node.p,
+                                          m->d_chunk8_body.p, m->d_node_pos8.p, m->d_dfs2bfs.p, r.out + q0, s));
+#ifdef UGP_EXPERIMENTS
+    else if (!r.tie_count && m->d_node_pos8.p && m->d_rank_dfs.p && sb.b8.ub && !sb.b8.stats && m->knobs.phase2_packed) {
+        // (experiment, UGP_PHASE2_PACKED=1) phase 2 as a mode of the packed walk: one unit per (tile, chunk) record that holds some
+        // sample's global minimum.  Exact, but 6x slower than k_ties as it stands (1.8 against 0.3 ms per 16,384 samples): its
+        // units re-walk half of their chunks; DESIGN.md 7.2
+        HIP_TRY(W.d_tie_units.reserve((size_t)((n_tiles512 + 7) / 8) * 8 * f.n_chunks * 4));
+        HIP_TRY(W.d_tie_info.reserve(128));
+        HIP_TRY(ugp::launch_phase2_packed(sb.b8, W.d_list.p, sb.d_list_n, W.d_gbest_part.p, W.d_gbest.p, n_tiles512, W.d_tie_units.p, W.d_tie_info.p, sb.d_cnt, sb.d_key,
+                                          m->d_node_pos8.p, m->d_rank_dfs.p, m->d_chunk_node.p, m->d_rank2bfs.p, (uint32_t)nq, r.out + q0, sb.order,
+                                          sb.blocks, s));
+    }
+#endif
+    else
+        HIP_TRY(ugp::launch_phase2(sb.a, W.d_lbest.p, W.d_list.p, sb.d_list_n, W.d_gbest_part.p, W.d_gbest.p, n_tiles512, W.d_items.p, sb.d_nitems,
+                                   (uint32_t)std::min<uint64_t>(sb.pairs, 0xFFFFFFFFull), sb.d_cnt, sb.d_key,
+                                   m->d_rank2bfs.p, r.ex ? r.ex->rank2out : nullptr, r.out + q0, sb.order, f.max_slots, r.tie_count != nullptr,
+                                   sb.uq.luniq ? &sb.uq : nullptr, s));
+    if (r.tie_count) m->tie_lists_filled++;
+    return UGP_OK;
+}
+
+// -p in the output's own order: level by level of the breadth-first expansion, 64 consecutive scores of one sample per
+// wave store (k_scores_level); the depth-first walk of launch_place writes 4 bytes per 32-byte sector
+int level_scores(PlaceCall &c, SubBatch &sb) {
+    ugp_mat *m = c.m;
+    ugp_mat::Work &W = c.W;
+    const auto &f = m->flat;
+    const uint64_t nq = sb.nq;
+    const uint32_t qpad = (uint32_t)((nq + 7) / 8 * 8);
+    const bool d16 = c.qs->max_rows + f.max_path_muts + 2 < 0xFFFFull;
+    const size_t d_words = ((size_t)m->max_level_width * ((qpad + ugp::SCORES_SB - 1) / ugp::SCORES_SB * ugp::SCORES_SB) * (d16 ? 2 : 4) + 3) / 4;
+    HIP_TRY(W.d_part_best.reserve(d_words)); HIP_TRY(W.d_part_cnt.reserve(d_words));   // (the two D arrays; this mode has no partial results)
+    HIP_TRY(ugp::launch_scores_levels(m->d_node_pair.p, m->d_parent.p, m->d_stream.p, W.d_table.p, c.cp.n_sites, sb.d_dbottom, m->h_level_off.data(),
+                                      (uint32_t)m->h_level_off.size() - 1, W.d_part_best.p, W.d_part_cnt.p, d16, m->max_level_width, qpad, (uint32_t)nq, f.n_nodes,
+                                      sb.a.scores, m->knobs.scores_block, c.s));
+    HIP_TRY(hipEventRecord(sb.es->ev[2], c.s));
+    return UGP_OK;
+}
+
+// The one-sample-per-lane walk of the whole tree (32-bit), and for mode 0 the merge of its groups' partial results.
+int lane_walk(PlaceCall &c, SubBatch &sb) {
+    ugp_mat *m = c.m;
+    ugp_mat::Work &W = c.W;
+    const PlaceReq &r = c.r;
+    HIP_TRY(ugp::launch_place(sb.a, r.ex ? r.mode + 4 : r.mode, m->flat.max_slots, c.s));
+    HIP_TRY(hipEventRecord(sb.es->ev[2], c.s));
+    if (r.mode == 0)
+        HIP_TRY(ugp::launch_merge(W.d_part_best.p, W.d_part_cnt.p, W.d_part_key.p, (r.ex && r.ex->rank2out) ? r.ex->rank2out : m->d_rank2bfs.p, sb.p.G,
+                                  (uint32_t)sb.nq, r.out + sb.q0, c.s));
+    return UGP_OK;
+}
+
+// The sub-batch's last event and what ugp_get_timing reports of it.
+int sub_end(PlaceCall &c, SubBatch &sb) {
+    ugp_mat *m = c.m;
+    ugp_mat::Work &W = c.W;
+    ugp_mat::Work::Gen &TG = *c.TG;
+    const ugp::Knobs &K = m->knobs;
+    const bool packed = c.cp.packed_ok;
+    if ((K.seed_prev || K.seed_check) && packed && !c.r.coarse_only && c.r.mode == 0) {
+        HIP_TRY(W.d_prev_res.reserve(c.call.Q));
+        HIP_TRY(hipMemcpyAsync(W.d_prev_res.p + sb.q0, c.r.out + sb.q0, sb.nq * sizeof(ugp_result), hipMemcpyDeviceToDevice, c.s));
+        W.prev_serial = (sb.q0 + sb.nq >= c.call.Q) ? c.qs->serial : 0;   // valid once every sub-batch of THIS query set has been stored
+    }
+    HIP_TRY(hipEventRecord(sb.es->ev[3], c.s));
+    if (sb.p.b3_tuned) sb.es->b3_class = sb.p.b3_class;   // (from here on the tuner may read this sub-batch's events)
+    W.last_used_best8 = packed;
+    TG.last.packed_path = packed ? 1u : 0u;
+    sb.es->used = true;
+    TG.last.place_launches++;
+    TG.last.n_tiles += packed ? sb.p.n_tiles512 : sb.p.n_tiles;
+    TG.last.n_groups = sb.p.G;
+    return UGP_OK;
+}
+
+// Every placement entry point ends here.  What is decided -- path, sub-batch size, groups, builders, units, grid -- is ugp_plan.hpp's;
+// this is the order of the work on the device.
+int run_place(ugp_mat *m, ugp_qset *qs, const PlaceReq &r) {
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = r.stream;
+    PlaceCall c{m, qs, r, m->work[r.wi], s, nullptr, {}, {}, {}, nullptr};
+    m->last_work = r.wi;
     // the previous call that used this workspace set may have run on another stream
-    if (W.done && W.done_on != s) HIP_TRY(hipStreamWaitEvent(s, W.done, 0));
-    struct Finish {   // whatever way this call ends: mark the set's last use
-        ugp_mat::Work &W; hipStream_t s;
-        ~Finish() {
-            if (W.join_pending) { (void)hipStreamWaitEvent(s, W.ev_join, 0); W.join_pending = false; }   // (a call that failed between fork and join)
-            if (!W.done && hipEventCreateWithFlags(&W.done, hipEventDisableTiming) != hipSuccess) { W.done = nullptr; return; }
-            (void)hipEventRecord(W.done, s);
-            W.done_on = s;
-        }
-    } finish{W, s};
-    W.cur = (W.cur + 1u) & 3u;
-    ugp_mat::Work::Gen &TG = W.gens[W.cur];
-    if (int rc = harvest_timing(m, W, TG)) return rc;   // (this ring entry's previous call, four uses of the set ago, before its events are recorded again)
-    TG.events_used = 0;
-    TG.last = {};
-    TG.timing_pending = true;
-    if (Q == 0) return UGP_OK;
-    // at least one table row, so that words without a row of their own (headers,
-    // reference-everywhere sites) always have the valid row 0 to fetch
-    const uint32_t n_sites = std::max<uint32_t>((uint32_t)f.n_sites, 1u);
-    const uint32_t active_words = (n_sites + 31) / 32;
-    // Locality sort: place every sample on the coarse top-of-the-tree MAT first; samples are then
-    // assigned to 512-sample tiles in the DFS order of that coarse placement (k_sort_keys).
-    // (16-bit phase 1: every D / cost must stay below 0x7F7F, the value the shared upper bounds start from;
-    // a tree with a masked mutation behind an ordinary one on the same node -- never produced by the reference's
-    // sorted Node::add_mutation, mutation_annotated_tree.cpp:720-752 -- needs the order-aware 32-bit walk)
-    // (the extended searches take the packed path too when their options are the kind it can express: a node order / distance is a
-    // tie rank of phase 2, a node mask has been turned into exclusions by the caller, a per-sample excluded node is taken out of
-    // the one chunk minimum it can have set, behind phase 1 (k_fix_skip); per-node scores stay on the one-sample-per-lane kernel)
-    const bool ex_packable = ex && ex->packed && !ex->mask && (!ex->skip || ex->skip_chunk) && !ex->scores;
-    const uint32_t *const ex_skip = (ex_packable && ex->skip) ? ex->skip : nullptr;   // (caller order; + q0 per sub-batch)
-    const bool packed_ok = (mode == 0) && (!ex || ex_packable) && !K.force_v1 && !f.mask_not_first && (qs->max_rows + f.max_path_muts + 2 < 0x7F7Full);
-    const bool sorted = packed_ok && m->coarse && Q > 512 && !K.no_sort && !K.no_prune;
-    TG.coarse_timed = false;
-    // The side stream (see Work::aux): only where there is something to put on it -- the sorted main pass.
-    // And only for a call that has the device to itself: measured with three calls in flight (six queues instead of three), the
-    // cross-queue waits cost far more than the overlap gives -- 12.9 -> 10.4 M placements/s; a lone call gains 45 us of its 1.96 ms.
-    // OPT-IN (UGP_FORK=1) since the end of round 6: a process has four hardware queues by default, a handle's three streams plus
-    // their side streams oversubscribe them, and which streams then share a queue -- and serialise -- depends on what the process
-    // created before: the SECOND handle of a process ran its overlapped calls one after the other (tools/probe_context.py: config 3's
-    // size 7.7 -> 4.7 M/s, the headline workload 13.9 -> 9.6) for a gain of 45 us on the first.
-    const bool can_fork = sorted && !coarse_only && !K.no_fork && !m->sharing;
-    bool fill_ahead = false;   // the first sub-batch's table has been filled with the reference bases on the side stream, under the pre-pass
-    if (can_fork) {
-        if (!W.aux) {
-            HIP_TRY(hipStreamCreateWithFlags(&W.aux, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&W.ev_fork, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&W.ev_fill, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&W.ev_join, hipEventDisableTiming));
-        }
-        // plain batches (fill + scatter; the other tile builders write every row themselves): the fill depends on nothing but the set
-        // being free, which `s` has just waited for
-        int nmi0 = -1;
-        for (int i = 0; i < 2; i++) if (qs->nmask_for[i] == m && n_sites) nmi0 = i;
-        const uint64_t nq0 = std::min<uint64_t>(Q, (uint64_t)kMaxTilesPerLaunch * 64);
-        if (nmi0 < 0 && K.tile_build <= 0 && f.n_sites && nq0 == Q) {
-            const uint64_t dw = (uint64_t)((nq0 + 511) / 512) * (n_sites + ugp::TABLE_CONST_ROWS) * 64;
-            HIP_TRY(W.d_table.reserve(dw));
-            HIP_TRY(hipEventRecord(W.ev_fork, s));
-            HIP_TRY(hipStreamWaitEvent(W.aux, W.ev_fork, 0));
-            HIP_TRY(ugp::launch_fill_table(W.d_table.p, m->d_site_ref.p, n_sites, dw, W.aux));
-            HIP_TRY(hipEventRecord(W.ev_fill, W.aux));
-            fill_ahead = true;
-        }
-    }
-    if (sorted) {
-        HIP_TRY(W.d_coarse_res.reserve(Q));
-        if (!TG.ev_coarse[0]) { HIP_TRY(hipEventCreate(&TG.ev_coarse[0])); HIP_TRY(hipEventCreate(&TG.ev_coarse[1])); }
-        HIP_TRY(hipEventRecord(TG.ev_coarse[0], s));
-        // The pre-pass has no phase 2: its walk records which node set every chunk minimum (k_best8<ARG>, k_coarse_result) -- any
-        // node of minimal cost serves the sort and the descent.  (UGP_COARSE_PHASE2=1: the full phase 2 instead, i.e. the
-        // reference's tie-break winner: 0.2 ms more per 16,384 samples, the same answers.)
-        m->coarse->sharing = m->sharing; m->coarse->share_n = m->share_n; m->coarse->share_sets = m->share_sets;
-        const bool coarse_arg = m->coarse->d_node_pos8.p && m->coarse->flat.max_chunk8_words < 65536u && !K.coarse_phase2;
-        if (int rc = run_place(m->coarse, qs, 0, W.d_coarse_res.p, nullptr, nullptr, nullptr, nullptr, nullptr, 0, s, coarse_arg, nullptr, wi)) return rc;
-        HIP_TRY(hipSetDevice(m->device));
-        HIP_TRY(hipEventRecord(TG.ev_coarse[1], s));
-        TG.coarse_timed = true;
-    }
-    // samples per sub-batch: at most 262,144, and few enough that the per-(chunk, sample) minima of phase 1
-    // (2 bytes each) stay below 24 GiB (8 until round 4: 131,072 samples per launch sequence at 10M nodes; the walk does
-    // 16,384 samples' worth of work in 0.55 ms at 262,144 per launch against 0.68 at 65,536 -- 1M queries per call 20.0 -> 23.1 M/s)
-    uint64_t sub_tiles = kMaxTilesPerLaunch;
-    if (m->flat.n_chunks) sub_tiles = std::min<uint64_t>(sub_tiles, std::max<uint64_t>(8, ((K.lbest_gib ? (uint64_t)K.lbest_gib : 24ull) << 30) / ((uint64_t)m->flat.n_chunks * 128) & ~7ull));
-    for (uint64_t q0 = 0; q0 < Q; q0 += sub_tiles * 64) {
-        const uint64_t nq = std::min<uint64_t>(Q - q0, sub_tiles * 64);
-        if (mode == 0 && d_tie_count) m->tie_sub_batches++;
-        const uint32_t n_tiles = (uint32_t)((nq + 63) / 64);
-        const uint32_t n_tiles512 = (uint32_t)((nq + 511) / 512);
-        // 16-bit packed phase 1 is exact while every D / cost stays below 0x8000 (bit 15 is the ineligible flag)
-        const bool use8 = packed_ok;
-        uint32_t G = pick_groups(m, n_tiles);
-        if (use8) {   // work units of a few chunks each, pulled from per-XCD queues by persistent waves (see k_best8)
-            uint32_t unit_chunks = 16;   // (most far units end in their preamble: the replay is the cost to amortise)
-            if (K.unit_chunks) unit_chunks = K.unit_chunks;
-            G = std::max<uint32_t>(1, (f.n_chunks + unit_chunks - 1) / unit_chunks);
-            // a small batch still has to fill the chip: at least ~4096 units in total
-            while (G < f.n_chunks && (uint64_t)G * n_tiles512 < 4096) G = std::min<uint32_t>(f.n_chunks, G * 2);
-            if (K.groups) G = std::min<uint32_t>(f.n_chunks, K.groups);
-        }
-        const uint64_t table_dwords = (uint64_t)n_tiles512 * (n_sites + ugp::TABLE_CONST_ROWS) * 64;
-        HIP_TRY(W.d_table.reserve(table_dwords));
-        const uint64_t pairs = (uint64_t)f.n_chunks * n_tiles512 * 8;
-        // every small buffer that has to start from zero lives in ONE allocation cleared by one memset:
-        // D(bottom) counters, active-row bitmap, work-queue heads, record lists' lengths, phase-2 item count, tie counts / keys
-        // Third pruning bound (round 5): for the sorted main walk of batches of up to 256 tiles, when the tree carries its posting lists
-        // and the tiles are built by the scatter kernels (they mark the tile's useful (site, allele) pairs)
-        const uint32_t useful_words = (n_sites + 7) / 8;
-        // (what the walk will be launched with is decided here, in front of the tile build: a batch whose walk keeps its active-row
-        // bitmap in LDS -- lds_bits == 1 -- has no third-bound variant, and building the tables for it, or letting the tuner book
-        // the batch as one "with", would be cost without effect: ADVICE r5)
-        int nmi = -1;   // the query set carries N masks for this tree
-        for (int i = 0; i < 2; i++) if (qs->nmask_for[i] == m && use8 && n_sites) nmi = i;
-        const uint64_t e0 = qs->ent_off[q0], e1 = qs->ent_off[q0 + nq];
-        // many rows per sample (high-ambiguity queries): the (tile, site block)-in-LDS builder; otherwise fill + one atomic per row
-        // (only for batches in arrival order, i.e. the coarse pass: consecutive threads then read neighbouring row lists; behind
-        // the locality sort the builder's uncoalesced row reads cost more than the scatter's atomics -- measured on config 5:
-        // coarse pass 2.72 -> 2.33 ms, sorted build 1.77 -> 2.03 ms)
-        bool lds_build = use8 && n_sites && !sorted && (e1 - e0) >= (uint64_t)nq * 128;
-        if (K.tile_build >= 0) lds_build = use8 && n_sites && K.tile_build != 0;
-        uint32_t lds_bits_plan = 0;
-        if (use8) {
-            const bool stats_on = K.stats;
-            lds_bits_plan = (!stats_on && (size_t)active_words * 4 <= 4096 && n_tiles512 >= 64 && !m->sharing) ? 1u : 0u;
-            if (nmi >= 0 && !stats_on) lds_bits_plan = 2u;
-            if (K.lds_bits >= 0) lds_bits_plan = stats_on ? 0u : (K.lds_bits == 2 ? 2u : (((size_t)active_words * 4 <= 4096 && K.lds_bits != 0) ? 1u : 0u));
-        }
-        const bool b3_can = use8 && !coarse_only && sorted && m->d_b3_events.p && !K.no_bound3 && K.bound3 != 0 && !K.no_prune && n_tiles512 <= 256 && K.tile_build <= 0 &&
-                            lds_bits_plan != 1u && !(lds_build && nmi < 0);
-        bool b3_want = b3_can;
-        const int b3_class = B3Tuner::class_of(e1 - e0, nq);
-        uint32_t b3_pos = 0;
-        uint64_t b3_seq = 0;
-        // UGP_BOUND3 unset: decided from what is known of the tree and of the batch (ugp_tuner.hpp b3_static_choice) -- every call of a
-        // kind runs the same way from the first one on; UGP_BOUND3=auto: the handle's run-time A/B (B3Tuner); 1 / 0: pinned
-        const bool b3_tuned = b3_can && K.bound3 == -1;
-        if (b3_tuned) { tuner_poll(m); b3_want = m->b3_tuner.next(b3_class, &b3_pos, &b3_seq); }
-        else if (b3_can && K.bound3 < -1) b3_want = ugp::b3_static_choice(m->wide_descent, b3_class, f.n_nodes);
-        const size_t z_dbottom = 0, z_active = z_dbottom + (size_t)n_tiles512 * 512, z_queue = z_active + (size_t)n_tiles512 * active_words,
-                     z_list_n = z_queue + 8, z_nitems = z_list_n + n_tiles512, z_cnt = z_nitems + 8, z_key = z_cnt + (size_t)n_tiles512 * 512,
-                     z_useful = z_key + (size_t)n_tiles512 * 512, z_end = z_useful + (b3_want ? (size_t)n_tiles512 * useful_words : 0);
-        HIP_TRY(W.d_zero.reserve(z_end));
-        uint32_t *const d_dbottom = W.d_zero.p + z_dbottom, *const d_active = W.d_zero.p + z_active, *const d_queue = W.d_zero.p + z_queue,
-                 *const d_list_n = W.d_zero.p + z_list_n, *const d_nitems = W.d_zero.p + z_nitems, *const d_cnt = W.d_zero.p + z_cnt,
-                 *const d_key = W.d_zero.p + z_key, *const d_useful = b3_want ? W.d_zero.p + z_useful : nullptr;
-        if (use8) {
-            HIP_TRY(W.d_lbest.reserve((size_t)f.n_chunks * n_tiles512 * 256));
-            HIP_TRY(W.d_list.reserve((size_t)f.n_chunks * n_tiles512));
-            HIP_TRY(W.d_ub.reserve((size_t)n_tiles512 * 256));
-            if (!coarse_only) {
-                HIP_TRY(W.d_gbest.reserve((size_t)n_tiles512 * 256));
-                HIP_TRY(W.d_gbest_part.reserve((size_t)ugp::GBEST_SLICES * n_tiles512 * 256));
-                HIP_TRY(W.d_items.reserve(pairs));
-            }
-        } else if (mode == 0) {
-            const size_t np = (size_t)n_tiles * G * 64;
-            HIP_TRY(W.d_part_best.reserve(np));
-            HIP_TRY(W.d_part_cnt.reserve(np));
-            HIP_TRY(W.d_part_key.reserve(np));
-        }
-        if (int rc = ensure_events(TG, TG.events_used + 1)) return rc;
-        EventSet &es = TG.events[TG.events_used++];
-        es.b3_class = -1;   // (set behind this sub-batch's last event record: until then the events still hold their previous use)
-        es.b3_used = b3_want; es.b3_tiles = n_tiles512; es.b3_pos = b3_pos; es.b3_seq = b3_seq; es.b3_first = m->b3_tuner.first;
-
-        HIP_TRY(hipEventRecord(es.ev[0], s));
-        const uint32_t *slot_of = nullptr, *order = nullptr;
-        if (sorted) {
-            HIP_TRY(W.d_keys.reserve(nq)); HIP_TRY(W.d_keys2.reserve(nq)); HIP_TRY(W.d_idx.reserve(nq));
-            HIP_TRY(W.d_order.reserve(nq)); HIP_TRY(W.d_slot.reserve(nq)); HIP_TRY(W.d_bins.reserve(std::max<uint32_t>(m->n_coarse_bins, 1)));
-            size_t tmp_bytes = 0;
-            HIP_TRY(ugp::launch_locality_sort(nullptr, nullptr, (uint32_t)nq, W.d_keys.p, W.d_keys2.p, W.d_idx.p, W.d_order.p,
-                                              W.d_slot.p, nullptr, &tmp_bytes, nullptr, 0, nullptr, s));
-            HIP_TRY(W.d_sort_tmp.reserve(tmp_bytes));
-            HIP_TRY(ugp::launch_locality_sort(W.d_coarse_res.p + q0, m->d_coarse2dfs.p, (uint32_t)nq, W.d_keys.p, W.d_keys2.p,
-                                              W.d_idx.p, W.d_order.p, W.d_slot.p, W.d_sort_tmp.p, &tmp_bytes, K.radix_sort ? nullptr : m->d_coarse_bin.p, m->n_coarse_bins, W.d_bins.p, s));
-            slot_of = W.d_slot.p; order = W.d_order.p;
-        }
-        HIP_TRY(hipMemsetAsync(W.d_zero.p, 0, z_end * sizeof(uint32_t), s));
-        if (nmi >= 0) {
-            HIP_TRY(ugp::launch_ntiles(W.d_table.p, d_active, active_words, n_tiles512, qs->d_nmask[nmi].p, qs->nmask_words[nmi], order, (uint32_t)q0, (uint32_t)nq,
-                                       m->d_site_ref.p, n_sites, s));
-            HIP_TRY(ugp::launch_scatter_list(W.d_table.p, d_dbottom, qs->d_pos.p, qs->d_ref.p, qs->d_nuc.p, qs->d_missing.p, qs->d_ent_q.p, m->d_pos2site.p,
-                                             f.max_pos, n_sites, (uint32_t)q0, (uint32_t)nq, d_active, active_words, slot_of, qs->d_plain_rows.p, qs->d_n_plain.p, qs->d_err.p,
-                                             d_useful, useful_words, s));
-        } else if (lds_build)
-            HIP_TRY(ugp::launch_build_tiles(W.d_table.p, d_active, active_words, n_tiles512, qs->d_ent_off.p, (uint32_t)q0, order, (uint32_t)nq, qs->d_pos.p,
-                                            qs->d_ref.p, qs->d_nuc.p, qs->d_missing.p, m->d_pos2site.p, m->d_site_pos.p, m->d_site_ref.p, n_sites, f.max_pos,
-                                            d_dbottom, qs->d_err.p, s));
-        else {
-        if (fill_ahead && q0 == 0) HIP_TRY(hipStreamWaitEvent(s, W.ev_fill, 0));
-        else HIP_TRY(ugp::launch_fill_table(W.d_table.p, m->d_site_ref.p, n_sites, table_dwords, s));
-        HIP_TRY(ugp::launch_scatter(W.d_table.p, d_dbottom, qs->d_pos.p + e0, qs->d_ref.p + e0,
-                                    qs->d_nuc.p + e0, qs->d_missing.p + e0, qs->d_ent_q.p + e0, m->d_pos2site.p,
-                                    f.max_pos, n_sites, e1 - e0, (uint32_t)q0, d_active, active_words, slot_of, qs->d_err.p, d_useful, useful_words, s));
-        }
-        // third pruning bound: the events of every tile's useful pairs -> block tables (ugp_bound3.hip)
-        const bool b3_on = b3_want;
-        if (b3_on) {
-            const uint32_t nb = ugp::b3_blocks(m->stream8_dwords), n_l1 = ugp::b3_div64(nb), n_l2 = ugp::b3_div64(n_l1), n_l3 = ugp::b3_div64(n_l2);
-            HIP_TRY(W.d_b3_pairmask.reserve((size_t)((n_tiles512 + 31) / 32) * n_sites * 4));
-            HIP_TRY(W.d_b3_over.reserve((size_t)n_tiles512 * nb)); HIP_TRY(W.d_b3_under.reserve((size_t)n_tiles512 * nb));
-            HIP_TRY(W.d_b3_l1.reserve((size_t)n_tiles512 * n_l1)); HIP_TRY(W.d_b3_l2.reserve((size_t)n_tiles512 * n_l2)); HIP_TRY(W.d_b3_l3.reserve((size_t)n_tiles512 * n_l3));
-            HIP_TRY(W.d_b3_dev.reserve(1));
-            const ugp::B3Dev hd{W.d_b3_over.p, W.d_b3_under.p, W.d_b3_l1.p, W.d_b3_l2.p, W.d_b3_l3.p, nb, n_l1, n_l2, n_l3};
-            if (memcmp(&hd, &W.b3_host, sizeof hd) != 0) {   // (pointers and sizes: they change only when a buffer grows)
-                HIP_TRY(hipStreamSynchronize(s));
-                HIP_TRY(hipMemcpy(W.d_b3_dev.p, &hd, sizeof hd, hipMemcpyHostToDevice));
-                W.b3_host = hd;
-            }
-            // (beside the seed descent, which needs the tiles but not the tables: the walk's launch joins the two)
-            hipStream_t sb = s;
-            if (can_fork) {
-                HIP_TRY(hipEventRecord(W.ev_fork, s));
-                HIP_TRY(hipStreamWaitEvent(W.aux, W.ev_fork, 0));
-                sb = W.aux;
-            }
-            HIP_TRY(ugp::launch_b3_tables(d_useful, useful_words, n_sites, n_tiles512, m->d_b3_group_off.p, m->d_b3_events.p, nb, W.d_b3_pairmask.p,
-                                          W.d_b3_over.p, W.d_b3_under.p, W.d_b3_l1.p, W.d_b3_l2.p, W.d_b3_l3.p, sb));
-            if (can_fork) { HIP_TRY(hipEventRecord(W.ev_join, W.aux)); W.join_pending = true; }
-        }
-        // phase 2 without a walk for the samples whose minimum is attained by one node (ugp_kernels.hpp Phase2Uniq): the plain search only
-        ugp::Phase2Uniq uq{};
-        const bool uniq_ok = use8 && sorted && !coarse_only && mode == 0 && !ex && !d_tie_count && f.n_nodes < (1ull << 31) && !K.no_uniq;
-        if (use8) {   // upper bounds of best(s) the pruning starts from
-#ifdef UGP_EXPERIMENTS
-            if (sorted && K.seed_prev && W.d_prev_res.cap >= Q && W.prev_serial == qs->serial)   // (experiment: bounds = the previous call's exact answers)
-                HIP_TRY(ugp::launch_seed_ub(W.d_prev_res.p + q0, order, (uint32_t)nq, n_tiles512, W.d_ub.p, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, s));
-            else
-#endif
-            if (sorted && !K.no_seed) {
-                // the coarse pass's best costs (real costs of real nodes), tightened by a greedy descent from the coarse best node
-                // through the full tree (k_descend; it reads the sample's alleles from the tiles just built)
-                const uint32_t *refined = nullptr;
-                uint32_t *dnode = nullptr;
-                // (the descent derives D of its start node from "cost(best_j) == best", which both forms of the pre-pass's result
-                // guarantee)
-                if (m->d_node_pair.p && m->d_coarse2bfs.p && !K.no_descent) {
-                    HIP_TRY(W.d_refined.reserve(nq));
-                    // (round 6) the descent also says WHICH node has the cost it reports: phase 2 answers the samples whose minimum is
-                    // attained by one node from it, without a walk (Phase2Uniq; plain searches of trees below 2^31 nodes)
-                    if (uniq_ok) { HIP_TRY(W.d_dnode.reserve(nq)); HIP_TRY(W.d_dres.reserve((size_t)n_tiles512 * 256)); dnode = W.d_dnode.p; }
-                    HIP_TRY(ugp::launch_descend(W.d_coarse_res.p + q0, order, (uint32_t)nq, m->d_coarse2bfs.p, m->d_node_pair.p,
-                                                m->d_parent.p, m->d_stream.p, W.d_table.p, n_sites, W.d_refined.p, m->wide_descent, K.descent_max, K.descent_slack,
-                                                ex_skip ? ex_skip + q0 : nullptr, dnode, s));
-                    refined = W.d_refined.p;
-#ifdef UGP_EXPERIMENTS
-                    if (K.stats && K.seed_check && W.prev_serial == qs->serial && W.d_prev_res.cap >= Q) {   // debug: seeds against the previous call's answers
-                        std::vector<uint32_t> ref(nq), ord(nq);
-                        std::vector<ugp_result> prev(nq), coarse(nq);
-                        HIP_TRY(hipStreamSynchronize(s));
-                        HIP_TRY(hipMemcpy(ref.data(), W.d_refined.p, nq * 4, hipMemcpyDeviceToHost));
-                        HIP_TRY(hipMemcpy(ord.data(), order, nq * 4, hipMemcpyDeviceToHost));
-                        HIP_TRY(hipMemcpy(prev.data(), W.d_prev_res.p + q0, nq * sizeof(ugp_result), hipMemcpyDeviceToHost));
-                        HIP_TRY(hipMemcpy(coarse.data(), W.d_coarse_res.p + q0, nq * sizeof(ugp_result), hipMemcpyDeviceToHost));
-                        uint64_t hist_r[18] = {0}, hist_c[18] = {0}, miss_anc = 0, miss_other = 0, miss_depth = 0;
-                        std::vector<uint32_t> c2b(m->coarse ? m->coarse->flat.n_nodes : 0);
-                        if (!c2b.empty()) HIP_TRY(hipMemcpy(c2b.data(), m->d_coarse2bfs.p, c2b.size() * 4, hipMemcpyDeviceToHost));
-                        for (uint64_t k = 0; k < nq; k++) {
-                            const int exact = prev[ord[k]].best_set_difference;
-                            hist_r[std::min(17, std::max(0, (int)ref[k] - exact))]++;
-                            hist_c[std::min(17, std::max(0, coarse[ord[k]].best_set_difference - exact))]++;
-                            if ((int)ref[k] > exact && !c2b.empty() && coarse[ord[k]].best_j < c2b.size()) {   // is the coarse best node an ancestor of the true one?
-                                const uint32_t j0 = c2b[coarse[ord[k]].best_j];
-                                uint32_t x = prev[ord[k]].best_j, depth = 0;
-                                while (x != UINT32_MAX && x != j0 && x != 0) { x = m->h_parent[x]; depth++; }
-                                if (x == j0) { miss_anc++; miss_depth += depth; } else {
-                                    miss_other++;
-                                    if (miss_other <= 12) {   // a few examples: depths of j0, the true best and their lowest common ancestor
-                                        auto depth_of = [&](uint32_t v) { uint32_t d = 0; while (v != 0 && v != UINT32_MAX) { v = m->h_parent[v]; d++; } return d; };
-                                        uint32_t a = j0, b = prev[ord[k]].best_j;
-                                        uint32_t da = depth_of(a), db = depth_of(b);
-                                        const uint32_t da0 = da, db0 = db;
-                                        while (da > db) { a = m->h_parent[a]; da--; }
-                                        while (db > da) { b = m->h_parent[b]; db--; }
-                                        while (a != b) { a = m->h_parent[a]; b = m->h_parent[b]; da--; }
-                                        fprintf(stderr, "[ugp stats]   sample %llu: coarse cost %d at depth %u, exact %d (x%u) at depth %u, common ancestor at depth %u, descent %u\n",
-                                                (unsigned long long)ord[k], coarse[ord[k]].best_set_difference, da0, exact, prev[ord[k]].num_best, db0, da, ref[k]);
-                                    }
-                                }
-                            }
-                        }
-                        fprintf(stderr, "[ugp stats] loose seeds: coarse best is an ancestor of the true best for %llu (mean distance %.1f), is not for %llu\n",
-                                (unsigned long long)miss_anc, miss_anc ? (double)miss_depth / miss_anc : 0.0, (unsigned long long)miss_other);
-                        fprintf(stderr, "[ugp stats] seed - exact best, descent:");
-                        for (int i = 0; i < 18; i++) fprintf(stderr, " %llu", (unsigned long long)hist_r[i]);
-                        fprintf(stderr, "\n[ugp stats] seed - exact best, coarse: ");
-                        for (int i = 0; i < 18; i++) fprintf(stderr, " %llu", (unsigned long long)hist_c[i]);
-                        fprintf(stderr, "\n");
-                    }
-#endif
-                }
-                // (the unused slots of the last tile: far from everything, see k_seed_ub; 16-bit safe by the guard of the packed path)
-                const uint32_t pad_d = K.no_pad_fix ? 0u : (uint32_t)std::min<uint64_t>(4096, 0x7F7Eu - 2u - std::min<uint64_t>(f.max_path_muts, 0x7F00u));
-                HIP_TRY(ugp::launch_seed_ub(W.d_coarse_res.p + q0, order, (uint32_t)nq, n_tiles512, W.d_ub.p, refined,
-                                            K.no_pad_fix ? nullptr : d_dbottom, pad_d, ex_skip ? ex_skip + q0 : nullptr, m->d_coarse2bfs.p, dnode, dnode ? W.d_dres.p : nullptr, s));
-                if (dnode && refined) { uq.dnode = dnode; uq.refined = refined; uq.dres = W.d_dres.p; }
-            } else
-                HIP_TRY(hipMemsetAsync(W.d_ub.p, 0x7F, (size_t)n_tiles512 * 256 * sizeof(uint32_t), s));   // 0x7F7F: above every valid cost
-        }
-        HIP_TRY(hipEventRecord(es.ev[1], s));
-
-        ugp::PlaceArgs a;
-        memset(&a, 0, sizeof(a));
-        a.stream = m->d_stream.p; a.pre_stream = m->d_pre.p;
-        a.chunk_body_off = m->d_chunk_body.p; a.chunk_pre_off = m->d_chunk_pre.p; a.chunk_node_off = m->d_chunk_node.p;
-        a.stream_t = m->d_stream_t.p; a.chunk_t_off = m->d_chunk_t.p;
-        a.table = W.d_table.p; a.dbottom = d_dbottom;
-        a.n_sites = n_sites; a.n_chunks = f.n_chunks; a.n_groups = G; a.n_tiles = n_tiles; a.n_queries = (uint32_t)nq;
-        a.part_best = W.d_part_best.p; a.part_cnt = W.d_part_cnt.p; a.part_key = W.d_part_key.p;
-        a.dfs2bfs = m->d_dfs2bfs.p; a.n_nodes = f.n_nodes;
-        a.scores = d_scores ? d_scores + q0 * f.n_nodes : nullptr;
-        a.best_in = d_best_in ? d_best_in + q0 : nullptr;
-        a.tie_count = d_tie_count ? d_tie_count + q0 : nullptr;
-        a.tie_j = d_tie_j ? d_tie_j + q0 * tie_cap : nullptr;
-        a.tie_hu = d_tie_hu ? d_tie_hu + q0 * tie_cap : nullptr;
-        a.tie_cap = tie_cap;
-        if (ex) {
-            a.node_mask = ex->mask; a.skip = ex->skip ? ex->skip + q0 : nullptr; a.alt_rank = ex->alt_rank; a.out_index = ex->out_index;
-            if (mode == 0) a.scores = ex->scores ? ex->scores + q0 * f.n_nodes : nullptr;
-        }
-        if (use8) {
-            ugp::Best8Args b;
-            memset(&b, 0, sizeof(b));
-            b.stream8 = m->d_stream8.p; b.pre8 = m->d_pre8.p;
-            b.chunk8_body_off = m->d_chunk8_body.p; b.chunk8_pre_off = m->d_chunk8_pre.p;
-            b.table = W.d_table.p; b.dbottom = d_dbottom;
-            b.n_sites = n_sites; b.n_chunks = f.n_chunks; b.n_groups = G; b.n_tiles = n_tiles512;
-            b.lbest = W.d_lbest.p;
-            if (coarse_only) { HIP_TRY(W.d_lpos.reserve((size_t)f.n_chunks * n_tiles512 * 256)); b.lpos = W.d_lpos.p; }
-            b.list = W.d_list.p; b.list_n = d_list_n;
-            if (uq.dnode) {
-                HIP_TRY(W.d_luniq.reserve((size_t)f.n_chunks * n_tiles512 * 16));   // (64 bytes per record)
-                HIP_TRY(W.d_gcnt.reserve((size_t)n_tiles512 * 256)); HIP_TRY(W.d_gcnt_part.reserve((size_t)ugp::GBEST_SLICES * n_tiles512 * 256));
-                b.luniq = W.d_luniq.p; uq.luniq = W.d_luniq.p; uq.gcnt = W.d_gcnt.p; uq.gcnt_part = W.d_gcnt_part.p;
-            }
-            W.last_list_n = d_list_n; W.last_list_tiles = n_tiles512; W.last_nitems = coarse_only ? nullptr : d_nitems;
-            b.queue = d_queue;
-            b.ub = K.no_prune ? nullptr : W.d_ub.p;
-            const uint32_t *hstart = nullptr, *hlen = nullptr;
-            if (sorted && !K.no_lpt) {   // hand out every tile's own region first (scheduling only)
-                HIP_TRY(W.d_gstart.reserve(n_tiles512)); HIP_TRY(W.d_hlen.reserve(n_tiles512));
-                HIP_TRY(ugp::launch_tile_ranges(W.d_keys2.p, (uint32_t)nq, n_tiles512, m->d_chunk_node.p, f.n_chunks,
-                                                std::max<uint32_t>(1, (f.n_chunks + G - 1) / G), W.d_gstart.p, W.d_hlen.p, s));
-                hstart = W.d_gstart.p; hlen = W.d_hlen.p;
-            }
-            const uint32_t unit_chunks = std::max<uint32_t>(1, (f.n_chunks + G - 1) / G);
-            b.ub_every = 128;
-            if (K.ub_every) b.ub_every = K.ub_every;
-            b.freeze_ub = ex_skip ? 1u : 0u;   // (the chunk minima include the samples' excluded nodes: no bound may be taken from them)
-            b.refill_all_rows = K.refill_all ? 1u : 0u;
-            b.heavy_prio = K.heavy_prio;
-            // (trees with large polytomies keep the tile-after-tile order: measured, 7 % apart in either direction)
-            const uint32_t light_order = K.light_order >= 0 ? (uint32_t)K.light_order : (m->wide_descent ? 1u : 0u);
-            uint32_t heavy_chunks = 16;
-            if (K.heavy_chunks) heavy_chunks = K.heavy_chunks;
-            // Units outside the tiles' own regions grow with the distance from the region (they end in their preamble or after a
-            // few jumps: what they cost is the replay, not their length) -- only when there is a region to measure from and bounds
-            // to prune with.
-            uint32_t grow_every = (hstart && b.ub) ? 8u : 0u, unit_max = unit_chunks * 16u;
-            if (K.unit_grow >= 0) grow_every = (hstart && b.ub) ? (uint32_t)K.unit_grow : 0u;
-            if (K.unit_max) unit_max = K.unit_max;
-            // A preamble record says where the body goes on behind a path node's subtree in INFO_JUMP_MASK's 18 bits, the largest
-            // value meaning "beyond the unit": no unit may be longer than that many words.  (Should even the basic units be --
-            // chunks of thousands of words: nodes with thousands of mutations -- the replay runs without those records.)
-            {
-                const uint64_t reach = ugp::INFO_JUMP_MASK - 1u, cw = std::max<uint32_t>(1, f.max_chunk8_words);
-                unit_max = (uint32_t)std::max<uint64_t>(unit_chunks, std::min<uint64_t>(unit_max, reach / cw));
-                b.no_pre_records = ((uint64_t)std::max(unit_chunks, heavy_chunks) * cw > reach) ? 1u : 0u;
-            }
-            {
-                auto len_of = [&](uint32_t i) -> uint64_t {
-                    if (!grow_every) return unit_chunks;
-                    return std::min<uint64_t>((uint64_t)unit_chunks << std::min<uint32_t>(i / grow_every, 16u), std::max(unit_max, unit_chunks));
-                };
-                uint32_t n_side = 0;
-                for (uint64_t done = 0; done < f.n_chunks; n_side++) done += len_of(n_side);
-                const uint32_t per_tile_cap = (f.n_chunks + heavy_chunks - 1) / heavy_chunks + 2u * n_side + 2u;
-                HIP_TRY(W.d_units.reserve((size_t)n_tiles512 * per_tile_cap * 4));
-                HIP_TRY(W.d_unit_info.reserve(32 + 96));
-                // units that run long are cut while they run: the shared list of split-off halves (k_best8)
-                uint32_t split_cycles = 400000, split_heavy = 400000;
-                if (K.split_cycles >= 0) split_cycles = (uint32_t)K.split_cycles;
-                if (K.split_heavy >= 0) split_heavy = (uint32_t)K.split_heavy;
-                if (!split_heavy) split_heavy = 0xFFFFFFFFu;
-                if (!split_cycles || f.n_chunks >= (1u << 20) || n_tiles512 > 4096) split_cycles = split_heavy = 0xFFFFFFFFu;   // (never; the entry's fields)
-                constexpr uint32_t kDynCap = 1u << 17;
-                if (!W.d_dyn.p) {
-                    HIP_TRY(W.d_dyn.reserve(kDynCap));
-                    W.dyn_epoch = 2047;
-                }
-                if (++W.dyn_epoch >= 2048u) { HIP_TRY(hipMemsetAsync(W.d_dyn.p, 0, (size_t)kDynCap * 8, s)); W.dyn_epoch = 1; }   // (11 bits: stale entries never alias)
-                uint32_t *dyn_ctl = W.d_unit_info.p + 32;
-                b.dyn_ctl = dyn_ctl; b.dyn_units = (unsigned long long *)W.d_dyn.p; b.dyn_cap = kDynCap; b.dyn_epoch = W.dyn_epoch; b.split_cycles = split_cycles; b.split_heavy = split_heavy; b.split_dense = K.split_dense >= 0 ? (uint32_t)K.split_dense : 0xFFFFFFFFu; b.split_many = K.split_many ? ((K.split_many & 0xFFFFu) | (std::max(1u, K.split_many_heavy ? K.split_many_heavy : K.split_many) << 16)) : 0u;
-                HIP_TRY(ugp::launch_build_units(hstart, hlen, n_tiles512, f.n_chunks, unit_chunks, heavy_chunks, grow_every, unit_max, light_order, per_tile_cap,
-                                                W.d_units.p, W.d_unit_info.p, W.d_unit_info.p + 8, dyn_ctl, s));
-                b.units = (const uint4 *)W.d_units.p; b.unit_base = W.d_unit_info.p; b.unit_count = W.d_unit_info.p + 8;
-            }
-            HIP_TRY(W.d_stats.reserve(96));
-            if (q0 == 0) { if (K.stats) HIP_TRY(hipMemsetAsync(W.d_stats.p, 0, 96 * sizeof(uint64_t), s)); W.last_words_total = 0; }   // (the counters exist only in the statistics build: no launch for them otherwise)
-            b.stats = K.stats ? W.d_stats.p : nullptr;   // the counters are two contended atomics per skip: debug only
-            if (b.stats && !K.trace.empty() && !coarse_only) {   // per-unit records of this launch, dumped by ugp_get_timing
-                constexpr size_t kTraceCap = 1u << 20;
-                HIP_TRY(W.d_trace.reserve(8 + kTraceCap * 6));
-                HIP_TRY(hipMemsetAsync(W.d_trace.p, 0, 64, s));
-                b.trace = W.d_trace.p; b.trace_cap = kTraceCap;
-            }
-            W.last_words_total += (uint64_t)n_tiles512 * m->stream8_dwords;
-            b.max_slots = f.max_slots;
-            // LDS holds the hot slots only (the kernel's registers allow 6 waves per SIMD, 13 KB of LDS per wave
-            // would stop at 3); the colder ones, touched once per ~1,300 words, go to a small global scratch
-            b.lds_slots = f.lds_slots;   // fixed when the tree was flattened (headers touching colder slots are flagged there)
-            // persistent grid: as many one-wave blocks as the device keeps resident (cached per handle and LDS
-            // size), never more than there are units; the cold-slot scratch is sized for exactly that grid
-            // The variant with the tile's active-row bitmap in LDS (up to 4 KB of it, i.e. 32,768 sites): a restart of the walk is two
-            // memory round trips instead of three, for 3 KB more LDS per wave (13 resident waves per CU instead of 17).  Measured:
-            // k_best8 4.52 -> 4.09 ms at 65,536 samples, where the launch is long enough to be bound by its throughput; 1.87 -> 1.97 ms
-            // at 16,384, where the tail of the launch and the number of resident waves matter more.  Hence: from 64 tiles on.
-            // (not when two calls share the device: the grids are halved then, and the LDS is better spent on resident waves --
-            // 65,536 samples per call, pipelined: 10.5 M/s with, 11.0 M/s without)
-            b.lds_bits = lds_bits_plan;   // (decided in front of the tile build, with the third bound)
-            // Batches with thousands of N cells per sample (their tiles come from the N masks: nmi >= 0): every site row of every tile is
-            // live, the bitmap says "fetch the row" for every word -- the variant without a bitmap saves each restart a dependent round
-            // trip and each group a load (round 5; exact for any batch: a site's own row is always right, the constant row is the shortcut)
-            // (nmi >= 0: lds_bits_plan == 2)
-            const size_t lds_bytes = (size_t)b.lds_slots * 64 * 16 + (b.lds_bits == 1 ? (((size_t)active_words * 4 + 15) & ~(size_t)15) : 0);
-            b.b3 = (b3_on && b.ub && b.lds_bits != 1) ? W.d_b3_dev.p : nullptr;
-            if (b.b3) TG.last.bound3 = 1;
-            const int variant = coarse_only ? (b.lds_bits == 2 ? 4 : 2) : (b.b3 ? (b.lds_bits == 2 ? 6 : 5) : (b.lds_bits == 2 ? 3 : (b.lds_bits ? 1 : 0)));   // (the kernel launch_best8 will pick)
-            if (m->occ_lds != lds_bytes || m->occ_variant != variant) {
-                HIP_TRY(hipDeviceGetAttribute(&m->n_cu, hipDeviceAttributeMultiprocessorCount, m->device));
-                HIP_TRY(ugp::best8_occupancy(lds_bytes, variant, &m->occ_per_cu));
-                m->occ_lds = lds_bytes; m->occ_variant = variant;
-            }
-            int waves_cu = std::max(m->occ_per_cu, 1);
-            // Two calls on the device (ugp_place_device, the other set's call still running when this one is queued): each walk
-            // takes half of what the device keeps resident, so that both grids ARE resident instead of one waiting for the other's
-            // waves to exit -- measured at 16,384 samples per call: 2.71 -> 2.29 ms per call (6.05 -> 7.2 M placements/s), best at
-            // 8 of the 17 waves per CU of that time (7: 2.32, 9: 2.39, 12: 2.51); with 16 resident since the B halves moved into registers, 8 again (6: 1.85, 8: 1.75, 10: 1.86 ms).  A call that finds the device to itself keeps the full grid.
-            // (end of round 6, measured again with the smaller helpers, interleaved A/Bs in profiles/r06_ab_shared*.txt: a caller that keeps
-            // THREE short calls in flight does best with 5 of the 16 slots per walk whatever the number of walks found running at the
-            // moment -- 14.1-14.5 M/s against 13.6 with the share recomputed per call (5 or 8), 13.9 with 6, 13.8 with 4 or 7; the
-            // SARS-CoV-2 shape 12.6 against 12.3.  Callers of long calls -- two sets: 65 536 samples, hundreds of rows per sample -- keep
-            // half of the slots: 6.8 M/s against 5.8 with 5 on config 5.)
-            if (m->sharing) waves_cu = std::max(1, K.shared_waves ? (int)K.shared_waves : (m->share_sets >= 3 ? waves_cu * 5 / 16 : waves_cu / 2));
-            // (round 6) A lone call of a short, plain batch fills three quarters of the slots: with every slot taken more waves wait for
-            // work at the end of the launch, every waiting wave makes a running one cut its unit, and every piece replays a preamble --
-            // measured alone (profiles/r06_sweep_lone_waves.txt), 16 -> 12 waves per CU: 0.98 -> 0.89 ms at 16 384 x 10 M, 0.92 -> 0.77 at
-            // 4 096, 0.76 -> 0.67 at 1 M nodes; batches of hundreds of rows per sample, 65 536 samples and the polytomy shape gain nothing or lose.
-            else if (!coarse_only && sorted && b3_class == 0 && n_tiles512 <= 32 && !m->wide_descent && waves_cu >= 16) waves_cu = waves_cu * 3 / 4;
-            if (K.waves_per_cu) waves_cu = std::max(1, std::min(std::max(m->occ_per_cu, 1), (int)K.waves_per_cu));   // tuning
-            uint64_t blocks = (uint64_t)waves_cu * std::max(m->n_cu, 1);
-            blocks = std::min<uint64_t>(blocks, (uint64_t)n_tiles512 * G);
-            blocks = ((blocks + 7) / 8) * 8;
-            HIP_TRY(W.d_cold.reserve((size_t)blocks * std::max<uint32_t>(f.max_slots - b.lds_slots, 1) * 512));   // 32 B per lane and cold slot
-            b.cold = W.d_cold.p;
-            b.active = d_active; b.active_words = active_words;
-            // (UGP_KBEST_EXCLUSIVE: of the two calls that may be on the device at a time, ugp_place_device, only one runs this
-            // kernel at any moment -- measured: 2.77 against 2.71 ms per step when the two persistent grids simply share the
-            // chip; the small kernels in front of the second walk are slowed by the first and become the critical path)
-            const bool exclusive = K.kbest_exclusive;
-            if (exclusive && !coarse_only && m->kb_done && m->kb_done_on != s) HIP_TRY(hipStreamWaitEvent(s, m->kb_done, 0));
-            if (W.join_pending) { HIP_TRY(hipStreamWaitEvent(s, W.ev_join, 0)); W.join_pending = false; }
-            HIP_TRY(ugp::launch_best8(b, (uint32_t)blocks, s));
-            if (exclusive && !coarse_only) {
-                if (!m->kb_done) HIP_TRY(hipEventCreateWithFlags(&m->kb_done, hipEventDisableTiming));
-                HIP_TRY(hipEventRecord(m->kb_done, s));
-                m->kb_done_on = s;
-            }
-            HIP_TRY(hipEventRecord(es.ev[2], s));
-            if (ex_skip && !coarse_only)   // the one chunk minimum per sample that its excluded node may have set, again without it
-                HIP_TRY(ugp::launch_fix_skip(a, W.d_lbest.p, ex->skip_chunk + q0, n_tiles512, m->d_rank2bfs.p, order, f.max_slots, s));
-            if (coarse_only)
-                HIP_TRY(ugp::launch_coarse_result(W.d_lbest.p, W.d_lpos.p, W.d_list.p, d_list_n, f.n_chunks, n_tiles512, (uint32_t)nq, m->d_chunk_node.p,
-                                                  m->d_chunk8_body.p, m->d_node_pos8.p, m->d_dfs2bfs.p, d_out + q0, s));
-#ifdef UGP_EXPERIMENTS
-            else if (!d_tie_count && m->d_node_pos8.p && m->d_rank_dfs.p && b.ub && !b.stats && K.phase2_packed) {
-                // (experiment, UGP_PHASE2_PACKED=1) phase 2 as a mode of the packed walk: one unit per (tile, chunk) record that holds some
-                // sample's global minimum.  Exact, but 6x slower than k_ties as it stands (1.8 against 0.3 ms per 16,384 samples): its
-                // units re-walk half of their chunks; DESIGN.md 7.2
-                HIP_TRY(W.d_tie_units.reserve((size_t)((n_tiles512 + 7) / 8) * 8 * f.n_chunks * 4));
-                HIP_TRY(W.d_tie_info.reserve(128));
-                HIP_TRY(ugp::launch_phase2_packed(b, W.d_list.p, d_list_n, W.d_gbest_part.p, W.d_gbest.p, n_tiles512, W.d_tie_units.p, W.d_tie_info.p, d_cnt, d_key,
-                                                  m->d_node_pos8.p, m->d_rank_dfs.p, m->d_chunk_node.p, m->d_rank2bfs.p, (uint32_t)nq, d_out + q0, order,
-                                                  (uint32_t)blocks, s));
-            }
-#endif
-            else
-                HIP_TRY(ugp::launch_phase2(a, W.d_lbest.p, W.d_list.p, d_list_n, W.d_gbest_part.p, W.d_gbest.p, n_tiles512, W.d_items.p, d_nitems,
-                                           (uint32_t)std::min<uint64_t>(pairs, 0xFFFFFFFFull), d_cnt, d_key,
-                                           m->d_rank2bfs.p, ex ? ex->rank2out : nullptr, d_out + q0, order, f.max_slots, d_tie_count != nullptr,
-                                           uq.luniq ? &uq : nullptr, s));
-                if (d_tie_count) m->tie_lists_filled++;
-        } else if (mode == 1 && !ex && !m->h_level_off.empty() && !K.scores_dfs) {
-            // -p in the output's own order: level by level of the breadth-first expansion, 64 consecutive scores of one sample per
-            // wave store (k_scores_level); the depth-first walk below writes 4 bytes per 32-byte sector
-            const uint32_t qpad = (uint32_t)((nq + 7) / 8 * 8);
-            const bool d16 = qs->max_rows + f.max_path_muts + 2 < 0xFFFFull;
-            const size_t d_words = ((size_t)m->max_level_width * ((qpad + ugp::SCORES_SB - 1) / ugp::SCORES_SB * ugp::SCORES_SB) * (d16 ? 2 : 4) + 3) / 4;
-            HIP_TRY(W.d_part_best.reserve(d_words)); HIP_TRY(W.d_part_cnt.reserve(d_words));   // (the two D arrays; this mode has no partial results)
-            HIP_TRY(ugp::launch_scores_levels(m->d_node_pair.p, m->d_parent.p, m->d_stream.p, W.d_table.p, n_sites, d_dbottom, m->h_level_off.data(),
-                                              (uint32_t)m->h_level_off.size() - 1, W.d_part_best.p, W.d_part_cnt.p, d16, m->max_level_width, qpad, (uint32_t)nq, f.n_nodes,
-                                              a.scores, K.scores_block, s));
-            HIP_TRY(hipEventRecord(es.ev[2], s));
-        } else {
-            HIP_TRY(ugp::launch_place(a, ex ? mode + 4 : mode, f.max_slots, s));
-            HIP_TRY(hipEventRecord(es.ev[2], s));
-            if (mode == 0)
-                HIP_TRY(ugp::launch_merge(W.d_part_best.p, W.d_part_cnt.p, W.d_part_key.p, (ex && ex->rank2out) ? ex->rank2out : m->d_rank2bfs.p, G,
-                                          (uint32_t)nq, d_out + q0, s));
-        }
-        if ((K.seed_prev || K.seed_check) && use8 && !coarse_only && mode == 0) {
-            HIP_TRY(W.d_prev_res.reserve(Q));
-            HIP_TRY(hipMemcpyAsync(W.d_prev_res.p + q0, d_out + q0, nq * sizeof(ugp_result), hipMemcpyDeviceToDevice, s));
-            W.prev_serial = (q0 + nq >= Q) ? qs->serial : 0;   // valid once every sub-batch of THIS query set has been stored
-        }
-        HIP_TRY(hipEventRecord(es.ev[3], s));
-        if (b3_tuned) es.b3_class = b3_class;   // (from here on the tuner may read this sub-batch's events)
-        W.last_used_best8 = use8;
-        TG.last.packed_path = use8 ? 1u : 0u;
-        es.used = true;
-        TG.last.place_launches++;
-        TG.last.n_tiles += use8 ? n_tiles512 : n_tiles;
-        TG.last.n_groups = G;
+    if (c.W.done && c.W.done_on != s) HIP_TRY(hipStreamWaitEvent(s, c.W.done, 0));
+    Finish finish{c.W, s};
+    if (int rc = open_timing(c)) return rc;
+    if (qs->n_queries == 0) return UGP_OK;
+    c.tree = plan_tree(m);
+    c.call = plan_call_facts(m, qs, r);
+    c.cp = ugp::plan_call(c.tree, m->knobs, c.call);
+    c.ex_skip = c.cp.ex_skip ? r.ex->skip : nullptr;
+    c.TG->coarse_timed = false;
+    if (int rc = side_fill(c)) return rc;
+    if (c.cp.sorted) if (int rc = coarse_pass(c)) return rc;
+    for (uint64_t q0 = 0; q0 < c.call.Q; q0 += c.cp.sub_tiles * 64) {
+        SubBatch sb;
+        if (int rc = sub_begin(c, sb, q0)) return rc;
+        if (c.cp.sorted) if (int rc = locality_sort(c, sb)) return rc;
+        if (int rc = build_tiles(c, sb)) return rc;
+        if (sb.p.b3_want) if (int rc = b3_tables(c, sb)) return rc;
+        if (c.cp.packed_ok) if (int rc = seed_bounds(c, sb)) return rc;
+        HIP_TRY(hipEventRecord(sb.es->ev[1], s));
+        place_args(c, sb);
+        if (c.cp.packed_ok) {
+            if (int rc = packed_walk(c, sb)) return rc;
+            if (int rc = packed_result(c, sb)) return rc;
+        } else if (r.mode == 1 && !r.ex && !m->h_level_off.empty() && !m->knobs.scores_dfs) {
+            if (int rc = level_scores(c, sb)) return rc;
+        } else if (int rc = lane_walk(c, sb)) return rc;
+        if (int rc = sub_end(c, sb)) return rc;
     }
     return UGP_OK;
 }
@@ -1437,7 +1496,9 @@ uint64_t ugp_qset_size(const ugp_qset *qs) { return qs ? qs->n_queries : 0; }
 int ugp_place_device(ugp_mat *m, ugp_qset *qs, void *d_out, void *stream) {
     if (!m || !qs || (!d_out && qs->n_queries)) return fail(UGP_ERR_INVALID, "null argument");
     if (qs->device != m->device) return fail(UGP_ERR_INVALID, "query set lives on another device");
-    return run_place(m, qs, 0, (ugp_result *)d_out, nullptr, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
+    PlaceReq r;
+    r.out = (ugp_result *)d_out; r.stream = (hipStream_t)stream;
+    return run_place(m, qs, r);
 }
 
 // Is the other workspace set's call still on the device?  (Then this call's tree walks leave it half of the chip.)  Or was it
@@ -1468,21 +1529,24 @@ static void note_sharing(ugp_mat *m, int wi, int depth) {
 // Ordering (include/usher_amd.h): `stream` receives every call's completion, in call order; a call is ordered behind the
 // work that was queued on `stream` before the PREVIOUS overlapped call on this handle (one call of lag: work queued since
 // then sits behind that call's completion and would serialise the two) -- and behind all of it when the handle is idle.
-int ugp_pipeline_depth(const ugp_mat *m) { return m ? std::max(2, std::min(kMaxSets, (int)m->knobs.depth)) : 0; }
+int ugp_pipeline_depth(const ugp_mat *m) { return m ? ugp::pipeline_depth(m->knobs) : 0; }
+
+// The handle's own stream for a workspace set, made on first use.
+static int own_stream(ugp_mat *m, ugp_mat::Work &W) {
+    if (!W.stream) { ugp::fitch_drop_streams(m->device); HIP_TRY(hipStreamCreateWithFlags(&W.stream, hipStreamNonBlocking)); }   // (the Fitch-Sankoff pool's idle upload stream would shift this one's hardware queue)
+    return UGP_OK;
+}
 
 int ugp_place_device_overlapped(ugp_mat *m, ugp_qset *qs, void *d_out, void *stream) {
     if (!m || !qs || (!d_out && qs->n_queries)) return fail(UGP_ERR_INVALID, "null argument");
     if (qs->device != m->device) return fail(UGP_ERR_INVALID, "query set lives on another device");
     HIP_TRY(hipSetDevice(m->device));
-    const int depth = std::max(2, std::min(kMaxSets, (int)m->knobs.depth));
-    // Long calls gain nothing from a third batch on the device (measured: 65,536 samples per call 17.4 M/s with two, 16.9 with three;
-    // thousands of N rows per sample 3.1 against 2.9), short ones do (16,384: 10.2 -> 11.3; 1,024 on a 100k-node tree 5.7 -> 6.8):
-    // they cycle through two of the handle's sets.  The ordering promise is the handle's (depth - 1 calls of lag) either way.
-    const int use = (qs->n_queries > 32768 || qs->n_ent > qs->n_queries * 128) ? 2 : depth;
+    const int depth = ugp::pipeline_depth(m->knobs);
+    const int use = ugp::sets_in_use(m->knobs, qs->n_queries, qs->n_ent);   // (long calls: two of the handle's sets)
     const int wi = m->next_work % use;
     m->next_work = (wi + 1) % use;
     ugp_mat::Work &W = m->work[wi];
-    if (!W.stream) { ugp::fitch_drop_streams(m->device); HIP_TRY(hipStreamCreateWithFlags(&W.stream, hipStreamNonBlocking)); }   // (the Fitch-Sankoff pool's idle upload stream would shift this one's hardware queue)
+    if (int rc = own_stream(m, W)) return rc;
     note_sharing(m, wi, use);
     struct Unshare { ugp_mat *m; ~Unshare() { m->sharing = false; m->share_n = 1; } } unshare{m};
     // What was on the caller's stream when this call was made (a ring of events by call number) is waited for by the call
@@ -1497,7 +1561,9 @@ int ugp_place_device_overlapped(ugp_mat *m, ugp_qset *qs, void *d_out, void *str
     // (one more call of lag -- and one more output buffer for the caller to cycle through -- was measured: 12.3 -> 12.5 M/s, the
     // cross-queue signalling it hides is 2 % of a chain; not worth a wider contract)
     else if (kc + 1 >= (uint64_t)depth) HIP_TRY(hipStreamWaitEvent(W.stream, m->entry_ring[(kc - (uint64_t)(depth - 1)) % kMaxSets], 0));
-    if (int rc = run_place(m, qs, 0, (ugp_result *)d_out, nullptr, nullptr, nullptr, nullptr, nullptr, 0, W.stream, false, nullptr, wi)) return rc;
+    PlaceReq r;
+    r.out = (ugp_result *)d_out; r.stream = W.stream; r.wi = wi;
+    if (int rc = run_place(m, qs, r)) return rc;
     if (W.done) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, W.done, 0));   // (recorded at the end of run_place)
     return UGP_OK;
 }
@@ -1515,9 +1581,8 @@ int ugp_place_batch_async(ugp_mat *m, const ugp_queries *q, ugp_result *out, ugp
     *job = nullptr;
     HIP_TRY(hipSetDevice(m->device));
     // as many jobs in flight as the handle keeps overlapped calls on the device (ugp_pipeline_depth; long batches: two, as there)
-    const int depth = std::max(2, std::min(kMaxSets, (int)m->knobs.depth));
     const uint64_t n_rows = q->n_queries ? q->ent_off[q->n_queries] - q->ent_off[0] : 0;
-    const int use = (q->n_queries > 32768 || n_rows > q->n_queries * 128) ? 2 : depth;
+    const int use = ugp::sets_in_use(m->knobs, q->n_queries, n_rows);
     // the next free set from the cursor on (jobs of different lengths cycle through different numbers of sets: a long job resets
     // the cursor of the short ones, and the set behind it may still hold a job although fewer than `use` are outstanding)
     int wi = -1;
@@ -1525,7 +1590,7 @@ int ugp_place_batch_async(ugp_mat *m, const ugp_queries *q, ugp_result *out, ugp
     if (wi < 0) return fail(UGP_ERR_INVALID, "as many jobs as the handle keeps in flight (ugp_pipeline_depth; two for long batches) are outstanding: ugp_job_wait the oldest first");
     ugp_mat::Work &W = m->work[wi];
     if (W.job_busy) return fail(UGP_ERR_INVALID, "as many jobs as the handle keeps in flight (ugp_pipeline_depth) are outstanding: ugp_job_wait the oldest first");
-    if (!W.stream) { ugp::fitch_drop_streams(m->device); HIP_TRY(hipStreamCreateWithFlags(&W.stream, hipStreamNonBlocking)); }   // (the Fitch-Sankoff pool's idle upload stream would shift this one's hardware queue)
+    if (int rc = own_stream(m, W)) return rc;
     if (!W.job_qs) { W.job_qs = new (std::nothrow) ugp_qset(); if (!W.job_qs) return fail(UGP_ERR_NOMEM, "out of host memory"); }
     // the previous use of this set (a job two calls ago, or any other entry point) has to be over before its staging is overwritten
     if (W.done) HIP_TRY(hipEventSynchronize(W.done));
@@ -1533,7 +1598,9 @@ int ugp_place_batch_async(ugp_mat *m, const ugp_queries *q, ugp_result *out, ugp
     HIP_TRY(W.d_job_out.reserve(q->n_queries));
     if (int rc = W.job_out.reserve(std::max<size_t>(q->n_queries, 1) * sizeof(ugp_result) + 8, true)) return rc;
     note_sharing(m, wi, use);   // (is the other set's job still on the device?)
-    int rc = run_place(m, W.job_qs, 0, W.d_job_out.p, nullptr, nullptr, nullptr, nullptr, nullptr, 0, W.stream, false, nullptr, wi);
+    PlaceReq r;
+    r.out = W.d_job_out.p; r.stream = W.stream; r.wi = wi;
+    int rc = run_place(m, W.job_qs, r);
     m->sharing = false; m->share_n = 1;
     if (rc != UGP_OK) return rc;
     // results and the row check's verdict into pinned memory, behind the kernels; W.done is recorded again behind them.
@@ -1582,7 +1649,9 @@ int ugp_place_batch(ugp_mat *m, const ugp_queries *q, ugp_result *out) {
     ugp_qset *qs = m->own_qs;
     if (int rc = qset_fill(m, q, qs)) return rc;
     HIP_TRY(m->d_own_out.reserve(q->n_queries));
-    if (int rc = run_place(m, qs, 0, m->d_own_out.p, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr)) return rc;
+    PlaceReq r;
+    r.out = m->d_own_out.p;
+    if (int rc = run_place(m, qs, r)) return rc;
     if (q->n_queries) HIP_TRY(hipMemcpy(out, m->d_own_out.p, q->n_queries * sizeof(ugp_result), hipMemcpyDeviceToHost));
     return UGP_OK;
 }
@@ -1596,7 +1665,9 @@ int ugp_scores_per_node(ugp_mat *m, const ugp_queries *q, int32_t *out) {
     int rc = UGP_OK;
     hipError_t e = d_scores.reserve(total);
     if (e != hipSuccess) rc = fail(UGP_ERR_HIP, std::string("hipMalloc scores: ") + hipGetErrorString(e));
-    if (rc == UGP_OK) rc = run_place(m, qs, 1, nullptr, d_scores.p, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+    PlaceReq r;
+    r.mode = 1; r.scores = d_scores.p;
+    if (rc == UGP_OK) rc = run_place(m, qs, r);
     if (rc == UGP_OK && total) {
         rc = copy_d2h_staged(out, d_scores.p, total * sizeof(int32_t));
     }
@@ -1617,7 +1688,6 @@ int ugp_tied_nodes(ugp_mat *m, const ugp_queries *q, uint32_t cap, uint32_t *tie
     DevBuf<uint8_t> d_hu;
     int rc = UGP_OK;
     const uint64_t padded = ((Q + 63) / 64) * 64;
-    hipError_t e = hipSuccess;
     auto chk = [&](hipError_t x, const char *what) {
         if (rc == UGP_OK && x != hipSuccess) rc = fail(UGP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(x));
     };
@@ -1631,12 +1701,16 @@ int ugp_tied_nodes(ugp_mat *m, const ugp_queries *q, uint32_t cap, uint32_t *tie
     // first, then the one-sample-per-lane walk of the whole tree that appends every node attaining them.
     if (rc == UGP_OK) chk(hipMemsetAsync(d_cnt.p, 0, padded * sizeof(uint32_t), nullptr), "memset");
     m->tie_lists_filled = m->tie_sub_batches = 0;
-    if (rc == UGP_OK) rc = run_place(m, qs, 0, d_res.p, nullptr, nullptr, m->knobs.ties_dfs ? nullptr : d_cnt.p, d_j.p, d_hu.p, cap, nullptr);
+    PlaceReq r;   // results, and the tie lists where phase 2 writes them
+    r.out = d_res.p; r.tie_count = m->knobs.ties_dfs ? nullptr : d_cnt.p; r.tie_j = d_j.p; r.tie_hu = d_hu.p; r.tie_cap = cap;
+    if (rc == UGP_OK) rc = run_place(m, qs, r);
     const bool filled = rc == UGP_OK && m->tie_sub_batches > 0 && m->tie_lists_filled == m->tie_sub_batches;
     if (rc == UGP_OK && !filled) {   // the wanted scores stay on the device
         chk(ugp::launch_extract_best(d_res.p, (uint32_t)Q, d_best.p, nullptr), "extract best");
         chk(hipMemsetAsync(d_cnt.p, 0, padded * sizeof(uint32_t), nullptr), "memset");
-        if (rc == UGP_OK) rc = run_place(m, qs, 2, nullptr, nullptr, d_best.p, d_cnt.p, d_j.p, d_hu.p, cap, nullptr);
+        PlaceReq t;
+        t.mode = 2; t.best_in = d_best.p; t.tie_count = d_cnt.p; t.tie_j = d_j.p; t.tie_hu = d_hu.p; t.tie_cap = cap;
+        if (rc == UGP_OK) rc = run_place(m, qs, t);
     }
     if (rc == UGP_OK) {
         chk(hipMemcpy(tie_count, d_cnt.p, Q * sizeof(uint32_t), hipMemcpyDeviceToHost), "copy tie counts");
@@ -1656,7 +1730,6 @@ int ugp_tied_nodes(ugp_mat *m, const ugp_queries *q, uint32_t cap, uint32_t *tie
             for (uint32_t t = 0; t < k; t++) { tie_j[i * cap + t] = tmp[t].first; tie_has_unique[i * cap + t] = tmp[t].second; }
         }
     }
-    (void)e;
     ugp_qset_destroy(qs);
     return rc;
 }
@@ -2022,15 +2095,22 @@ int ugp_place_batch_ex(ugp_mat *m, const ugp_queries *q, const ugp_place_opts *o
         if (rc == UGP_OK && xd.mask) rc = mask_words(m, xd.mask, true);
         const uint8_t *masked = xd.mask;
         xd.mask = nullptr; xd.packed = true; xd.scores = nullptr;
-        if (rc == UGP_OK) rc = run_place(m, qs, 0, d_out.p, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, false, &xd);
+        PlaceReq r;
+        r.out = d_out.p; r.ex = &xd;
+        if (rc == UGP_OK) rc = run_place(m, qs, r);
         if (masked) { const int rc2 = mask_words(m, masked, false); if (rc == UGP_OK) rc = rc2; }
         if (rc == UGP_OK && scores_by_levels) {
-            rc = run_place(m, qs, 1, nullptr, x.d_scores.p, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+            PlaceReq sr;
+            sr.mode = 1; sr.scores = x.d_scores.p;
+            rc = run_place(m, qs, sr);
             if (rc == UGP_OK && ugp::launch_scores_mask(x.d_scores.p, q->n_queries, m->flat.n_nodes, x.dev.mask, x.dev.skip, nullptr) != hipSuccess)
                 rc = fail(UGP_ERR_HIP, "masking the scores");
         }
-    } else
-    if (rc == UGP_OK) rc = run_place(m, qs, 0, d_out.p, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, false, &x.dev);
+    } else if (rc == UGP_OK) {
+        PlaceReq r;
+        r.out = d_out.p; r.ex = &x.dev;
+        rc = run_place(m, qs, r);
+    }
     if (rc == UGP_OK && hipMemcpy(out, d_out.p, q->n_queries * sizeof(ugp_result), hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(UGP_ERR_HIP, "copy results");
     if (rc == UGP_OK && opts->scores) rc = copy_d2h_staged(opts->scores, x.d_scores.p, (size_t)q->n_queries * m->flat.n_nodes * sizeof(int32_t));
@@ -2089,15 +2169,21 @@ int ugp_place_batch_prepared(ugp_mat *m, const ugp_queries *q, const ugp_ex *e, 
         if (rc == UGP_OK && masked) rc = mask_words(m, masked, true);
         ExDev xp = xd;
         xp.mask = nullptr; xp.packed = true;
-        if (rc == UGP_OK) rc = run_place(m, qs, 0, m->d_own_out.p, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, false, &xp);
+        PlaceReq r;
+        r.out = m->d_own_out.p; r.ex = &xp;
+        if (rc == UGP_OK) rc = run_place(m, qs, r);
         if (masked) { const int rc2 = mask_words(m, masked, false); if (rc == UGP_OK) rc = rc2; }
         if (rc == UGP_OK && d_scores) {   // the score matrix straight into the caller's device buffer, level by level; what was not scored reads 0
-            rc = run_place(m, qs, 1, nullptr, d_scores, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+            PlaceReq sr;
+            sr.mode = 1; sr.scores = d_scores;
+            rc = run_place(m, qs, sr);
             if (rc == UGP_OK && ugp::launch_scores_mask(d_scores, Q, N, xd.mask, xd.skip, nullptr) != hipSuccess) rc = fail(UGP_ERR_HIP, "masking the scores");
         }
     } else {
         if (d_scores) { HIP_TRY(hipMemsetAsync(d_scores, 0, (size_t)Q * N * sizeof(int32_t), nullptr)); xd.scores = d_scores; }
-        rc = run_place(m, qs, 0, m->d_own_out.p, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, false, &xd);
+        PlaceReq r;
+        r.out = m->d_own_out.p; r.ex = &xd;
+        rc = run_place(m, qs, r);
     }
     if (rc == UGP_OK && hipMemcpy(out, m->d_own_out.p, Q * sizeof(ugp_result), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(UGP_ERR_HIP, "copy results");
     if (rc == UGP_OK)
@@ -2135,16 +2221,22 @@ int ugp_tied_nodes_ex(ugp_mat *m, const ugp_queries *q, const ugp_place_opts *op
         xd.mask = nullptr; xd.packed = true;
         if (rc == UGP_OK) chk(hipMemsetAsync(d_cnt.p, 0, padded * sizeof(uint32_t), nullptr), "memset");
         m->tie_lists_filled = m->tie_sub_batches = 0;
-        if (rc == UGP_OK) rc = run_place(m, qs, 0, d_res.p, nullptr, nullptr, d_cnt.p, d_j.p, d_hu.p, cap, nullptr, false, &xd);
+        PlaceReq r;
+        r.out = d_res.p; r.tie_count = d_cnt.p; r.tie_j = d_j.p; r.tie_hu = d_hu.p; r.tie_cap = cap; r.ex = &xd;
+        if (rc == UGP_OK) rc = run_place(m, qs, r);
         listed = rc == UGP_OK && m->tie_sub_batches > 0 && m->tie_lists_filled == m->tie_sub_batches;
         if (masked) { const int rc2 = mask_words(m, masked, false); if (rc == UGP_OK) rc = rc2; }
     }
-    if (rc == UGP_OK && !listed) rc = run_place(m, qs, 0, d_res.p, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, false, &x.dev);
+    PlaceReq r;   // the one-sample-per-lane form: the best scores first, then the lists
+    r.out = d_res.p; r.ex = &x.dev;
+    if (rc == UGP_OK && !listed) rc = run_place(m, qs, r);
     if (rc == UGP_OK && !listed) {
         chk(ugp::launch_extract_best(d_res.p, (uint32_t)Q, d_best.p, nullptr), "extract best");
         chk(hipMemsetAsync(d_cnt.p, 0, padded * sizeof(uint32_t), nullptr), "memset");
     }
-    if (rc == UGP_OK && !listed) rc = run_place(m, qs, 2, nullptr, nullptr, d_best.p, d_cnt.p, d_j.p, d_hu.p, cap, nullptr, false, &x.dev);
+    PlaceReq t;
+    t.mode = 2; t.best_in = d_best.p; t.tie_count = d_cnt.p; t.tie_j = d_j.p; t.tie_hu = d_hu.p; t.tie_cap = cap; t.ex = &x.dev;
+    if (rc == UGP_OK && !listed) rc = run_place(m, qs, t);
     if (rc == UGP_OK) {
         chk(hipMemcpy(tie_count, d_cnt.p, Q * sizeof(uint32_t), hipMemcpyDeviceToHost), "copy tie counts");
         if (cap) {

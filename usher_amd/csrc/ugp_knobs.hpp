@@ -17,7 +17,7 @@ namespace ugp {
 struct Knobs {
     // switches
     bool force_v1 = false, no_sort = false, no_prune = false, coarse_phase2 = false, no_seed = false, no_descent = false, no_pad_fix = false,
-         no_lpt = false, radix_sort = false, refill_all = false, scores_dfs = false, ties_dfs = false, debug_sharing = false, ex_slow = false, no_bound3 = false, no_uniq = false, no_fork = true;   // (no_fork: the side stream of a lone call is opt-in, UGP_FORK=1 -- see ugp_capi.cpp)
+         no_lpt = false, radix_sort = false, refill_all = false, scores_dfs = false, ties_dfs = false, debug_sharing = false, ex_slow = false, no_bound3 = false, no_uniq = false, no_fork = true;   // (no_fork: the side stream of a lone call is opt-in, UGP_FORK=1 -- see can_fork, ugp_plan.hpp)
     // -1 = the library's own choice
     int bound3 = -2,   // third pruning bound: -2 = decided from the tree and the batch (b3_static_choice), -1 = UGP_BOUND3=auto: the run-time tuner, 0 / 1 pinned
         tile_build = -1, nmask = -1, lds_bits = -1, light_order = -1, unit_grow = -1, split_cycles = -1, split_heavy = -1, split_dense = -1,
