@@ -311,7 +311,54 @@ int ugp_genotype_rows(ugp_mat *mat, uint64_t lo, uint64_t hi, uint8_t *codes /* 
 int ugp_genotype_rows_chunked(ugp_mat *mat, uint64_t lo, uint64_t hi, uint8_t *codes, uint64_t chunk_cells);
 /* Bench hook: milliseconds of device time of the row kernel alone over sites [lo, hi), without the copy to the host; mean of `reps` runs. */
 int ugp_genotype_rows_time(ugp_mat *mat, uint64_t lo, uint64_t hi, uint32_t reps, double *ms);
-/* RIPPLES (ripples/main.cpp): the options of :22-44 that the search reads.  branch_len >= 1 and parsimony_improvement >= 0
+/* matUtils summary (matUtils/summary.cpp): the mutation table (-m, :139-174), the RoHo records (-R without -E, :343-506) and the
+ * clade counts (-c :88-137, -C :297-341).  ugp_summary_attach shares the depth-first tables of `tree` exactly as
+ * ugp_genotypes_attach does (the handle's tree; arrays are copied; mut_par is needed; mut_nuc / mut_par of non-masked mutations in
+ * 1 .. 15, UGP_ERR_UNSUPPORTED otherwise; tables built from other mutation arrays: UGP_ERR_INVALID) and builds, once per handle, the
+ * OCCURRENCE LIST -- every mutation entry sorted by (key, depth-first position of its node) -- and the strict-descendant leaf
+ * count of every node.  The KEY of an entry is what Mutation::get_string() prints: (position, mut_par as stored, mut_nuc); every
+ * masked entry (mut_pos < 0) has the one key "MASKED".
+ * ugp_summary_mutations: the distinct non-masked keys with the number of entries that carry them, over all nodes, root included,
+ *   ascending by (pos, par, nuc).  out[0 .. min(cap, *n_out)) is written and *n_out is the true count.
+ * ugp_summary_roho: one record per (parent n, key) that write_roho_table reports, ascending by the depth-first position of n (records
+ *   of one parent in depth-first order of their entry; the host orders them by name).  The candidates of n are the keys on its
+ *   NON-LEAF children (masked counts as a key; a key stored twice on one child is one candidate; when two non-leaf children carry a
+ *   key the LATER one owns it and the earlier is not reported; the root's own entries are no candidates).  A candidate is erased
+ *   when its key occurs on a node of n's subtree at depth >= depth(n) + 2 -- under the owning child or under a sibling; a leaf CHILD
+ *   of n with the key does not erase it.  With lc(c) the leaves strictly below c: a record needs lc(owner) > 5 and at least one OTHER
+ *   non-leaf child with lc > 5; offspring_with = lc(owner); median_without = the middle of the sorted lc > 5 of those others, for
+ *   an even number (a + b) / 2 in integer division (:461-465); child_count = the non-leaf children of n (ccheck.size()).  `entry` is
+ *   the index in tree->mut_off's CSR of the first entry with the key on `child`.  cap / *n_out as above.
+ * The _chunked twins (test hooks) set the work-items per launch window (0: default): list entries for the mutation table, candidate
+ *   entries (those of non-leaf nodes other than the root) for RoHo.
+ * ugp_summary_clades: per annotation column c the nodes col_off[c] .. col_off[c + 1] of `nodes` (BFS; a node twice in one column is
+ *   UGP_ERR_INVALID) carry a non-empty annotation.  Per listed node: incl = the leaves strictly below it, excl = the leaves whose
+ *   nearest listed STRICT ancestor in that column it is (a listed leaf counts nothing).  leaf_clade[c * n_leaves + i] = that
+ *   ancestor (BFS) for the i-th leaf in BFS order (Tree::get_leaves), or UINT32_MAX. */
+typedef struct ugp_sm_mutation {
+    int32_t pos;
+    uint8_t par, nuc;    /* 4-bit codes                                            */
+    uint8_t pad[2];
+    uint32_t count;      /* entries with this key                                  */
+} ugp_sm_mutation;
+typedef struct ugp_sm_roho {
+    uint32_t parent, child;      /* BFS indices                                    */
+    uint32_t entry;              /* index into the caller's mutation CSR           */
+    uint32_t child_count;        /* non-leaf children of parent                    */
+    uint32_t offspring_with;     /* leaves strictly below child                    */
+    uint32_t median_without;     /* med_non before it becomes a float              */
+} ugp_sm_roho;
+int ugp_summary_attach(ugp_mat *mat, const ugp_tree_desc *tree);
+int ugp_summary_mutations(ugp_mat *mat, ugp_sm_mutation *out, uint64_t cap, uint64_t *n_out);
+int ugp_summary_mutations_chunked(ugp_mat *mat, ugp_sm_mutation *out, uint64_t cap, uint64_t *n_out, uint64_t chunk_items);
+int ugp_summary_roho(ugp_mat *mat, ugp_sm_roho *out, uint64_t cap, uint64_t *n_out);
+int ugp_summary_roho_chunked(ugp_mat *mat, ugp_sm_roho *out, uint64_t cap, uint64_t *n_out, uint64_t chunk_items);
+int ugp_summary_clades(ugp_mat *mat, const uint64_t *col_off /* [n_cols + 1] */, const uint32_t *nodes /* BFS */, uint64_t n_cols,
+                       uint32_t *incl /* [col_off[n_cols]] */, uint32_t *excl /* [col_off[n_cols]] */, uint32_t *leaf_clade /* [n_cols * n_leaves] */);
+/* Bench hook: milliseconds of device time of the occurrence-list sort alone and of the RoHo kernel alone over every candidate
+ * (no compaction, no copy to the host); mean of `reps` runs. */
+int ugp_summary_time(ugp_mat *mat, uint32_t reps, double *sort_ms, double *roho_ms);
+/* RIPPLES (ripples/main.cpp): the options of :22-44 that the search reads. branch_len >= 1 and parsimony_improvement >= 0
  * (UGP_ERR_INVALID otherwise: the reference's size_t arithmetic of :445-453 is not reproduced for negative values). */
 typedef struct ugp_ripples_opts {
     uint32_t branch_len;              /* -l: rows on each side of a breakpoint pair                         */

@@ -1,0 +1,34 @@
+"""The kernels of ugp_summary.hip do not spill, use no scratch and hold exactly the LDS they declare (the block scan's per-wave
+sums), read from the compiler's own resource report; the list of the file's own kernels is complete.  The device radix sort's
+kernels (rocprim, instantiated in this file) are the library's code: they are held to no register spills; its onesweep kernel
+keeps a private digit array of a few dozen bytes in scratch by design, which is no spill."""
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "usher_amd", "csrc")
+SCAN = 4 * 4   # block_incl_scan: one int per wave
+LDS = {"k_sm_keys": 0, "k_sm_heads": 0, "k_sm_segsum": SCAN, "k_sm_scan": SCAN, "k_sm_runs": 0, "k_sm_nodes": 0, "k_sm_bigseg": 0,
+       "k_sm_candkey": 0, "k_sm_mutations": 0, "k_sm_roho": 0, "k_sm_emit": 0, "k_sm_gather": 0, "k_sm_clade_incl": 0, "k_sm_clade_leaf": 0}
+
+
+def test_summary_kernels_do_not_spill(tmp_path):
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-structurizecfg-skip-uniform-regions=1",
+                        "-I" + os.path.join(ROOT, "include"), "-x", "hip", "-c", os.path.join(CSRC, "ugp_summary.hip"), "--cuda-device-only",
+                        "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "a.o")], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    seen = {}
+    for b in re.split(r"remark: Function Name: ", r.stderr)[1:]:
+        seen[b.split()[0]] = {k: int(v) for k, v in re.findall(r"remark:\s+([A-Za-z ]+?)(?: \[[a-z/]+\])?: (\d+)", b)}
+    own = {name: v for name, v in seen.items() if "k_sm_" in name}
+    for kernel, lds in LDS.items():
+        hits = [v for name, v in own.items() if re.search(kernel + r"(?![a-z_])", name)]
+        assert len(hits) == 1, (kernel, list(own))
+        assert hits[0]["LDS Size"] == lds, (kernel, hits[0])
+    assert len(own) == len(LDS), list(own)
+    assert len(seen) > len(own), "the radix sort's kernels are missing from the report"
+    for name, v in seen.items():
+        assert v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0, (name, v)
+        assert v["ScratchSize"] == 0 or name not in own, (name, v)

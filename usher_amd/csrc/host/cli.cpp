@@ -191,6 +191,31 @@ extern "C" int uh_write_pb_arrays(uint64_t n, const uint32_t *parent, const uint
     if (!uh::write_pb_from_arrays(n, parent, mut_off, pos, ref, par, nuc, path, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
     return 0;
 }
+// The same with node names and clade annotations (ann_off: CSR per node into `ann`; a node may carry fewer than the root), through
+// save_mat: the hand-shaped annotated MATs of the summary tests.  Mutations keep their stored order.
+extern "C" int uh_write_pb_annotated(uint64_t n, const uint32_t *parent, const uint64_t *mut_off, const int32_t *pos, const uint8_t *ref,
+                                     const uint8_t *par, const uint8_t *nuc, const char *const *names, const uint64_t *ann_off,
+                                     const char *const *ann, const char *path) {
+    if (!n || !names || !ann_off) { fprintf(stderr, "uh_write_pb_annotated: bad arguments\n"); return 1; }
+    uh::Tree T;
+    std::vector<uh::Node *> nodes(n, nullptr);
+    for (uint64_t j = 0; j < n; j++) {
+        if (j && parent[j] >= j) { fprintf(stderr, "uh_write_pb_annotated: parents must precede their children\n"); return 1; }
+        uh::Node *nd = T.create_node(names[j], j ? nodes[parent[j]] : nullptr);
+        if (!nd) { fprintf(stderr, "uh_write_pb_annotated: the name %s is taken\n", names[j]); return 1; }
+        nodes[j] = nd;
+        nd->clade_annotations.clear();
+        for (uint64_t k = ann_off[j]; k < ann_off[j + 1]; k++) nd->clade_annotations.emplace_back(ann[k]);
+        for (uint64_t k = mut_off[j]; k < mut_off[j + 1]; k++) {
+            uh::Mutation m;
+            m.position = pos[k]; m.ref_nuc = (int8_t)ref[k]; m.par_nuc = (int8_t)par[k]; m.mut_nuc = (int8_t)nuc[k];
+            nd->mutations.push_back(m);
+        }
+    }
+    std::string err;
+    if (!uh::save_mat(T, path, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
+    return 0;
+}
 extern "C" int uh_write_vcf_csr(uint64_t n_samples, const uint64_t *ent_off, const int32_t *pos, const uint8_t *ref, const uint8_t *nuc, const uint8_t *is_missing,
                                 const char *prefix, const char *path) {
     std::string err;

@@ -30,6 +30,7 @@
 #include "ugp_annotate.hpp"
 #include "ugp_nearest.hpp"
 #include "ugp_genotypes.hpp"
+#include "ugp_summary.hpp"
 #include "ugp_update.hpp"
 #include "usher_amd.h"
 
@@ -295,6 +296,7 @@ struct ugp_mat {
     ugp::AnnState *ann = nullptr;    // matUtils annotate tables (ugp_annotate_attach), or none
     ugp::NearState *near = nullptr;  // matUtils extract nearest-k tables (ugp_nearest_attach), or none
     ugp::GtState *gt = nullptr;      // matUtils extract -v tables (ugp_genotypes_attach), or none
+    ugp::SmState *sm = nullptr;      // matUtils summary tables (ugp_summary_attach), or none
     ugp::DfsTables *dfs = nullptr;   // the depth-first tables uncertainty and annotate share (their first attach), or none
     hipEvent_t kb_done = nullptr;    // behind the latest k_best8 launch of this handle ...
     hipStream_t kb_done_on = nullptr;   // ... on this stream
@@ -1368,6 +1370,7 @@ void ugp_mat_destroy(ugp_mat *m) {
     ugp::ann_free(m->ann);
     ugp::nk_free(m->near);
     ugp::gt_free(m->gt);
+    ugp::sm_free(m->sm);
     ugp::dfs_tables_free(m->dfs);
     delete m;
 }
@@ -1901,6 +1904,41 @@ int ugp_genotype_rows(ugp_mat *m, uint64_t lo, uint64_t hi, uint8_t *codes) { re
 int ugp_genotype_rows_time(ugp_mat *m, uint64_t lo, uint64_t hi, uint32_t reps, double *ms) {
     if (!m) return fail(UGP_ERR_INVALID, "null argument");
     return ugp::gt_rows_time(m->gt, lo, hi, reps, ms);
+}
+
+// ---- matUtils summary: mutation table, RoHo records, clade counts (ugp_summary.hip) -----------------------------------
+
+int ugp_summary_attach(ugp_mat *m, const ugp_tree_desc *tree) {
+    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
+    if (int rc = check_handle_tree(m, tree)) return rc;
+    return ugp::sm_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->sm);
+}
+
+int ugp_summary_mutations_chunked(ugp_mat *m, ugp_sm_mutation *out, uint64_t cap, uint64_t *n_out, uint64_t chunk_items) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sm_mutations(m->sm, out, cap, n_out, chunk_items);
+}
+
+int ugp_summary_mutations(ugp_mat *m, ugp_sm_mutation *out, uint64_t cap, uint64_t *n_out) {
+    return ugp_summary_mutations_chunked(m, out, cap, n_out, 0);
+}
+
+int ugp_summary_roho_chunked(ugp_mat *m, ugp_sm_roho *out, uint64_t cap, uint64_t *n_out, uint64_t chunk_items) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sm_roho(m->sm, out, cap, n_out, chunk_items);
+}
+
+int ugp_summary_roho(ugp_mat *m, ugp_sm_roho *out, uint64_t cap, uint64_t *n_out) { return ugp_summary_roho_chunked(m, out, cap, n_out, 0); }
+
+int ugp_summary_clades(ugp_mat *m, const uint64_t *col_off, const uint32_t *nodes, uint64_t n_cols, uint32_t *incl, uint32_t *excl,
+                       uint32_t *leaf_clade) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sm_clades(m->sm, col_off, nodes, n_cols, incl, excl, leaf_clade);
+}
+
+int ugp_summary_time(ugp_mat *m, uint32_t reps, double *sort_ms, double *roho_ms) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sm_time(m->sm, reps, sort_ms, roho_ms);
 }
 
 // ---- RIPPLES (ugp_ripples.hip) -----------------------------------------------------------------------------------------

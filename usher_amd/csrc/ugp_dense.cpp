@@ -12,6 +12,31 @@
 
 namespace ugp {
 
+int dfs_tables_same_arrays(const DfsTables &T, const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const char *who) {
+    const std::string other = std::string("the handle's depth-first tables were built from other mutation arrays (an earlier uncertainty, annotate, "
+                                          "nearest, genotypes or summary attach): ") + who + " needs the arrays of that attach, or a handle of its own";
+    const uint64_t M = tree->mut_off[tree->n_nodes];
+    if (T.m != M || T.n != tree->n_nodes) return set_error(UGP_ERR_INVALID, other);
+    if (hipSetDevice(T.device) != hipSuccess) return set_error(UGP_ERR_HIP, "hipSetDevice failed");
+    std::vector<uint32_t> morig(M), mbits(M);
+    std::vector<int32_t> mpos(M);
+    if (M) {
+        UGP_HIP_TRY(hipMemcpy(morig.data(), T.morig.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        UGP_HIP_TRY(hipMemcpy(mbits.data(), T.mbits.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        UGP_HIP_TRY(hipMemcpy(mpos.data(), T.mpos.p, M * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    uint64_t e = 0;
+    bool same = true;
+    for (uint64_t i = 0; i < T.n && same; i++) {
+        const uint32_t b = dfs2bfs[i];
+        for (uint64_t k = tree->mut_off[b]; k < tree->mut_off[b + 1] && same; k++, e++)
+            same = e < M && morig[e] == k && mpos[e] == tree->mut_pos[k] &&
+                   (mbits[e] & 0xffffu) == ((uint32_t)tree->mut_nuc[k] | (uint32_t)tree->mut_ref[k] << 8);
+    }
+    if (!same || e != M) return set_error(UGP_ERR_INVALID, other);
+    return UGP_OK;
+}
+
 void dfs_tables_free(DfsTables *t) {
     if (!t) return;
     (void)hipSetDevice(t->device);

@@ -143,6 +143,9 @@ struct DfsTables {
 int dfs_tables(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
                int entry_bits, DfsTables **tables);
 void dfs_tables_free(DfsTables *t);
+// The handle's tables may be older than the attach that reads the caller's arrays THROUGH them (morig, pent): UGP_OK when `t` was
+// built from exactly the mutation arrays of `tree` (compared entry by entry), else UGP_ERR_INVALID naming the call `who`.
+int dfs_tables_same_arrays(const DfsTables &t, const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const char *who);
 
 // ---- the literal score: loop 1 run literally, loops 2 and 3 in closed form, the eligibility ------------------------
 

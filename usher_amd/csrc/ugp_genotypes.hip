@@ -256,31 +256,8 @@ int gt_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, c
             return set_error(UGP_ERR_UNSUPPORTED, "mut_nuc / mut_par of a non-masked mutation outside 1 .. 15");
     }
     try {
-        // The handle's tables may be older than this call (dfs_tables keeps what an earlier attach built), and this attach is
-        // the first to read the caller's arrays THROUGH them (morig, pent): they must be the tables of exactly these arrays.
         const DfsTables &T = **tables;
-        const char *other = "the handle's depth-first tables were built from other mutation arrays (an earlier uncertainty, annotate, "
-                            "nearest or genotypes attach): ugp_genotypes_attach needs the arrays of that attach, or a handle of its own";
-        if (T.m != M || T.n != tree->n_nodes) return set_error(UGP_ERR_INVALID, other);
-        if (hipSetDevice(device) != hipSuccess) return set_error(UGP_ERR_HIP, "hipSetDevice failed");
-        {
-            std::vector<uint32_t> morig(M), mbits(M);
-            std::vector<int32_t> mpos(M);
-            if (M) {
-                UGP_HIP_TRY(hipMemcpy(morig.data(), T.morig.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost));
-                UGP_HIP_TRY(hipMemcpy(mbits.data(), T.mbits.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost));
-                UGP_HIP_TRY(hipMemcpy(mpos.data(), T.mpos.p, M * sizeof(int32_t), hipMemcpyDeviceToHost));
-            }
-            uint64_t e = 0;
-            bool same = true;
-            for (uint64_t i = 0; i < T.n && same; i++) {
-                const uint32_t b = dfs2bfs[i];
-                for (uint64_t k = tree->mut_off[b]; k < tree->mut_off[b + 1] && same; k++, e++)
-                    same = e < M && morig[e] == k && mpos[e] == tree->mut_pos[k] &&
-                           (mbits[e] & 0xffffu) == ((uint32_t)tree->mut_nuc[k] | (uint32_t)tree->mut_ref[k] << 8);
-            }
-            if (!same || e != M) return set_error(UGP_ERR_INVALID, other);
-        }
+        if (int same = dfs_tables_same_arrays(T, tree, dfs2bfs, "ugp_genotypes_attach")) return same;
         GtState *S = new GtState();
         S->device = device;
         S->T = *tables;

@@ -419,6 +419,69 @@ class Placer:
         self._ck(self._L.ugp_genotype_rows_time(self._h, lo, hi, int(reps), C.byref(ms)))
         return float(ms.value)
 
+    # ---- matUtils summary (ugp_summary_attach / _mutations / _roho / _clades) ---------------------------------------------
+    SM_MUTATION = np.dtype([("pos", np.int32), ("par", np.uint8), ("nuc", np.uint8), ("pad", np.uint8, (2,)), ("count", np.uint32)])
+    SM_ROHO = np.dtype([("parent", np.uint32), ("child", np.uint32), ("entry", np.uint32), ("child_count", np.uint32),
+                        ("offspring_with", np.uint32), ("median_without", np.uint32)])
+    SM_CLADE = np.dtype([("column", np.uint32), ("node", np.uint32), ("inclusive", np.uint32), ("exclusive", np.uint32)])
+
+    def summary_attach(self, arrays: Optional[Dict] = None):
+        """ugp_summary_attach with the placer's own tree, or with other mutation arrays on the same topology (masked entries, a key
+        twice on one node: trees the placement tables refuse).  The depth-first tables are shared as genotypes_attach describes."""
+        t = self._t if arrays is None else _TreeArrays(arrays)
+        self._ck(self._L.ugp_summary_attach(self._h, C.byref(t.desc)))
+        self._sm_ready = True
+
+    def _sm_records(self, fn, dtype, chunk_items, cap):
+        if not getattr(self, "_sm_ready", False):
+            self.summary_attach()
+        n_out = C.c_uint64(0)
+        if cap is None:   # the two-call convention: the count, then the records
+            self._ck(fn(self._h, None, 0, C.byref(n_out), int(chunk_items)))
+            cap = int(n_out.value)
+        out = np.zeros(int(cap), dtype)
+        self._ck(fn(self._h, _ptr(out) if cap else None, int(cap), C.byref(n_out), int(chunk_items)))
+        self._sm_n_out = int(n_out.value)
+        return out[:min(int(cap), self._sm_n_out)]
+
+    def summary_mutations(self, chunk_items: int = 0, cap: Optional[int] = None):
+        """matUtils summary -m (summary.cpp:139-174): an SM_MUTATION array of the distinct non-masked (pos, stored parent allele,
+        allele) with their number of occurrences over all nodes, ascending.  chunk_items (test hook): list entries per launch
+        window; cap (test hook): room for that many records only, the true count is then in _sm_n_out."""
+        return self._sm_records(self._L.ugp_summary_mutations_chunked, self.SM_MUTATION, chunk_items, cap)
+
+    def summary_roho(self, chunk_items: int = 0, cap: Optional[int] = None):
+        """matUtils summary -R (summary.cpp:343-506, without dates): an SM_ROHO array, one record per reported (parent, mutation),
+        ascending by the depth-first position of the parent; nodes are BFS indices, `entry` indexes the mutation CSR."""
+        return self._sm_records(self._L.ugp_summary_roho_chunked, self.SM_ROHO, chunk_items, cap)
+
+    def summary_clades(self, columns):
+        """matUtils summary -c / -C (summary.cpp:88-137, 297-341): columns[c] = the nodes (BFS) with a non-empty annotation in column
+        c.  Returns (per_node, leaf_clade): an SM_CLADE array in the order given -- the leaves strictly below each node and the
+        leaves whose nearest annotated strict ancestor in that column it is -- and a uint32 array [n_columns, n_leaves]: that
+        ancestor for every leaf in BFS order, 0xFFFFFFFF when there is none."""
+        if not getattr(self, "_sm_ready", False):
+            self.summary_attach()
+        off, nodes = self._clades_csr(columns)
+        n_leaves = self._t.n - len(np.unique(self._t.parent[1:]))
+        per = np.zeros(len(nodes), self.SM_CLADE)
+        per["column"] = np.repeat(np.arange(len(columns), dtype=np.uint32), np.diff(off).astype(np.int64))
+        per["node"] = nodes
+        incl = np.zeros(len(nodes), np.uint32); excl = np.zeros(len(nodes), np.uint32)
+        leaf_clade = np.zeros((len(columns), n_leaves), np.uint32)
+        self._ck(self._L.ugp_summary_clades(self._h, _ptr(off), _ptr(nodes), len(columns), _ptr(incl), _ptr(excl), _ptr(leaf_clade)))
+        per["inclusive"] = incl
+        per["exclusive"] = excl
+        return per, leaf_clade
+
+    def summary_time(self, reps: int = 5):
+        """Bench hook: (sort_ms, roho_ms), the device time of the occurrence-list sort and of the RoHo kernel over every candidate."""
+        if not getattr(self, "_sm_ready", False):
+            self.summary_attach()
+        a, b = C.c_double(0), C.c_double(0)
+        self._ck(self._L.ugp_summary_time(self._h, int(reps), C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
+
     RIPPLES_EVENT = np.dtype([("branch", np.uint64), ("i", np.uint32), ("j", np.uint32), ("donor", np.uint32), ("acceptor", np.uint32),
                               ("donor_count", np.uint32), ("acceptor_count", np.uint32), ("donor_score", np.int32),
                               ("acceptor_score", np.int32), ("donor_sibling", np.uint8), ("acceptor_sibling", np.uint8),
