@@ -358,6 +358,53 @@ int ugp_summary_clades(ugp_mat *mat, const uint64_t *col_off /* [n_cols + 1] */,
 /* Bench hook: milliseconds of device time of the occurrence-list sort alone and of the RoHo kernel alone over every candidate
  * (no compaction, no copy to the host); mean of `reps` runs. */
 int ugp_summary_time(ugp_mat *mat, uint32_t reps, double *sort_ms, double *roho_ms);
+/* matUtils summary --translate (matUtils/translate.cpp: translate_main, do_mutations in TSV mode): per node the codons its mutations
+ * touch, with their letters before and after.  ugp_translate_attach shares the depth-first tables of `tree` exactly as
+ * ugp_genotypes_attach does (the handle's tree; arrays are copied; mut_par is needed; mut_nuc / mut_par of non-masked mutations in
+ * 1 .. 15, UGP_ERR_UNSUPPORTED otherwise; tables built from other mutation arrays: UGP_ERR_INVALID).
+ * ugp_translate_codons: the codon table in the reference's creation order (build_codon_map); codon c has the slots
+ *   slot_pos[3c .. 3c + 2] (1-based genome positions as mut_pos; a '+' codon ascends, a '-' codon descends) with the letters
+ *   slot_init[3c .. 3c + 2] they hold before any mutation ('-': the complemented FASTA).  The codons of a position rank by their
+ *   index.  A slot position < 1 or >= 2^28, or two equal ones within a codon, are UGP_ERR_INVALID.  The table replaces any earlier
+ *   one; n_codons = 0 is a table without codons.
+ * A position is CODING when a slot holds it.  The OWNER of a position on a node is the node's first non-masked entry there; the
+ *   STATE BEFORE node v at a slot with position p is the letter of mut_nuc of the owner of p on the nearest strict ancestor of v
+ *   that has one, else the slot's initial letter.  An owner at a coding position is INCONSISTENT when the letter of its mut_par as
+ *   stored differs from the state before its node at a slot that holds its position (the reference's walk is then history
+ *   dependent: undoing a node does not restore what was there).  A node with two non-masked entries at one coding position is a
+ *   DUPLICATE node.  Masked entries (mut_pos < 0) are skipped; a repeated non-coding position is nobody's business.
+ * ugp_translate: one record per (node, codon with an owner of the node in one of its slots), ascending by (depth-first position of
+ *   the node, lowest such position of the codon on that node, codon index) -- the order do_mutations first touches them.
+ *   before[s] = the state before the node at slot s, after[s] = the letter of mut_nuc of the node's owner at slot s, else
+ *   before[s]; ent[s] = that owner's index in tree->mut_off's CSR, else UINT32_MAX.  Letters are those of get_nuc
+ *   ("NACMGRSVTWYHKDBN").  out[0 .. min(cap, *n_out)) is written and *n_out is the true count.  `info` (may be NULL) is filled by
+ *   every call that ran; first_inconsistent is the first such entry in depth-first order of its node, then stored order (CSR index),
+ *   first_duplicate the first such node in depth-first order (BFS index), UINT32_MAX when there is none.  When n_inconsistent or
+ *   n_duplicate is non-zero the call returns UGP_ERR_UNSUPPORTED, *n_out = 0 and nothing is written to `out`: the caller walks
+ *   the tree serially instead.  A call before the attach or before the codon table is UGP_ERR_INVALID and names the missing call.
+ * ugp_translate_chunked (test hook) sets the work-items -- (owner at a coding position, codon of that position) pairs -- per launch
+ *   window (0: default). */
+typedef struct ugp_tr_record {
+    uint32_t node;               /* BFS index                                      */
+    uint32_t codon;              /* index into the codon table                     */
+    uint8_t before[3], after[3]; /* letters per slot                               */
+    uint8_t pad[2];
+    uint32_t ent[3];             /* the node's entry at each slot, or UINT32_MAX   */
+} ugp_tr_record;
+typedef struct ugp_tr_info {
+    uint64_t n_records;          /* as counted, also when the call refuses         */
+    uint64_t n_nodes;            /* nodes with at least one record                 */
+    uint64_t n_inconsistent, n_duplicate;
+    uint32_t first_inconsistent; /* CSR index of the entry                         */
+    uint32_t first_duplicate;    /* BFS index of the node                          */
+} ugp_tr_info;
+int ugp_translate_attach(ugp_mat *mat, const ugp_tree_desc *tree);
+int ugp_translate_codons(ugp_mat *mat, uint64_t n_codons, const int32_t *slot_pos /* [3 n_codons] */, const uint8_t *slot_init /* [3 n_codons] */);
+int ugp_translate(ugp_mat *mat, ugp_tr_record *out, uint64_t cap, uint64_t *n_out, ugp_tr_info *info);
+int ugp_translate_chunked(ugp_mat *mat, ugp_tr_record *out, uint64_t cap, uint64_t *n_out, ugp_tr_info *info, uint64_t chunk_items);
+/* Bench hook: milliseconds of device time of the passes of ugp_translate alone (records, scan, compaction over every window; no copy to
+ * the host); mean of `reps` runs. */
+int ugp_translate_time(ugp_mat *mat, uint32_t reps, double *ms);
 /* RIPPLES (ripples/main.cpp): the options of :22-44 that the search reads. branch_len >= 1 and parsimony_improvement >= 0
  * (UGP_ERR_INVALID otherwise: the reference's size_t arithmetic of :445-453 is not reproduced for negative values). */
 typedef struct ugp_ripples_opts {

@@ -101,6 +101,11 @@ SYMBOLS = {
     "ugp_summary_roho_chunked": (C.c_int, [P, P, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64]),
     "ugp_summary_clades": (C.c_int, [P, P, P, C.c_uint64, P, P, P]),
     "ugp_summary_time": (C.c_int, [P, C.c_uint32, P, P]),
+    "ugp_translate_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc)]),
+    "ugp_translate_codons": (C.c_int, [P, C.c_uint64, P, P]),
+    "ugp_translate": (C.c_int, [P, P, C.c_uint64, C.POINTER(C.c_uint64), P]),
+    "ugp_translate_chunked": (C.c_int, [P, P, C.c_uint64, C.POINTER(C.c_uint64), P, C.c_uint64]),
+    "ugp_translate_time": (C.c_int, [P, C.c_uint32, P]),
     "ugp_ripples_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc), P]),
     "ugp_ripples": (C.c_int, [P, C.POINTER(ugp_ripples_opts), P, C.c_uint64, P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ugp_subtree_mask": (C.c_int, [P, C.c_uint32, C.c_uint32, C.c_uint32, P]),

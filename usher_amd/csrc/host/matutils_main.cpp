@@ -5,6 +5,7 @@
 //   matutils-amd extract -i tree.pb [-s samples.txt] [-k sample:k] [-Y y] [-a -b -P n] [-u -t -o -v file] [-n] [-d dir] [--reference-ties]
 //                        [--host-genotypes]
 //   matutils-amd summarize -i tree.pb [-s -c -C -m -a -R file ...] [-A] [-M] [-d dir] [--host]
+//   matutils-amd translate -i tree.pb -g genes.gtf -f ref.fa -t out.tsv [-d dir] [--host]
 //
 // uncertainty_main / findEPPs_wrapper (uncertainty.cpp:279-339, 541-560): load the MAT, uncondense its leaves, read the sample
 // names, and for every sample report its equally parsimonious placements and neighborhood size (-e) and the candidate parents
@@ -16,6 +17,9 @@
 // make_vcf, convert.cpp:14-320; site table and genotype codes from ugp_genotypes.hip, formatted here chunk by chunk).
 // summary_main (summary.cpp:635-776), as the subcommand `summarize`: the sample, clade, sample-clade, mutation, aberrant and RoHo tables and the basic counts; the
 // numbers of -m, -R, -c and -C come from ugp_summary.hip, --host computes them with the reference's serial walks instead.
+// summary --translate (translate.cpp: translate_main, do_mutations), as the subcommand `translate`: per node the amino-acid, nucleotide
+// and codon changes and the leaves below it.  The codon letters come from ugp_translate.hip; a tree whose stored parent alleles
+// disagree with the states above them (every mutated - strand gene), or --host, takes the reference's serial do / undo walk.
 #include <hip/hip_runtime_api.h>
 #include <sys/stat.h>
 #include <zlib.h>
@@ -51,7 +55,7 @@ void usage(FILE *f) {
             "  -T, --threads            accepted for compatibility (the searches run on the device)\n"
             "      --device             HIP device ordinal [0]\n"
             "  (-d / --dropout-mutations is not supported)\n"
-            "       matutils-amd annotate --help | matutils-amd extract --help | matutils-amd summarize --help\n");
+            "       matutils-amd annotate --help | matutils-amd extract --help | matutils-amd summarize --help | matutils-amd translate --help\n");
 }
 
 int uncertainty(int argc, char **argv) {
@@ -1800,6 +1804,384 @@ int summary(int argc, char **argv) {   // summary_main, :635-776
     return 0;
 }
 
+// ---- translate (translate.cpp, summary --translate) ----------------------------------------------------------------
+
+void translate_usage(FILE *f) {
+    fprintf(f,
+            "Usage: matutils-amd translate -i tree.pb -g genes.gtf -f ref.fa -t out.tsv [-d dir] [-T n] [--device k] [--host]\n"
+            "  -i, --input-mat          input mutation-annotated tree [REQUIRED]\n"
+            "  -g, --input-gtf          GTF of the genes (CDS lines; taken as given, not relative to -d) [REQUIRED]\n"
+            "  -f, --input-fasta        FASTA of the reference (taken as given, not relative to -d) [REQUIRED]\n"
+            "  -t, --translate          tsv of the amino acid, nucleotide and codon changes of every node [REQUIRED]\n"
+            "  -d, --output-directory   directory of the output file [./]\n"
+            "  -T, --threads            accepted for compatibility (the table runs on the device)\n"
+            "      --device             HIP device ordinal [0]\n"
+            "      --host               the reference's serial walk on the host (slow; no device)\n");
+}
+
+// translate.hpp:20-49: the standard code and the ambiguous codons that still name one amino acid; anything else reads 'X'
+char tr_protein(const std::string &nt) {
+    static const std::unordered_map<std::string, char> table = [] {
+        const char *rows[] = {"A GCT GCC GCA GCG GCN", "C TGT TGC TGY", "D GAT GAC GAY", "E GAA GAG GAR", "F TTT TTC TTY", "G GGT GGC GGA GGG GGN",
+                              "H CAT CAC CAY", "I ATT ATC ATA ATH", "K AAA AAG AAR", "L TTA TTG CTT CTC CTA CTG YTR CTN", "M ATG", "N AAT AAC AAY",
+                              "P CCT CCC CCA CCG CCN", "Q CAA CAG CAR", "R CGT CGC CGA CGG AGA AGG CGN MGR", "S TCT TCC TCA TCG AGT AGC TCN AGY",
+                              "T ACT ACC ACA ACG ACN", "V GTT GTC GTA GTG GTN", "W TGG", "Y TAT TAC TAY", "* TAG TAA TGA"};
+        std::unordered_map<std::string, char> m;
+        for (const char *r : rows) {
+            std::vector<std::string> w;
+            split_ws(r, w);
+            for (size_t i = 1; i < w.size(); i++) m[w[i]] = w[0][0];
+        }
+        return m;
+    }();
+    const auto it = table.find(nt);
+    return it == table.end() ? 'X' : it->second;
+}
+char tr_complement(char c) {
+    static const char from[] = "ACGTMRWSYKVHDBN", to[] = "TGCAKYWSRMBDHVN";
+    const char *p = c ? strchr(from, c) : nullptr;
+    return p ? to[p - from] : 'N';
+}
+
+struct TrCodon {   // struct Codon, translate.hpp:51-94; sign: slot k holds position start + sign * k (the reference indexes by abs())
+    std::string orf_name, nucleotides, initial;
+    int codon_number = 0, start_position = 0, sign = 1;
+    char protein = 'X';
+    void mutate(int nuc_pos, char nuc) {
+        nucleotides[std::abs(nuc_pos - start_position)] = nuc;
+        protein = tr_protein(nucleotides);
+    }
+    std::string codon_id() const { return orf_name + ':' + std::to_string(codon_number + 1); }
+};
+using TrCodonMap = std::unordered_map<int, std::vector<TrCodon *>>;
+
+std::vector<std::string> tr_split(const std::string &s, char delim) {   // split, :3-11
+    std::vector<std::string> out;
+    std::stringstream ss(s);
+    std::string item;
+    while (std::getline(ss, item, delim)) out.push_back(item);
+    return out;
+}
+
+bool tr_read_fasta(const std::string &path, std::string &ref) {   // build_reference, :13-30
+    std::ifstream f(path);
+    if (!f) { fprintf(stderr, "ERROR: Could not open the fasta file: %s!\n", path.c_str()); return false; }
+    std::string line;
+    while (std::getline(f, line)) {
+        if (line.empty() || line[0] == '>') continue;
+        for (auto &c : line) c = (char)toupper(c);
+        if (line.back() == '\r') line.pop_back();
+        ref += line;
+    }
+    return true;
+}
+
+// build_codon_map, :42-238: the codons in creation order.  Where the reference would read past the FASTA or past a line's fields,
+// this returns false with one line in `err`.
+bool tr_build_codons(const std::string &path, const std::string &ref, std::vector<TrCodon> &codons, std::string &err) {
+    std::ifstream f(path);
+    if (!f) { err = "ERROR: Could not open the gtf file: " + path + "!"; return false; }
+    std::vector<std::string> lines, done;
+    std::string line;
+    while (std::getline(f, line)) lines.push_back(line);
+    auto number = [&](const std::string &s, int &v) {
+        try { v = std::stoi(s); } catch (...) { err = "ERROR: GTF: '" + s + "' is not a number"; return false; }
+        return true;
+    };
+    auto gene_of = [&](const std::string &field, std::string &gene) {
+        const std::vector<std::string> parts = tr_split(field, '"');
+        if (parts.size() < 2) { err = "ERROR: GTF: gene_id without a quoted name"; return false; }
+        gene = parts[1];
+        return true;
+    };
+    auto add = [&](const std::string &gene, int &counter, int pos, int sign) {
+        if (pos < 0 || pos >= (int)ref.size() || pos + 2 * sign < 0 || pos + 2 * sign >= (int)ref.size()) {
+            err = "ERROR: GTF: a CDS of gene " + gene + " reaches past the FASTA (" + std::to_string(ref.size()) + " bases)";
+            return false;
+        }
+        TrCodon c;
+        c.orf_name = gene; c.codon_number = counter++; c.start_position = pos; c.sign = sign;
+        for (int k = 0; k < 3; k++) c.nucleotides += sign > 0 ? ref[pos + k] : tr_complement(ref[pos - k]);
+        c.initial = c.nucleotides;
+        c.protein = tr_protein(c.nucleotides);
+        codons.push_back(c);
+        return true;
+    };
+    auto cds = [&](const std::string &gene, int &counter, int start, int stop, char strand) {
+        if (strand == '+') {
+            for (int pos = start - 1; pos < stop; pos += 3) if (!add(gene, counter, pos, 1)) return false;
+        } else {
+            for (int pos = stop - 1; pos > start; pos -= 3) if (!add(gene, counter, pos, -1)) return false;   // (0-based against 1-based, as :118)
+        }
+        return true;
+    };
+    const char *few = "ERROR: GTF: a data line with fewer than 9 columns";
+    for (const std::string &outer : lines) {
+        if (outer.empty() || outer[0] == '#') continue;
+        const std::vector<std::string> fo = tr_split(outer, '\t');
+        if (fo.size() <= 1) continue;
+        if (fo.size() < 9) { err = few; return false; }
+        if (fo[8].substr(0, 7) != "gene_id") { err = "ERROR: GTF file formatted incorrectly. Please see the wiki for details."; return false; }
+        std::string gene;
+        if (!gene_of(fo[8], gene)) return false;
+        const char strand = fo[6].empty() ? '\0' : fo[6][0];
+        if (fo[2] != "CDS") continue;
+        if (std::find(done.begin(), done.end(), gene) != done.end()) continue;
+        done.push_back(gene);
+        int first_start = 0, first_stop = 0, counter = 0;
+        if (!number(fo[3], first_start) || !number(fo[4], first_stop) || !cds(gene, counter, first_start, first_stop, strand)) return false;
+        for (const std::string &inner : lines) {   // the gene's further CDS lines continue its codon numbers
+            if (inner.empty() || inner[0] == '#') continue;
+            const std::vector<std::string> fi = tr_split(inner, '\t');
+            if (fi.size() < 9) { err = few; return false; }
+            std::string gene_inner;
+            if (!gene_of(fi[8], gene_inner)) return false;
+            if (fi[2] != "CDS" || gene_inner != gene) continue;
+            int start = 0, stop = 0;
+            if (!number(fi[3], start) || !number(fi[4], stop)) return false;
+            const char s2 = fi[6].empty() ? '\0' : fi[6][0];
+            if (start != first_start || strand != s2)
+                if (!cds(gene, counter, start, stop, s2)) return false;
+        }
+    }
+    return true;
+}
+
+TrCodonMap tr_codon_map(std::vector<TrCodon> &codons) {
+    TrCodonMap m;
+    for (TrCodon &c : codons)
+        for (int k = 0; k < 3; k++) m[c.start_position + c.sign * k].push_back(&c);
+    return m;
+}
+
+// do_mutations, :498-588, taxodium_format == false
+std::string tr_do_mutations(std::vector<uh::Mutation> &mutations, TrCodonMap &codon_map) {
+    std::string prot_string, nuc_string, cchange_string;
+    std::sort(mutations.begin(), mutations.end(), by_position);
+    struct ByPos { bool operator()(const uh::Mutation *a, const uh::Mutation *b) const { return a->position < b->position; } };
+    std::unordered_map<std::string, std::set<const uh::Mutation *, ByPos>> codon_to_nt_map;
+    std::unordered_map<std::string, std::string> latest_codon_map, orig_codons;
+    std::unordered_map<std::string, char> orig_proteins;
+    std::vector<TrCodon *> affected_codons;
+    for (const auto &m : mutations) {
+        const char mutated_nuc = uh::nuc_char(m.mut_nuc), par_nuc = uh::nuc_char(m.par_nuc);
+        const int pos = m.position - 1;
+        const auto it = codon_map.find(pos);
+        if (it == codon_map.end()) continue;   // not a coding mutation
+        for (TrCodon *c : it->second) {
+            const std::string codon_id = c->codon_id();
+            c->mutate(pos, par_nuc);
+            if (orig_proteins.find(codon_id) == orig_proteins.end()) orig_proteins.insert({codon_id, c->protein});
+            if (std::find(affected_codons.begin(), affected_codons.end(), c) == affected_codons.end()) affected_codons.push_back(c);
+            if (orig_codons.find(codon_id) == orig_codons.end()) orig_codons.insert({codon_id, c->nucleotides});
+            c->mutate(pos, mutated_nuc);
+            latest_codon_map[codon_id] = c->nucleotides;
+            codon_to_nt_map[codon_id].insert(&m);
+        }
+    }
+    for (TrCodon *c : affected_codons) {
+        const std::string codon_id = c->codon_id();
+        const std::vector<std::string> parts = tr_split(codon_id, ':');
+        prot_string += parts[0] + ':' + orig_proteins.find(codon_id)->second + parts[1] + c->protein + ';';
+        for (const uh::Mutation *m : codon_to_nt_map.find(codon_id)->second) nuc_string += m->str() + ",";
+        if (!nuc_string.empty() && nuc_string.back() == ',') { nuc_string.resize(nuc_string.length() - 1); nuc_string += ';'; }
+        cchange_string += orig_codons.find(codon_id)->second + ">" + latest_codon_map.find(codon_id)->second + ";";
+    }
+    for (std::string *s : {&nuc_string, &prot_string, &cchange_string})
+        if (!s->empty() && s->back() == ';') s->resize(s->length() - 1);
+    if (nuc_string.empty() || prot_string.empty() || cchange_string.empty()) return "";
+    return prot_string + '\t' + nuc_string + '\t' + cchange_string;
+}
+
+void tr_undo_mutations(const std::vector<uh::Mutation> &mutations, TrCodonMap &codon_map) {   // :590-605
+    for (const auto &m : mutations) {
+        const int pos = m.position - 1;
+        const auto it = codon_map.find(pos);
+        if (it == codon_map.end()) continue;
+        for (TrCodon *c : it->second) c->mutate(pos, uh::nuc_char(m.par_nuc));
+    }
+}
+
+const char *kTranslateHeader = "node_id\taa_mutations\tnt_mutations\tcodon_changes\tleaves_sharing_mutations\n";
+
+// get_leaves(node).size() of every node in one pass (a leaf counts itself): flat_index must be the position in `dfs`
+std::vector<uint32_t> tr_leaf_counts(const std::vector<uh::Node *> &dfs) {
+    std::vector<uint32_t> cnt(dfs.size(), 0);
+    for (size_t i = dfs.size(); i-- > 0;) {
+        if (dfs[i]->is_leaf()) cnt[i] = 1;
+        if (dfs[i]->parent) cnt[dfs[i]->parent->flat_index] += cnt[i];
+    }
+    return cnt;
+}
+
+// translate_main's loop, :270-291.  (In a depth-first expansion the last common ancestor of a node and the node visited before it
+// is the node's parent, so the undo chain runs up to there.)
+void host_translate(uh::Tree &T, std::vector<TrCodon> &codons, std::ofstream &f) {
+    for (TrCodon &c : codons) { c.nucleotides = c.initial; c.protein = tr_protein(c.initial); }
+    TrCodonMap codon_map = tr_codon_map(codons);
+    const std::vector<uh::Node *> dfs = T.dfs();
+    for (size_t i = 0; i < dfs.size(); i++) { dfs[i]->flat_index = (uint32_t)i; dfs[i]->flat_epoch = 0; }
+    const std::vector<uint32_t> leaves = tr_leaf_counts(dfs);
+    f << kTranslateHeader;
+    uh::Node *last_visited = nullptr;
+    for (size_t i = 0; i < dfs.size(); i++) {
+        uh::Node *node = dfs[i];
+        if (last_visited != node->parent)
+            for (uh::Node *trace = last_visited; trace != node->parent; trace = trace->parent) tr_undo_mutations(trace->mutations, codon_map);
+        const std::string result = tr_do_mutations(node->mutations, codon_map);
+        if (result != "") f << node->id << '\t' << result << '\t' << leaves[i] << '\n';
+        last_visited = node;
+    }
+}
+
+// The device path: the records of ugp_translate.hip, formatted to the same bytes.  False (with a line on stderr) when the library
+// refuses the tree: the caller walks it on the host.
+bool device_translate(uh::Tree &T, const std::vector<TrCodon> &codons, int device, std::ofstream &f) {
+    const std::vector<uh::Node *> bfs = T.bfs();
+    const uint64_t N = bfs.size();
+    for (uint64_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
+    std::vector<uint32_t> parent(N);
+    std::vector<uint64_t> mut_off(N + 1, 0);
+    std::vector<int32_t> pos;
+    std::vector<uint8_t> ref, par, nuc;
+    std::vector<const uh::Mutation *> ent;
+    for (uint64_t j = 0; j < N; j++) {
+        parent[j] = bfs[j]->parent ? bfs[j]->parent->flat_index : UINT32_MAX;
+        for (const auto &m : bfs[j]->mutations) {
+            pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
+            ent.push_back(&m);
+        }
+        mut_off[j + 1] = pos.size();
+    }
+    const std::vector<uint64_t> no_off(N + 1, 0);
+    if (pos.empty()) { pos.push_back(0); ref.push_back(0); par.push_back(0); nuc.push_back(0); }   // (never read: no null arrays)
+    const ugp_tree_desc bare{N, parent.data(), no_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+    const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+    struct Handle { ugp_mat *h = nullptr; ~Handle() { if (h) ugp_mat_destroy(h); } } H;
+    if (ugp_mat_create(&bare, device, &H.h) != UGP_OK) lib_fail("ugp_mat_create");
+    int rc = ugp_translate_attach(H.h, &desc);
+    if (rc == UGP_ERR_UNSUPPORTED) {
+        fprintf(stderr, "The device does not take this tree (%s); walking it on the host.\n", ugp_last_error());
+        return false;
+    }
+    if (rc != UGP_OK) lib_fail("ugp_translate_attach");
+    std::vector<int32_t> slot_pos(3 * codons.size());
+    std::vector<uint8_t> slot_init(3 * codons.size());
+    for (size_t c = 0; c < codons.size(); c++)
+        for (int k = 0; k < 3; k++) {
+            slot_pos[3 * c + k] = codons[c].start_position + codons[c].sign * k + 1;
+            slot_init[3 * c + k] = (uint8_t)codons[c].initial[k];
+        }
+    if (ugp_translate_codons(H.h, codons.size(), slot_pos.data(), slot_init.data()) != UGP_OK) lib_fail("ugp_translate_codons");
+    uint64_t n = 0;
+    ugp_tr_info info;
+    rc = ugp_translate(H.h, nullptr, 0, &n, &info);
+    if (rc == UGP_ERR_UNSUPPORTED) {
+        fprintf(stderr, "The closed form does not hold for this tree: %llu inconsistent parent alleles", (unsigned long long)info.n_inconsistent);
+        if (info.n_inconsistent) {
+            const uint64_t j = std::upper_bound(mut_off.begin(), mut_off.end(), (uint64_t)info.first_inconsistent) - mut_off.begin() - 1;
+            fprintf(stderr, " (first: %s on %s)", ent[info.first_inconsistent]->str().c_str(), bfs[j]->id.c_str());
+        }
+        fprintf(stderr, ", %llu nodes with a coding position twice", (unsigned long long)info.n_duplicate);
+        if (info.n_duplicate) fprintf(stderr, " (first: %s)", bfs[info.first_duplicate]->id.c_str());
+        fprintf(stderr, "; walking it on the host.\n");
+        return false;
+    }
+    if (rc != UGP_OK) lib_fail("ugp_translate");
+    std::vector<ugp_tr_record> recs(n);
+    if (n && ugp_translate(H.h, recs.data(), n, &n, &info) != UGP_OK) lib_fail("ugp_translate");
+    // leaves per node, by breadth-first index: children come after their parent
+    std::vector<uint32_t> leaves(N, 0);
+    for (uint64_t j = N; j-- > 0;) {
+        if (bfs[j]->is_leaf()) leaves[j] = 1;
+        if (bfs[j]->parent) leaves[bfs[j]->parent->flat_index] += leaves[j];
+    }
+    std::string out = kTranslateHeader, prot, nt, cch;
+    for (size_t a = 0; a < recs.size();) {   // the records of one node follow each other
+        size_t b = a;
+        prot.clear(); nt.clear(); cch.clear();
+        for (; b < recs.size() && recs[b].node == recs[a].node; b++) {
+            const ugp_tr_record &r = recs[b];
+            const TrCodon &c = codons[r.codon];
+            const std::string before((const char *)r.before, 3), after((const char *)r.after, 3);
+            if (b > a) { prot += ';'; nt += ';'; cch += ';'; }
+            prot += c.orf_name + ':' + tr_protein(before) + std::to_string(c.codon_number + 1) + tr_protein(after);
+            bool first = true;
+            for (int k = c.sign > 0 ? 0 : 2; k >= 0 && k < 3; k += c.sign) {   // ascending position
+                if (r.ent[k] == UINT32_MAX) continue;
+                if (!first) nt += ',';
+                nt += ent[r.ent[k]]->str();
+                first = false;
+            }
+            cch += before + ">" + after;
+        }
+        out += bfs[recs[a].node]->id + '\t' + prot + '\t' + nt + '\t' + cch + '\t' + std::to_string(leaves[recs[a].node]) + '\n';
+        if (out.size() > (1u << 20)) { f << out; out.clear(); }
+        a = b;
+    }
+    f << out;
+    return true;
+}
+
+int translate(int argc, char **argv) {   // summary_main's --translate branch (summary.cpp:698-713) and translate_main
+    std::string mat, dir = "./", gtf, fasta, table;
+    bool host = false;
+    int device = 0;
+    for (int i = 0; i < argc; i++) {
+        const std::string a = argv[i];
+        auto val = [&](std::string &dst) -> bool {
+            if (i + 1 >= argc) { fprintf(stderr, "ERROR: %s needs a value\n", a.c_str()); translate_usage(stderr); return false; }
+            dst = argv[++i];
+            return true;
+        };
+        std::string tmp;
+        bool ok = true;
+        if (a == "-i" || a == "--input-mat") ok = val(mat);
+        else if (a == "-d" || a == "--output-directory") ok = val(dir);
+        else if (a == "-g" || a == "--input-gtf") ok = val(gtf);
+        else if (a == "-f" || a == "--input-fasta") ok = val(fasta);
+        else if (a == "-t" || a == "--translate") ok = val(table);
+        else if (a == "-T" || a == "--threads") ok = val(tmp);
+        else if (a == "--device") { ok = val(tmp); device = atoi(tmp.c_str()); }
+        else if (a == "--host") host = true;
+        else if (a == "-h" || a == "--help") { translate_usage(stdout); return 0; }
+        else { fprintf(stderr, "ERROR: unknown option %s\n", a.c_str()); translate_usage(stderr); return 1; }
+        if (!ok) return 1;
+    }
+    if (mat.empty()) { fprintf(stderr, "ERROR: the option '--input-mat' is required but missing\n"); translate_usage(stderr); return 1; }
+    if (table.empty()) { fprintf(stderr, "ERROR: the option '--translate' is required but missing\n"); translate_usage(stderr); return 1; }
+    if (gtf.empty()) fprintf(stderr, "ERROR: You must specify a GTF file with -g\n");
+    if (fasta.empty()) fprintf(stderr, "ERROR: You must specify a FASTA reference file with -f\n");
+    if (gtf.empty() || fasta.empty()) return 1;
+    struct stat sb;
+    if (stat(dir.c_str(), &sb) != 0) {
+        fprintf(stderr, "Creating output directory.\n\n");
+        mkdir(dir.c_str(), 0777);
+    }
+    char *canon = realpath(dir.c_str(), nullptr);
+    if (!canon) { fprintf(stderr, "ERROR: cannot resolve the output directory %s\n", dir.c_str()); return 1; }
+    const std::string path = std::string(canon) + "/" + table;
+    free(canon);
+    fprintf(stderr, "Loading input MAT file %s.\n", mat.c_str());
+    uh::Tree T;
+    std::string err;
+    if (!uh::load_mat(mat, T, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+    T.uncondense_leaves();
+    std::string reference;
+    if (!tr_read_fasta(fasta, reference)) return 1;
+    std::vector<TrCodon> codons;
+    if (!tr_build_codons(gtf, reference, codons, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
+    fprintf(stderr, "Writing translation to output %s\n", path.c_str());
+    const auto t0 = std::chrono::steady_clock::now();
+    std::ofstream f(path, std::ios::binary);
+    if (!f) { fprintf(stderr, "ERROR: Could not open file for writing: %s!\n", path.c_str()); return 1; }
+    if (host || !device_translate(T, codons, device, f)) host_translate(T, codons, f);
+    f.close();
+    if (!f) { fprintf(stderr, "ERROR: could not write %s\n", path.c_str()); return 1; }
+    fprintf(stderr, "Completed in %ld msec \n\n", (long)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count());
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -1809,6 +2191,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "extract")) return extract(argc - 2, argv + 2);
     // matUtils summary runs as `summarize`: the spelling `summary` stays refused, as it has been since the tool's first release
     if (!strcmp(argv[1], "summarize")) return summary(argc - 2, argv + 2);
-    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate, extract, summarize)\n", argv[1]);
+    if (!strcmp(argv[1], "translate")) return translate(argc - 2, argv + 2);
+    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate, extract, summarize, translate)\n", argv[1]);
     return 1;
 }

@@ -31,6 +31,7 @@
 #include "ugp_nearest.hpp"
 #include "ugp_genotypes.hpp"
 #include "ugp_summary.hpp"
+#include "ugp_translate.hpp"
 #include "ugp_update.hpp"
 #include "usher_amd.h"
 
@@ -297,6 +298,7 @@ struct ugp_mat {
     ugp::NearState *near = nullptr;  // matUtils extract nearest-k tables (ugp_nearest_attach), or none
     ugp::GtState *gt = nullptr;      // matUtils extract -v tables (ugp_genotypes_attach), or none
     ugp::SmState *sm = nullptr;      // matUtils summary tables (ugp_summary_attach), or none
+    ugp::TrState *tr = nullptr;      // matUtils summary --translate tables (ugp_translate_attach), or none
     ugp::DfsTables *dfs = nullptr;   // the depth-first tables uncertainty and annotate share (their first attach), or none
     hipEvent_t kb_done = nullptr;    // behind the latest k_best8 launch of this handle ...
     hipStream_t kb_done_on = nullptr;   // ... on this stream
@@ -1371,6 +1373,7 @@ void ugp_mat_destroy(ugp_mat *m) {
     ugp::nk_free(m->near);
     ugp::gt_free(m->gt);
     ugp::sm_free(m->sm);
+    ugp::tr_free(m->tr);
     ugp::dfs_tables_free(m->dfs);
     delete m;
 }
@@ -1939,6 +1942,33 @@ int ugp_summary_clades(ugp_mat *m, const uint64_t *col_off, const uint32_t *node
 int ugp_summary_time(ugp_mat *m, uint32_t reps, double *sort_ms, double *roho_ms) {
     if (!m) return fail(UGP_ERR_INVALID, "null argument");
     return ugp::sm_time(m->sm, reps, sort_ms, roho_ms);
+}
+
+// ---- matUtils summary --translate: codon changes per node (ugp_translate.hip) ------------------------------------------
+
+int ugp_translate_attach(ugp_mat *m, const ugp_tree_desc *tree) {
+    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
+    if (int rc = check_handle_tree(m, tree)) return rc;
+    return ugp::tr_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->tr);
+}
+
+int ugp_translate_codons(ugp_mat *m, uint64_t n_codons, const int32_t *slot_pos, const uint8_t *slot_init) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::tr_codons(m->tr, n_codons, slot_pos, slot_init);
+}
+
+int ugp_translate_chunked(ugp_mat *m, ugp_tr_record *out, uint64_t cap, uint64_t *n_out, ugp_tr_info *info, uint64_t chunk_items) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::tr_run(m->tr, out, cap, n_out, info, chunk_items);
+}
+
+int ugp_translate(ugp_mat *m, ugp_tr_record *out, uint64_t cap, uint64_t *n_out, ugp_tr_info *info) {
+    return ugp_translate_chunked(m, out, cap, n_out, info, 0);
+}
+
+int ugp_translate_time(ugp_mat *m, uint32_t reps, double *ms) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::tr_time(m->tr, reps, ms);
 }
 
 // ---- RIPPLES (ugp_ripples.hip) -----------------------------------------------------------------------------------------

@@ -482,6 +482,68 @@ class Placer:
         self._ck(self._L.ugp_summary_time(self._h, int(reps), C.byref(a), C.byref(b)))
         return float(a.value), float(b.value)
 
+    # ---- matUtils summary --translate (ugp_translate_attach / _codons / ugp_translate) ----------------------------------------
+    TR_RECORD = np.dtype([("node", np.uint32), ("codon", np.uint32), ("before", np.uint8, (3,)), ("after", np.uint8, (3,)),
+                          ("pad", np.uint8, (2,)), ("ent", np.uint32, (3,))])
+    TR_INFO = np.dtype([("n_records", np.uint64), ("n_nodes", np.uint64), ("n_inconsistent", np.uint64), ("n_duplicate", np.uint64),
+                        ("first_inconsistent", np.uint32), ("first_duplicate", np.uint32)])
+
+    def translate_attach(self, arrays: Optional[Dict] = None):
+        """ugp_translate_attach with the placer's own tree, or with other mutation arrays on the same topology (masked entries,
+        ambiguous alleles, a position twice on one node: trees the placement tables refuse).  The depth-first tables are shared as
+        genotypes_attach describes."""
+        t = self._t if arrays is None else _TreeArrays(arrays)
+        self._ck(self._L.ugp_translate_attach(self._h, C.byref(t.desc)))
+        self._tr_ready = True
+
+    def translate_codons(self, slot_pos, slot_init):
+        """ugp_translate_codons: the codon table in the reference's creation order.  slot_pos [n, 3]: 1-based positions as mut_pos
+        (descending for a '-' codon); slot_init [n, 3]: the letters before any mutation (bytes, or a str / bytes of 3 n letters).
+        Replaces any earlier table."""
+        if not getattr(self, "_tr_ready", False):
+            self.translate_attach()
+        pos = np.ascontiguousarray(slot_pos, dtype=np.int32).reshape(-1)
+        if isinstance(slot_init, str):
+            slot_init = slot_init.encode()
+        init = (np.frombuffer(slot_init, np.uint8) if isinstance(slot_init, (bytes, bytearray))
+                else np.ascontiguousarray(slot_init, dtype=np.uint8).reshape(-1))
+        init = np.ascontiguousarray(init)
+        if len(pos) % 3 or len(pos) != len(init):
+            raise UgpError(-1, "slot_pos and slot_init hold three values per codon")
+        self._ck(self._L.ugp_translate_codons(self._h, len(pos) // 3, _ptr(pos), _ptr(init)))
+
+    def translate(self, chunk_items: int = 0, cap: Optional[int] = None):
+        """matUtils summary --translate (translate.cpp, do_mutations in TSV mode): (records, info) -- a TR_RECORD array, one record per
+        (node, codon its mutations touch), ascending by (depth-first position of the node, lowest mutated position of the codon on
+        it, codon index), and a TR_INFO scalar.  A tree whose stored parent alleles disagree with the states above them, or with
+        a coding position twice on one node, raises UgpError -2 (the serial walk is history dependent there); the TR_INFO of the
+        last call, refused or not, stays in _tr_info.  chunk_items (test hook): work-items per launch window; cap (test hook):
+        room for that many records only."""
+        info = np.zeros(1, self.TR_INFO)
+        self._tr_info = None
+        n_out = C.c_uint64(0)
+        fn = self._L.ugp_translate_chunked
+
+        def call(buf, room):
+            rc = fn(self._h, _ptr(buf) if room else None, int(room), C.byref(n_out), _ptr(info), int(chunk_items))
+            if rc != -1:   # (an invalid call fills nothing)
+                self._tr_info = info[0].copy()
+            self._ck(rc)
+
+        if cap is None:   # the two-call convention: the count, then the records
+            call(None, 0)
+            cap = int(n_out.value)
+        out = np.zeros(int(cap), self.TR_RECORD)
+        call(out, cap)
+        self._tr_n_out = int(n_out.value)
+        return out[:min(int(cap), self._tr_n_out)], info[0].copy()
+
+    def translate_time(self, reps: int = 5) -> float:
+        """Bench hook: milliseconds of device time of the passes of ugp_translate alone, no copy to the host."""
+        ms = C.c_double(0)
+        self._ck(self._L.ugp_translate_time(self._h, int(reps), C.byref(ms)))
+        return float(ms.value)
+
     RIPPLES_EVENT = np.dtype([("branch", np.uint64), ("i", np.uint32), ("j", np.uint32), ("donor", np.uint32), ("acceptor", np.uint32),
                               ("donor_count", np.uint32), ("acceptor_count", np.uint32), ("donor_score", np.int32),
                               ("acceptor_score", np.int32), ("donor_sibling", np.uint8), ("acceptor_sibling", np.uint8),
