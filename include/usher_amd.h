@@ -543,6 +543,12 @@ int ugp_get_timing_sum(ugp_mat *mat, ugp_timing *sum, uint32_t *n_calls);
  * call built them: cum_over / cum_under per block of 16 packed-stream words.  *n_blocks = entries per tile (0: that call did not
  * use the bound); with over == NULL only the count is returned.  Blocking; the caller checks `tile` against its own batch. */
 int ugp_debug_bound3_tables(ugp_mat *mat, uint32_t tile, uint16_t *over, uint16_t *under, uint64_t cap, uint64_t *n_blocks);
+/* Test hook: only the locality pre-pass of a batch, by method (0: the walk of the coarse tree, 1: the pass from the samples' own
+ * rows, refused with UGP_ERR_UNSUPPORTED where a call would not take it).  Blocking.  cost / coarse_node: [n_queries]; kept_bfs
+ * (optional, room for kept_cap): the BFS indices of the coarse tree's nodes, which coarse_node indexes. */
+int ugp_debug_coarse_pass(ugp_mat *mat, ugp_qset *qs, int method, int32_t *cost, uint32_t *coarse_node, uint32_t *kept_bfs, uint64_t kept_cap, uint64_t *n_kept);
+/* Test hook: the pre-pass of the handle's latest placement call -- 0: none, 1: the walk of the coarse tree, 2: from the samples' rows. */
+int ugp_debug_last_prepass(const ugp_mat *mat);
 
 /* Message for the last non-zero return on the calling thread. */
 const char *ugp_last_error(void);

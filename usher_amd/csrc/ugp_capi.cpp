@@ -21,6 +21,7 @@
 #include "ugp_bound3.hpp"
 #include "ugp_dense.hpp"
 #include "ugp_tuner.hpp"
+#include "ugp_coarse.hpp"
 #include "ugp_plan.hpp"
 #include "ugp_flatten.hpp"
 #include "ugp_kernels.hpp"
@@ -193,6 +194,11 @@ struct ugp_mat {
     bool wide_descent = false;
     DevBuf<uint32_t> d_coarse2dfs, d_coarse_bin;   // coarse node -> depth-first rank in the full tree / its position among the coarse nodes in that order
     uint32_t n_coarse_bins = 0;
+    // the pre-pass without tiles (ugp_coarse.hpp): the coarse tree's static tables, or none (cs_nodes == 0)
+    DevBuf<uint32_t> d_cs_node, d_cs_rmq, d_cs_site_off, d_cs_events;
+    uint32_t cs_nodes = 0, cs_max_per_pos = 0;
+    int last_prepass = 0;         // which pre-pass the handle's latest call took: 0 none, 1 the walk of the coarse tree, 2 k_coarse_sparse
+    bool mask_in_force = false;   // (between the two mask_words of an extended search: the streams carry a node mask)
     std::vector<uint32_t> h_level_off;   // breadth-first level boundaries (empty: the input is not a breadth-first expansion)
     uint32_t max_level_width = 0;
     // extended searches (ugp_place_batch_ex): host copy of the topology, the reference's depth-first order and its tie rank
@@ -430,6 +436,11 @@ ugp::PlanTree plan_tree(const ugp_mat *m) {
     t.n_nodes = f.n_nodes; t.n_sites = f.n_sites; t.n_chunks = f.n_chunks; t.max_chunk8_words = f.max_chunk8_words;
     t.max_path_muts = f.max_path_muts; t.lds_slots = f.lds_slots; t.mask_not_first = f.mask_not_first;
     t.coarse = m->coarse != nullptr; t.b3_events = m->d_b3_events.p != nullptr; t.wide_descent = m->wide_descent;
+    if (m->coarse && m->cs_nodes) {
+        t.coarse_nodes = m->cs_nodes; t.coarse_max_per_pos = m->cs_max_per_pos;
+        t.coarse_excluded = m->upd.n_excluded != 0;   // (ugp_mat_update counts on the main handle, also for the coarse tree's nodes)
+        t.coarse_masked = m->mask_in_force;
+    }
     return t;
 }
 
@@ -480,6 +491,35 @@ int side_fill(PlaceCall &c) {
 }
 
 // The coarse pre-pass of a sorted call: every sample placed on the coarse tree, into W.d_coarse_res.
+// A plain batch on an unchanged coarse tree (CallPlan::coarse_sparse): one launch for the whole call, from the samples' own rows.
+int coarse_sparse(ugp_mat *m, const ugp_qset *qs, uint32_t cap, ugp_result *out, hipStream_t s) {
+    const ugp_mat *t = m->coarse;
+    ugp::CoarseSparseArgs a{};
+    a.ent_off = (const uint64_t *)qs->d_ent_off.p; a.pos = qs->d_pos.p; a.ref = qs->d_ref.p; a.nuc = qs->d_nuc.p; a.is_missing = qs->d_missing.p;
+    a.err = qs->d_err.p; a.pos2site = t->d_pos2site.p; a.max_pos = (uint32_t)t->flat.max_pos; a.n_nodes = m->cs_nodes; a.n_queries = (uint32_t)qs->n_queries;
+    a.cap = cap; a.site_off = m->d_cs_site_off.p; a.events = (const uint2 *)m->d_cs_events.p; a.node = (const uint2 *)m->d_cs_node.p; a.rmq = m->d_cs_rmq.p;
+    a.dfs2bfs = t->d_dfs2bfs.p; a.out = out;
+    // (a set without rows has no row arrays on the device -- qset_fill stops in front of them, and a reused set still holds the
+    // previous batch's: the kernel then reads none of them)
+    a.n_ent = qs->n_ent; a.max_rows = qs->max_rows; a.max_per_pos = m->cs_max_per_pos;
+    HIP_TRY(ugp::launch_coarse_sparse(a, s));
+    return UGP_OK;
+}
+
+// The pre-pass as a walk of the coarse tree: the request coarse_pass() and the test hook hand to run_place.
+// The pre-pass has no phase 2: its walk records which node set every chunk minimum (k_best8<ARG>, k_coarse_result) -- any
+// node of minimal cost serves the sort and the descent.  (UGP_COARSE_PHASE2=1: the full phase 2 instead, i.e. the
+// reference's tie-break winner: 0.2 ms more per 16,384 samples, the same answers.)
+int coarse_walked(ugp_mat *m, ugp_qset *qs, ugp_result *out, hipStream_t s, int wi) {
+    m->coarse->sharing = m->sharing; m->coarse->share_n = m->share_n; m->coarse->share_sets = m->share_sets;
+    PlaceReq cr;
+    cr.out = out; cr.stream = s; cr.wi = wi;
+    cr.coarse_only = m->coarse->d_node_pos8.p && m->coarse->flat.max_chunk8_words < 65536u && !m->knobs.coarse_phase2;
+    if (int rc = run_place(m->coarse, qs, cr)) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    return UGP_OK;
+}
+
 int coarse_pass(PlaceCall &c) {
     ugp_mat *m = c.m;
     ugp_mat::Work &W = c.W;
@@ -487,15 +527,14 @@ int coarse_pass(PlaceCall &c) {
     HIP_TRY(W.d_coarse_res.reserve(c.call.Q));
     if (!TG.ev_coarse[0]) { HIP_TRY(hipEventCreate(&TG.ev_coarse[0])); HIP_TRY(hipEventCreate(&TG.ev_coarse[1])); }
     HIP_TRY(hipEventRecord(TG.ev_coarse[0], c.s));
-    // The pre-pass has no phase 2: its walk records which node set every chunk minimum (k_best8<ARG>, k_coarse_result) -- any
-    // node of minimal cost serves the sort and the descent.  (UGP_COARSE_PHASE2=1: the full phase 2 instead, i.e. the
-    // reference's tie-break winner: 0.2 ms more per 16,384 samples, the same answers.)
-    m->coarse->sharing = m->sharing; m->coarse->share_n = m->share_n; m->coarse->share_sets = m->share_sets;
-    PlaceReq cr;
-    cr.out = W.d_coarse_res.p; cr.stream = c.s; cr.wi = c.r.wi;
-    cr.coarse_only = m->coarse->d_node_pos8.p && m->coarse->flat.max_chunk8_words < 65536u && !m->knobs.coarse_phase2;
-    if (int rc = run_place(m->coarse, c.qs, cr)) return rc;
-    HIP_TRY(hipSetDevice(m->device));
+    m->last_prepass = c.cp.coarse_sparse ? 2 : 1;
+    if (c.cp.coarse_sparse) {
+        if (int rc = coarse_sparse(m, c.qs, c.cp.coarse_cap, W.d_coarse_res.p, c.s)) return rc;
+        HIP_TRY(hipEventRecord(TG.ev_coarse[1], c.s));
+        TG.coarse_timed = true;
+        return UGP_OK;
+    }
+    if (int rc = coarse_walked(m, c.qs, W.d_coarse_res.p, c.s, c.r.wi)) return rc;
     HIP_TRY(hipEventRecord(TG.ev_coarse[1], c.s));
     TG.coarse_timed = true;
     return UGP_OK;
@@ -949,6 +988,7 @@ int run_place(ugp_mat *m, ugp_qset *qs, const PlaceReq &r) {
     c.cp = ugp::plan_call(c.tree, m->knobs, c.call);
     c.ex_skip = c.cp.ex_skip ? r.ex->skip : nullptr;
     c.TG->coarse_timed = false;
+    m->last_prepass = 0;
     if (int rc = side_fill(c)) return rc;
     if (c.cp.sorted) if (int rc = coarse_pass(c)) return rc;
     for (uint64_t q0 = 0; q0 < c.call.Q; q0 += c.cp.sub_tiles * 64) {
@@ -990,6 +1030,7 @@ struct HostFlat {
     ugp::FlatMat f;
     std::vector<uint32_t> parent;   // copy of the caller's BFS parent array (extended searches need the topology)
     std::vector<uint32_t> coarse2dfs, coarse2bfs;
+    ugp::CoarseTables ctab;         // static tables of the coarse tree (the pre-pass without tiles), or unusable
     ugp::UVec<uint32_t> node_pair;   // full tree, for the seed descent (empty: input not in breadth-first order)
     bool wide_descent = false;       // more than 5 % of the nodes hang off a node with more than 16 children
     HostFlat *coarse = nullptr;
@@ -1066,6 +1107,11 @@ static int build_coarse(const ugp_tree_desc *t, const ugp::Options &opt, ugp::Fl
     hf.coarse2dfs.resize(keep.size());
     for (size_t k = 0; k < keep.size(); k++) hf.coarse2dfs[k] = ex.dfsidx[keep[k]];
     hf.coarse2bfs = keep;
+    {
+        const auto &cf = hf.coarse->f;
+        ugp::build_coarse_tables(keep.size(), parent.data(), mut_off.data(), pos.data(), ref.data(), nuc.data(), cf.dfs2bfs.data(), cf.pos2site.data(), cf.max_pos,
+                                 cf.n_sites, hf.ctab);
+    }
     return UGP_OK;
 }
 
@@ -1177,6 +1223,12 @@ static int upload_flat(const HostFlat &hf, int device, ugp_mat **out) {
         // (always: the seeds of a search that leaves one node out per sample compare the coarse winner with that node, k_seed_ub --
         // also on a tree that is not numbered breadth-first, where the descent below does not run)
         if ((e = m->d_coarse2bfs.upload(hf.coarse2bfs)) != hipSuccess) return bail(e, "upload coarse table");
+        if (hf.ctab.usable() && hf.ctab.n_nodes == hf.coarse->f.n_nodes) {
+            if ((e = m->d_cs_node.upload(hf.ctab.node)) != hipSuccess || (e = m->d_cs_rmq.upload(hf.ctab.rmq)) != hipSuccess ||
+                (e = m->d_cs_site_off.upload(hf.ctab.site_off)) != hipSuccess || (e = m->d_cs_events.upload(hf.ctab.events)) != hipSuccess)
+                return bail(e, "upload coarse table");
+            m->cs_nodes = hf.ctab.n_nodes; m->cs_max_per_pos = hf.ctab.max_per_pos;
+        }
         if (!hf.node_pair.empty()) {
             m->wide_descent = getenv("UGP_DESCENT_LANES") ? atoi(getenv("UGP_DESCENT_LANES")) > 16 : hf.wide_descent;
         }
@@ -1282,6 +1334,8 @@ template <class IO> void flat_io(IO &io, HostFlat &hf) {
     io.vec(f.stream_t); io.vec(f.chunk_t_off); io.vec(f.rank_dfs); io.vec(f.node_pos8); io.vec(f.hdr8_of_bfs); io.vec(f.rec_of_bfs); io.vec(f.post_of_bfs);
     io.vec(f.b3_group_off); io.vec(f.b3_events);
     io.vec(hf.parent); io.vec(hf.coarse2dfs); io.vec(hf.coarse2bfs); io.vec(hf.node_pair); io.pod(hf.wide_descent);
+    io.pod(hf.ctab.n_nodes); io.pod(hf.ctab.max_per_pos);
+    io.vec(hf.ctab.node); io.vec(hf.ctab.rmq); io.vec(hf.ctab.site_off); io.vec(hf.ctab.events);
 }
 }  // namespace
 extern "C" {
@@ -1337,6 +1391,8 @@ int ugp_mat_create_from_flat(const char *path, int device, ugp_mat **out) {
                 return fail(UGP_ERR_INVALID, "inconsistent flattening file (array sizes)");
             for (int32_t v : g.pos2site) if (v >= (int64_t)g.n_sites) return fail(UGP_ERR_INVALID, "inconsistent flattening file (site index out of range)");
         }
+        if (hf.ctab.n_nodes && (!hf.coarse || !ugp::coarse_tables_consistent(hf.ctab, hf.coarse->f.n_nodes, hf.coarse->f.n_sites)))
+            return fail(UGP_ERR_INVALID, "inconsistent flattening file (coarse tables)");
         return upload_flat(hf, device, out);
     } catch (const std::bad_alloc &) { return fail(UGP_ERR_NOMEM, "out of host memory"); }
 }
@@ -2134,6 +2190,7 @@ int mask_words(ugp_mat *m, const uint8_t *d_mask, bool set) {
         HIP_TRY(ugp::launch_mask_words(d_mask, t == m ? nullptr : m->d_coarse2bfs.p, (uint32_t)t->flat.n_nodes, U.d_hdr8.p, U.d_rec_pos.p, U.d_post.p,
                                        t->d_stream8.p, t->d_stream.p, t->d_stream_t.p, ugp::H_NOSCORE, set, nullptr));
     }
+    m->mask_in_force = set;
     return UGP_OK;
 }
 }  // namespace
@@ -2691,6 +2748,45 @@ int ugp_debug_bound3_tables(ugp_mat *m, uint32_t tile, uint16_t *over, uint16_t 
     for (size_t i = 0; i < nb; i++) under[i] = tmp[i];
     return UGP_OK;
 }
+
+// Test hook: only the pre-pass of a batch, by the method the caller names (0: the walk of the coarse tree, 1: k_coarse_sparse, refused
+// where the plan would not take it), blocking.  Per sample the cost and the coarse node (an index into the kept nodes); kept_bfs, if
+// given, receives the kept nodes' BFS indices in the full tree.
+int ugp_debug_coarse_pass(ugp_mat *m, ugp_qset *qs, int method, int32_t *cost, uint32_t *coarse_node, uint32_t *kept_bfs, uint64_t kept_cap, uint64_t *n_kept) {
+    if (!m || !qs || !n_kept || (qs->n_queries && (!cost || !coarse_node))) return fail(UGP_ERR_INVALID, "null argument");
+    if (!m->coarse) return fail(UGP_ERR_UNSUPPORTED, "this handle has no coarse tree");
+    if (method != 0 && method != 1) return fail(UGP_ERR_INVALID, "method must be 0 (walked) or 1 (sparse)");
+    HIP_TRY(hipSetDevice(m->device));
+    *n_kept = m->upd.coarse2bfs.size();
+    if (kept_bfs) {
+        if (kept_cap < *n_kept) return fail(UGP_ERR_INVALID, "buffer too small");
+        std::copy(m->upd.coarse2bfs.begin(), m->upd.coarse2bfs.end(), kept_bfs);
+    }
+    if (!qs->n_queries) return UGP_OK;
+    if (int rc = drain(m)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    PlaceReq r;   // (a plain call of this set, to ask the plan with)
+    const ugp::PlanTree tree = plan_tree(m);
+    ugp::PlanCall call = plan_call_facts(m, qs, r);
+    call.Q = std::max<uint64_t>(call.Q, 513);   // (the pre-pass of any batch: the plan sorts from 513 samples on)
+    const ugp::CallPlan cp = ugp::plan_call(tree, m->knobs, call);
+    ugp_mat::Work &W = m->work[0];
+    HIP_TRY(W.d_coarse_res.reserve(qs->n_queries));
+    if (method == 1) {
+        if (!cp.coarse_sparse) return fail(UGP_ERR_UNSUPPORTED, "the plan does not take the sparse pre-pass for this batch");
+        if (int rc = coarse_sparse(m, qs, cp.coarse_cap, W.d_coarse_res.p, nullptr)) return rc;
+    } else {
+        if (int rc = coarse_walked(m, qs, W.d_coarse_res.p, nullptr, 0)) return rc;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<ugp_result> res(qs->n_queries);
+    HIP_TRY(hipMemcpy(res.data(), W.d_coarse_res.p, res.size() * sizeof(ugp_result), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < res.size(); i++) { cost[i] = res[i].best_set_difference; coarse_node[i] = res[i].best_j; }
+    return UGP_OK;
+}
+
+// Test hook: which pre-pass the handle's latest placement call took (0: none, 1: the walk of the coarse tree, 2: k_coarse_sparse).
+int ugp_debug_last_prepass(const ugp_mat *m) { return m ? m->last_prepass : 0; }
 
 int ugp_get_timing_sum(ugp_mat *m, ugp_timing *sum, uint32_t *n_calls) {
     if (!m || !sum || !n_calls) return fail(UGP_ERR_INVALID, "null argument");

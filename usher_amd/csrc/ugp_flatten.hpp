@@ -144,7 +144,7 @@ constexpr uint32_t MAX_SITES = 1u << 22;
 // Version of everything flatten() produces (stream encodings, record fields, event lists): BUMP IT with every change of a layout.
 // ugp_flat_save stamps its files with it (next to the flattening switches), ugp_mat_create_from_flat refuses any other -- a build
 // time stamp of one translation unit cannot see a change made in another.  6: events listed under their own word's block.
-constexpr uint32_t FLAT_FORMAT_VERSION = 6;
+constexpr uint32_t FLAT_FORMAT_VERSION = 7;
 constexpr uint32_t MAX_NODE_MUTS = 65534;   // 0xFFFF marks a pruning pseudo-record of the tie stream
 
 struct Options {

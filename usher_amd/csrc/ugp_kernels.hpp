@@ -97,6 +97,21 @@ constexpr uint32_t GBEST_SLICES = 64;   // chunk-axis slices of the global-minim
 hipError_t launch_coarse_result(const uint32_t *lbest, const uint32_t *lpos, const uint32_t *list, const uint32_t *list_n, uint32_t n_chunks, uint32_t n_tiles512,
                                 uint32_t n_queries, const uint32_t *chunk_node_off, const uint32_t *chunk8_body_off, const uint32_t *node_pos8,
                                 const uint32_t *dfs2bfs, ugp_result *out, hipStream_t s);
+// The pre-pass without tiles (ugp_coarse.hip, ugp_coarse.hpp): the samples' own CSR rows, the coarse tree's static tables
+struct CoarseSparseArgs {
+    const uint64_t *ent_off; const int32_t *pos; const uint8_t *ref, *nuc, *is_missing;   // the query set
+    const unsigned long long *err;     // the set's row check (or null): anything but ~0 = placed as if it had no rows
+    const int32_t *pos2site;           // of the coarse tree
+    uint32_t max_pos, n_nodes, n_queries;
+    uint64_t n_ent, max_rows;          // of the set; n_ent == 0: no row array is read (a set without rows has none, or stale ones)
+    uint32_t max_per_pos;              // the largest number of events at one position
+    uint32_t cap;                      // boundary records of LDS per sample: a power of two >= 2 * max_rows * (events per position)
+    const uint32_t *site_off; const uint2 *events; const uint2 *node; const uint32_t *rmq;
+    const uint32_t *dfs2bfs;           // depth-first position -> coarse BFS index
+    ugp_result *out;
+};
+size_t coarse_sparse_lds_bytes(uint32_t cap);
+hipError_t launch_coarse_sparse(const CoarseSparseArgs &a, hipStream_t s);
 hipError_t launch_phase2_packed(const Best8Args &b1, const uint32_t *list, const uint32_t *list_n, uint32_t *gbest_part, uint32_t *gbest, uint32_t n_tiles512,
                                 void *units, uint32_t *info, uint32_t *cnt, uint32_t *key, const uint32_t *node_pos8, const uint32_t *rank_dfs,
                                 const uint32_t *chunk_node_off, const uint32_t *rank2bfs, uint32_t n_queries, ugp_result *out, const uint32_t *order,

@@ -8,6 +8,7 @@
 
 #include <algorithm>
 
+#include "ugp_coarse.hpp"
 #include "ugp_flatten.hpp"
 #include "ugp_knobs.hpp"
 #include "ugp_tuner.hpp"
@@ -24,6 +25,11 @@ struct PlanTree {   // the tree and its handle
     bool coarse = false;         // the handle has a coarse tree (locality sort)
     bool b3_events = false;      // ... and the third bound's posting lists
     bool wide_descent = false;
+    // the pre-pass from the samples' own rows (ugp_coarse.hpp): the coarse tree's static tables, and what rules them out
+    uint64_t coarse_nodes = 0;            // nodes of the coarse tree the tables were built for (0: no tables)
+    uint32_t coarse_max_per_pos = 0;      // the largest number of coarse mutations at one position
+    bool coarse_excluded = false;         // ugp_mat_update has taken a node out of the candidate set
+    bool coarse_masked = false;           // a node mask is in force on the streams (ugp_place_batch_ex)
 };
 struct PlanEx {   // which options an extended search carries (ExDev, ugp_capi.cpp)
     bool given = false, packed = false, mask = false, skip = false, skip_chunk = false, scores = false;
@@ -43,6 +49,8 @@ struct PlanCall {   // the query set and the call
 struct CallPlan {
     uint32_t n_sites = 1, active_words = 1, useful_words = 1;
     bool ex_packable = false, ex_skip = false, packed_ok = false, sorted = false, can_fork = false, fill_ahead = false;
+    bool coarse_sparse = false;           // the pre-pass runs as k_coarse_sparse, not as a walk of the coarse tree
+    uint32_t coarse_cap = 0;              // ... with this many boundary records of LDS per sample
     uint64_t sub_tiles = kMaxTilesPerLaunch;
 };
 
@@ -66,6 +74,14 @@ inline CallPlan plan_call(const PlanTree &t, const Knobs &K, const PlanCall &c) 
     // 16-bit packed phase 1 is exact while every D / cost stays below 0x8000 (bit 15 is the ineligible flag)
     p.packed_ok = (c.mode == 0) && (!c.ex.given || p.ex_packable) && !K.force_v1 && !t.mask_not_first && (c.max_rows + t.max_path_muts + 2 < 0x7F7Full);
     p.sorted = p.packed_ok && t.coarse && c.Q > 512 && !K.no_sort && !K.no_prune;
+    // The pre-pass without tiles: a sorted call of the plain search (or of an extended one that only leaves a node out per sample --
+    // the pre-pass never looks at it), on a coarse tree that is what its static tables describe -- no node excluded since, no mask on
+    // the streams --, whose positions fit 16 bits, and whose samples' events fit the LDS of a lane group: a row meets at most
+    // coarse_max_per_pos events, each two boundary records.  UGP_COARSE_PHASE2=1 keeps the walked pass.
+    p.coarse_sparse = p.sorted && (!c.ex.given || (c.ex.packed && !c.ex.mask && !c.ex.scores)) && !K.coarse_phase2 && t.coarse_nodes != 0 &&
+                      t.coarse_nodes <= kCoarseSparseMaxNodes && !t.coarse_excluded && !t.coarse_masked &&
+                      c.max_rows * (uint64_t)t.coarse_max_per_pos <= kCoarseSparseMaxEvents;
+    if (p.coarse_sparse) for (p.coarse_cap = 32; p.coarse_cap < 2 * c.max_rows * (uint64_t)t.coarse_max_per_pos; p.coarse_cap *= 2) {}
     // The side stream (see Work::aux): only where there is something to put on it -- the sorted main pass.
     // And only for a call that has the device to itself: measured with three calls in flight (six queues instead of three), the
     // cross-queue waits cost far more than the overlap gives -- 12.9 -> 10.4 M placements/s; a lone call gains 45 us of its 1.96 ms.

@@ -638,6 +638,19 @@ class Placer:
     def free_qset(self, h) -> None:
         self._L.ugp_qset_destroy(h)
 
+    def coarse_pass(self, qset, method: str):
+        """ugp_debug_coarse_pass (test hook): only the locality pre-pass of an uploaded batch, by method "walked" or "sparse" (UgpError
+        where a call would not take the sparse one).  Returns (cost [Q], coarse node [Q], BFS indices of the coarse tree's nodes)."""
+        Q = int(self._L.ugp_qset_size(qset))
+        cost = np.zeros(Q, np.int32); node = np.zeros(Q, np.uint32); kept = np.zeros(self.n_nodes, np.uint32)
+        n = C.c_uint64()
+        self._ck(self._L.ugp_debug_coarse_pass(self._h, qset, {"walked": 0, "sparse": 1}[method], _ptr(cost), _ptr(node), _ptr(kept), len(kept), C.byref(n)))
+        return cost, node, kept[:int(n.value)].copy()
+
+    def last_prepass(self) -> str:
+        """ugp_debug_last_prepass (test hook): the pre-pass the latest placement call took."""
+        return ("none", "walked", "sparse")[int(self._L.ugp_debug_last_prepass(self._h))]
+
     def place_device(self, qset, d_out_ptr: int, stream: int = 0) -> None:
         """ugp_place_device: stream-ordered on `stream`, like a kernel launch."""
         self._ck(self._L.ugp_place_device(self._h, qset, C.c_void_p(d_out_ptr), C.c_void_p(stream)))
