@@ -405,6 +405,44 @@ int ugp_translate_chunked(ugp_mat *mat, ugp_tr_record *out, uint64_t cap, uint64
 /* Bench hook: milliseconds of device time of the passes of ugp_translate alone (records, scan, compaction over every window; no copy to
  * the host); mean of `reps` runs. */
 int ugp_translate_time(ugp_mat *mat, uint32_t reps, double *ms);
+/* matUtils extract --closest-relatives / --within-distance (get_closest_samples, matUtils/select.cpp:577-714) for a batch of samples.
+ * ugp_relatives_attach shares the depth-first tables of `tree` (the handle's tree; arrays are copied; tables built from other mutation
+ * arrays: UGP_ERR_INVALID, nothing changed) and builds, once per handle, the leaves in depth-first order with a range minimum over
+ * their cum (blocks of UGP_REL_BLOCK leaves), the leaves ordered by (cum, depth-first rank) and, when name_rank is given, a range
+ * minimum over the name ranks in that order.  name_rank [n] by BFS index is a permutation of 0 .. n - 1: the order of the
+ * identifiers under std::string::operator< (unsigned bytes); NULL: no ranks.  A second attach replaces the first.
+ * With cum[v] the mutation entries on the root path of v (v and masked entries included), nm[v] those on v itself, t the sample,
+ * p_0 = parent(t), p_1, ... its ancestors, c_0 = t and c_j = p_{j-1}: the RING of level j is the leaves of subtree(p_j) outside
+ * subtree(c_j); a ring leaf l is d(l) = cum[t] + cum[l] - 2 cum[p_j] away; the level bound is L_j = cum[p_0] - cum[p_j] + nm[p_j].
+ * ugp_relatives_closest (fixed_k = false): levels 0, 1, ... in order; m_j = the smallest d of the ring (an empty ring has none); a
+ *   strictly smaller m_j replaces the list, an equal one appends; the climb stops after the first level with m_j < L_j, or after
+ *   the root's.  The list is, level by level, the ring leaves at the final distance in depth-first order.
+ * ugp_relatives_within (fixed_k = true): the ring leaves with d <= threshold, level by level, each level in depth-first order; the
+ *   climb stops after the first level with L_j > threshold, or after the root's.
+ * Two quirks of the reference are kept: L_j leaves out nm[t], and dist is 0 when there are no relatives.  The root has none.
+ * Sample i is a node (BFS index; any node).  info[i]: count = the length of its list, levels = the levels processed, dist = the
+ * final distance (closest mode; 0 in within mode), best = the BFS index of the relative with the smallest name rank among the
+ * closest (UINT32_MAX without relatives, without ranks, and in within mode).  out_off NULL: no lists (out_nodes and cap are
+ * ignored).  Else list i is out_nodes[out_off[i] .. out_off[i + 1]) (BFS indices); out_off [n + 1] is always complete,
+ * out_nodes[0 .. min(cap, *n_out)) is written and *n_out is the true total in either case.  An out-of-range node or a call before
+ * the attach is UGP_ERR_INVALID before anything is written.  Samples run in chunks of bounded device workspace; the _chunked
+ * twins (test hooks) set the samples per chunk (0: default) and with them the list entries per window (16 per sample). */
+#define UGP_REL_BLOCK 16
+typedef struct ugp_rel_info { uint32_t dist, count, levels, best; } ugp_rel_info;
+int ugp_relatives_attach(ugp_mat *mat, const ugp_tree_desc *tree, const uint32_t *name_rank /* [n] by BFS index, or NULL */);
+int ugp_relatives_closest(ugp_mat *mat, uint64_t n, const uint32_t *nodes /* BFS, any node */, ugp_rel_info *info /* [n] */,
+                          uint64_t *out_off /* [n + 1], or NULL: no lists */, uint32_t *out_nodes, uint64_t cap, uint64_t *n_out);
+int ugp_relatives_within(ugp_mat *mat, uint64_t n, const uint32_t *nodes, uint32_t threshold, ugp_rel_info *info,
+                         uint64_t *out_off, uint32_t *out_nodes, uint64_t cap, uint64_t *n_out);
+int ugp_relatives_closest_chunked(ugp_mat *mat, uint64_t n, const uint32_t *nodes, ugp_rel_info *info, uint64_t *out_off,
+                                  uint32_t *out_nodes, uint64_t cap, uint64_t *n_out, uint32_t chunk_samples);
+int ugp_relatives_within_chunked(ugp_mat *mat, uint64_t n, const uint32_t *nodes, uint32_t threshold, ugp_rel_info *info,
+                                 uint64_t *out_off, uint32_t *out_nodes, uint64_t cap, uint64_t *n_out, uint32_t chunk_samples);
+/* Bench hook: milliseconds of device time of the kernels alone over these samples -- count_ms the climb with its counts and the prefix
+ * sum, fill_ms the second climb that writes the lists (they stay on the device) -- mean of `reps` runs after one warm-up run.
+ * within = 0: closest mode (threshold ignored). */
+int ugp_relatives_time(ugp_mat *mat, uint64_t n, const uint32_t *nodes, int within, uint32_t threshold, uint32_t reps, double *count_ms,
+                       double *fill_ms);
 /* RIPPLES (ripples/main.cpp): the options of :22-44 that the search reads. branch_len >= 1 and parsimony_improvement >= 0
  * (UGP_ERR_INVALID otherwise: the reference's size_t arithmetic of :445-453 is not reproduced for negative values). */
 typedef struct ugp_ripples_opts {

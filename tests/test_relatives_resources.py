@@ -1,0 +1,33 @@
+"""The kernels of ugp_relatives.hip do not spill, use no scratch and hold exactly the LDS they declare (the per-wave sums of the two
+scans), read from the compiler's own resource report; the list of the file's own kernels is complete.  The device radix sort's
+kernels (rocprim, instantiated in this file) are the library's code: they are held to no register spills; its onesweep kernel
+keeps a private digit array of a few dozen bytes in scratch by design, which is no spill."""
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "usher_amd", "csrc")
+LDS = {"k_rel_closest": 0, "k_rel_within": 0, "k_rel_scan": 4 * 8, "k_rel_fillILb0": 0, "k_rel_fillILb1": 0, "k_rel_lpre": 4 * 4,
+       "k_rel_leaves": 0, "k_rel_boff": 0, "k_rel_sorted": 0, "k_rel_invert": 0, "k_rel_rmq_blocks": 0, "k_rel_rmq_level": 0}
+
+
+def test_relatives_kernels_do_not_spill(tmp_path):
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-structurizecfg-skip-uniform-regions=1",
+                        "-I" + os.path.join(ROOT, "include"), "-x", "hip", "-c", os.path.join(CSRC, "ugp_relatives.hip"), "--cuda-device-only",
+                        "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "a.o")], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    seen = {}
+    for b in re.split(r"remark: Function Name: ", r.stderr)[1:]:
+        seen[b.split()[0]] = {k: int(v) for k, v in re.findall(r"remark:\s+([A-Za-z ]+?)(?: \[[a-z/]+\])?: (\d+)", b)}
+    own = {name: v for name, v in seen.items() if "k_rel_" in name}
+    for kernel, lds in LDS.items():
+        hits = [v for name, v in own.items() if re.search(kernel + r"(?![a-z_])", name)]
+        assert len(hits) == 1, (kernel, list(own))
+        assert hits[0]["LDS Size"] == lds, (kernel, hits[0])
+    assert len(own) == len(LDS), list(own)
+    assert len(seen) > len(own), "the radix sort's kernels are missing from the report"
+    for name, v in seen.items():
+        assert v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0, (name, v)
+        assert v["ScratchSize"] == 0 or name not in own, (name, v)

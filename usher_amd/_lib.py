@@ -106,6 +106,12 @@ SYMBOLS = {
     "ugp_translate": (C.c_int, [P, P, C.c_uint64, C.POINTER(C.c_uint64), P]),
     "ugp_translate_chunked": (C.c_int, [P, P, C.c_uint64, C.POINTER(C.c_uint64), P, C.c_uint64]),
     "ugp_translate_time": (C.c_int, [P, C.c_uint32, P]),
+    "ugp_relatives_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc), P]),
+    "ugp_relatives_closest": (C.c_int, [P, C.c_uint64, P, P, P, P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ugp_relatives_within": (C.c_int, [P, C.c_uint64, P, C.c_uint32, P, P, P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ugp_relatives_closest_chunked": (C.c_int, [P, C.c_uint64, P, P, P, P, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32]),
+    "ugp_relatives_within_chunked": (C.c_int, [P, C.c_uint64, P, C.c_uint32, P, P, P, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32]),
+    "ugp_relatives_time": (C.c_int, [P, C.c_uint64, P, C.c_int, C.c_uint32, C.c_uint32, P, P]),
     "ugp_ripples_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc), P]),
     "ugp_ripples": (C.c_int, [P, C.POINTER(ugp_ripples_opts), P, C.c_uint64, P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ugp_subtree_mask": (C.c_int, [P, C.c_uint32, C.c_uint32, C.c_uint32, P]),

@@ -6,6 +6,7 @@
 //                        [--host-genotypes]
 //   matutils-amd summarize -i tree.pb [-s -c -C -m -a -R file ...] [-A] [-M] [-d dir] [--host]
 //   matutils-amd translate -i tree.pb -g genes.gtf -f ref.fa -t out.tsv [-d dir] [--host]
+//   matutils-amd relatives -i tree.pb [-s samples.txt] [-V closest.tsv [-q]] [--within-distance within.tsv [--distance-threshold n]] [--host]
 //
 // uncertainty_main / findEPPs_wrapper (uncertainty.cpp:279-339, 541-560): load the MAT, uncondense its leaves, read the sample
 // names, and for every sample report its equally parsimonious placements and neighborhood size (-e) and the candidate parents
@@ -20,6 +21,9 @@
 // summary --translate (translate.cpp: translate_main, do_mutations), as the subcommand `translate`: per node the amino-acid, nucleotide
 // and codon changes and the leaves below it.  The codon letters come from ugp_translate.hip; a tree whose stored parent alleles
 // disagree with the states above them (every mutated - strand gene), or --host, takes the reference's serial do / undo walk.
+// extract --closest-relatives / --within-distance (extract.cpp:768-823), as the subcommand `relatives`: per sample its closest
+// leaves, or those within a distance (get_closest_samples, select.cpp:577-714).  The lists come from ugp_relatives.hip; --host
+// runs the reference's walk statement by statement.  `extract` itself goes on refusing the four options.
 #include <hip/hip_runtime_api.h>
 #include <sys/stat.h>
 #include <zlib.h>
@@ -55,7 +59,8 @@ void usage(FILE *f) {
             "  -T, --threads            accepted for compatibility (the searches run on the device)\n"
             "      --device             HIP device ordinal [0]\n"
             "  (-d / --dropout-mutations is not supported)\n"
-            "       matutils-amd annotate --help | matutils-amd extract --help | matutils-amd summarize --help | matutils-amd translate --help\n");
+            "       matutils-amd annotate --help | matutils-amd extract --help | matutils-amd summarize --help | matutils-amd translate --help\n"
+            "       matutils-amd relatives --help\n");
 }
 
 int uncertainty(int argc, char **argv) {
@@ -2182,6 +2187,301 @@ int translate(int argc, char **argv) {   // summary_main's --translate branch (s
     return 0;
 }
 
+// ---- relatives (extract --closest-relatives / --within-distance: extract.cpp:768-823, select.cpp:577-714) -------------
+
+void relatives_usage(FILE *f) {
+    fprintf(f,
+            "Usage: matutils-amd relatives -i tree.pb [-s samples.txt] [-V closest.tsv [-q]] [--within-distance within.tsv\n"
+            "       [--distance-threshold n]] [-d dir] [-T n] [--device k] [--host]\n"
+            "  -i, --input-mat          input mutation-annotated tree (.pb / .pb.gz) [REQUIRED]\n"
+            "  -s, --samples            text file of sample ids, one per line [every leaf of the tree]\n"
+            "  -V, --closest-relatives  tsv of each sample's closest relative(s) and their distance\n"
+            "  -q, --break-ties         one closest relative per sample: the smallest name\n"
+            "      --within-distance    tsv of each sample's relatives within the distance threshold\n"
+            "      --distance-threshold the threshold of --within-distance [0]\n"
+            "  -d, --output-directory   directory of the output files [./]\n"
+            "  -T, --threads            accepted for compatibility (the searches run on the device)\n"
+            "      --device             HIP device ordinal [0]\n"
+            "      --host               the reference's serial walk on the host (slow; no device)\n");
+}
+
+// closest_samples_dfs, select.cpp:577-594
+void rel_dfs(const uh::Node *node, size_t path_length, size_t max_path_length, std::vector<std::pair<const uh::Node *, size_t>> &leaves, bool fixed_k) {
+    if (path_length > max_path_length) return;
+    for (const uh::Node *child : node->children) {
+        if (child->is_leaf()) {
+            if (fixed_k && path_length + child->mutations.size() <= max_path_length) leaves.push_back(std::make_pair(child, path_length + child->mutations.size()));
+            else if (!fixed_k) leaves.push_back(std::make_pair(child, path_length + child->mutations.size()));
+        } else {
+            rel_dfs(child, path_length + child->mutations.size(), max_path_length, leaves, fixed_k);
+        }
+    }
+}
+
+// get_closest_samples, select.cpp:596-714, statement by statement (identifiers are unique: nodes are compared by address).
+std::pair<std::vector<const uh::Node *>, size_t> host_closest_samples(const uh::Node *target, bool fixed_k, size_t k) {
+    std::pair<std::vector<const uh::Node *>, size_t> closest_samples;
+    closest_samples.second = 0;
+    const uh::Node *target_parent = target->parent;
+    const uh::Node *curr_target = target;
+    const uh::Node *parent = target->parent;
+    size_t min_dist = std::numeric_limits<size_t>::max();
+    size_t dist_to_orig_parent = 0;
+    bool go_up = true;
+    while (go_up && parent) {
+        const size_t parent_branch_length = parent->mutations.size() + dist_to_orig_parent;
+        std::vector<std::pair<const uh::Node *, size_t>> children_and_distances, children_and_distances_fixed_k;
+        size_t min_of_sibling_leaves = std::numeric_limits<size_t>::max();
+        for (const uh::Node *child : parent->children) {
+            if (child->is_leaf()) {
+                if (child == curr_target) continue;
+                const size_t child_branch_length = child->mutations.size();
+                if (child_branch_length < min_of_sibling_leaves) min_of_sibling_leaves = child_branch_length;
+            }
+        }
+        for (const uh::Node *child : parent->children) {
+            if (child == curr_target) continue;
+            if (child == target_parent) continue;
+            const size_t dist_so_far = dist_to_orig_parent + target->mutations.size() + child->mutations.size();
+            if (!child->is_leaf()) {
+                if (fixed_k) {
+                    rel_dfs(child, dist_so_far, k, children_and_distances_fixed_k, true);
+                } else {
+                    size_t max_path;
+                    if (min_of_sibling_leaves == std::numeric_limits<size_t>::max()) max_path = min_of_sibling_leaves;
+                    else max_path = min_of_sibling_leaves + dist_so_far;
+                    rel_dfs(child, dist_so_far, max_path, children_and_distances, false);
+                }
+            } else {
+                if (fixed_k && dist_so_far <= k) children_and_distances_fixed_k.push_back(std::make_pair(child, dist_so_far));
+                else if (!fixed_k) children_and_distances.push_back(std::make_pair(child, dist_so_far));
+            }
+        }
+        if (fixed_k) {
+            if (parent_branch_length > k) go_up = false;
+            for (const auto &child_and_dist : children_and_distances_fixed_k) {
+                closest_samples.first.push_back(child_and_dist.first);
+                closest_samples.second = 0;
+            }
+        } else {
+            for (const auto &child_and_dist : children_and_distances) {
+                const size_t child_branch_length = child_and_dist.second;
+                if (child_branch_length < parent_branch_length) go_up = false;
+                if (child_branch_length < min_dist) {
+                    min_dist = child_branch_length;
+                    closest_samples.first.clear();
+                    closest_samples.first.push_back(child_and_dist.first);
+                    closest_samples.second = min_dist;
+                } else if (child_branch_length == min_dist) {
+                    closest_samples.first.push_back(child_and_dist.first);
+                }
+            }
+        }
+        curr_target = parent;
+        parent = curr_target->parent;
+        dist_to_orig_parent = parent_branch_length;
+    }
+    return closest_samples;
+}
+
+// One line of the closest-relatives file (extract.cpp:782-803); nothing for a sample without relatives.
+void rel_closest_line(std::string &out, const std::string &sample, const std::vector<const uh::Node *> &rel, const uh::Node *smallest, size_t dist,
+                      bool break_ties) {
+    if (rel.empty() && !smallest) return;
+    out += sample; out += '\t';
+    if (break_ties) out += smallest->id;
+    else for (size_t i = 0; i < rel.size(); i++) { if (i) out += ','; out += rel[i]->id; }
+    out += '\t'; out += std::to_string(dist); out += '\n';
+}
+
+// One line of the within-distance file (:811-821): the substr drops the tab of a sample without relatives.
+void rel_within_line(std::string &out, const std::string &sample, const std::vector<const uh::Node *> &rel) {
+    out += sample;
+    for (size_t i = 0; i < rel.size(); i++) { out += i ? ',' : '\t'; out += rel[i]->id; }
+    out += '\n';
+}
+
+struct RelativesJob {
+    std::vector<std::string> names;          // the samples, in output order
+    std::vector<const uh::Node *> nodes;
+    std::string closest_path, within_path;
+    bool break_ties = false;
+    size_t threshold = 0;
+};
+
+bool rel_flush(std::ofstream &f, std::string &out, bool force) {
+    if (force || out.size() > (1u << 20)) { f << out; out.clear(); }
+    return (bool)f;
+}
+
+int host_relatives(const RelativesJob &J) {
+    std::string out;
+    if (!J.closest_path.empty()) {
+        std::ofstream f(J.closest_path, std::ios::binary);
+        for (size_t i = 0; i < J.nodes.size(); i++) {
+            const auto r = host_closest_samples(J.nodes[i], false, 0);
+            const uh::Node *smallest = nullptr;
+            if (J.break_ties)
+                for (const uh::Node *n : r.first) if (!smallest || n->id < smallest->id) smallest = n;
+            rel_closest_line(out, J.names[i], r.first, smallest, r.second, J.break_ties);
+            rel_flush(f, out, false);
+        }
+        if (!rel_flush(f, out, true)) { fprintf(stderr, "ERROR: could not write %s\n", J.closest_path.c_str()); return 1; }
+    }
+    if (!J.within_path.empty()) {
+        std::ofstream f(J.within_path, std::ios::binary);
+        for (size_t i = 0; i < J.nodes.size(); i++) {
+            rel_within_line(out, J.names[i], host_closest_samples(J.nodes[i], true, J.threshold).first);
+            rel_flush(f, out, false);
+        }
+        if (!rel_flush(f, out, true)) { fprintf(stderr, "ERROR: could not write %s\n", J.within_path.c_str()); return 1; }
+    }
+    return 0;
+}
+
+// The device path: ugp_relatives_closest / ugp_relatives_within in batches of samples, formatted to the same bytes.
+int device_relatives(uh::Tree &T, const RelativesJob &J, int device) {
+    const std::vector<uh::Node *> bfs = T.bfs();
+    const uint64_t N = bfs.size();
+    for (uint64_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
+    std::vector<uint32_t> parent(N);
+    std::vector<uint64_t> mut_off(N + 1, 0);
+    std::vector<int32_t> pos;
+    std::vector<uint8_t> ref, par, nuc;
+    for (uint64_t j = 0; j < N; j++) {
+        parent[j] = bfs[j]->parent ? bfs[j]->parent->flat_index : UINT32_MAX;
+        for (const auto &m : bfs[j]->mutations) {
+            pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
+        }
+        mut_off[j + 1] = pos.size();
+    }
+    const std::vector<uint64_t> no_off(N + 1, 0);
+    if (pos.empty()) { pos.push_back(0); ref.push_back(0); par.push_back(0); nuc.push_back(0); }   // (never read: no null arrays)
+    // the handle carries the topology only: the relatives tables count entries, whatever they hold
+    const ugp_tree_desc bare{N, parent.data(), no_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+    const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+    struct Handle { ugp_mat *h = nullptr; ~Handle() { if (h) ugp_mat_destroy(h); } } H;
+    if (ugp_mat_create(&bare, device, &H.h) != UGP_OK) lib_fail("ugp_mat_create");
+    std::vector<uint32_t> rank;
+    if (J.break_ties && !J.closest_path.empty()) {   // std::string::operator<
+        std::vector<uint32_t> order(N);
+        for (uint64_t j = 0; j < N; j++) order[j] = (uint32_t)j;
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return bfs[a]->id != bfs[b]->id ? bfs[a]->id < bfs[b]->id : a < b; });
+        rank.resize(N);
+        for (uint64_t r = 0; r < N; r++) rank[order[r]] = (uint32_t)r;
+    }
+    if (ugp_relatives_attach(H.h, &desc, rank.empty() ? nullptr : rank.data()) != UGP_OK) lib_fail("ugp_relatives_attach");
+    const size_t n = J.nodes.size(), per = size_t(1) << 16;   // samples per call: the lists of one call are held at once
+    std::vector<uint32_t> qn(n), lists;
+    for (size_t i = 0; i < n; i++) qn[i] = J.nodes[i]->flat_index;
+    std::vector<ugp_rel_info> info(per);
+    std::vector<uint64_t> off(per + 1);
+    std::vector<const uh::Node *> rel;
+    std::string out;
+    for (int within = 0; within < 2; within++) {
+        const std::string &path = within ? J.within_path : J.closest_path;
+        if (path.empty()) continue;
+        const bool want_lists = within || !J.break_ties;
+        std::ofstream f(path, std::ios::binary);
+        for (size_t i0 = 0; i0 < n; i0 += per) {
+            const size_t m = std::min(per, n - i0);
+            uint64_t total = 0;
+            for (int attempt = 0; attempt < 2; attempt++) {   // the second call has room for the total the first reported
+                const int rc = within ? ugp_relatives_within(H.h, m, qn.data() + i0, (uint32_t)std::min<size_t>(J.threshold, UINT32_MAX), info.data(),
+                                                             want_lists ? off.data() : nullptr, lists.data(), lists.size(), &total)
+                                      : ugp_relatives_closest(H.h, m, qn.data() + i0, info.data(), want_lists ? off.data() : nullptr, lists.data(),
+                                                              lists.size(), &total);
+                if (rc != UGP_OK) lib_fail(within ? "ugp_relatives_within" : "ugp_relatives_closest");
+                if (!want_lists || total <= lists.size()) break;
+                lists.resize(total);
+            }
+            for (size_t i = 0; i < m; i++) {
+                rel.clear();
+                if (want_lists) for (uint64_t x = off[i]; x < off[i + 1]; x++) rel.push_back(bfs[lists[x]]);
+                if (within) rel_within_line(out, J.names[i0 + i], rel);
+                else rel_closest_line(out, J.names[i0 + i], rel, info[i].count && J.break_ties ? bfs[info[i].best] : nullptr, info[i].dist, J.break_ties);
+                rel_flush(f, out, false);
+            }
+        }
+        if (!rel_flush(f, out, true)) { fprintf(stderr, "ERROR: could not write %s\n", path.c_str()); return 1; }
+    }
+    return 0;
+}
+
+int relatives(int argc, char **argv) {
+    std::string mat, fsamples, fclosest, fwithin, dir = "./";
+    bool host = false, break_ties = false;
+    long threshold = 0;
+    int device = 0;
+    for (int i = 0; i < argc; i++) {
+        const std::string a = argv[i];
+        auto val = [&](std::string &dst) -> bool {
+            if (i + 1 >= argc) { fprintf(stderr, "ERROR: %s needs a value\n", a.c_str()); relatives_usage(stderr); return false; }
+            dst = argv[++i];
+            return true;
+        };
+        std::string tmp;
+        bool ok = true;
+        if (a == "-i" || a == "--input-mat") ok = val(mat);
+        else if (a == "-s" || a == "--samples") ok = val(fsamples);
+        else if (a == "-V" || a == "--closest-relatives") ok = val(fclosest);
+        else if (a == "-q" || a == "--break-ties") break_ties = true;
+        else if (a == "--within-distance") ok = val(fwithin);
+        else if (a == "--distance-threshold") {
+            ok = val(tmp);
+            char *end = nullptr;
+            threshold = strtol(tmp.c_str(), &end, 10);
+            if (ok && (tmp.empty() || *end || threshold < 0)) { fprintf(stderr, "ERROR: bad value %s for %s\n", tmp.c_str(), a.c_str()); relatives_usage(stderr); return 1; }
+        }
+        else if (a == "-d" || a == "--output-directory") ok = val(dir);
+        else if (a == "-T" || a == "--threads") ok = val(tmp);
+        else if (a == "--device") { ok = val(tmp); device = atoi(tmp.c_str()); }
+        else if (a == "--host") host = true;
+        else if (a == "-h" || a == "--help") { relatives_usage(stdout); return 0; }
+        else { fprintf(stderr, "ERROR: unknown option %s\n", a.c_str()); relatives_usage(stderr); return 1; }
+        if (!ok) return 1;
+    }
+    if (mat.empty()) { fprintf(stderr, "ERROR: the option '--input-mat' is required but missing\n"); relatives_usage(stderr); return 1; }
+    if (fclosest.empty() && fwithin.empty()) { fprintf(stderr, "ERROR: No output files requested!\n"); return 1; }
+    struct stat sb;
+    if (stat(dir.c_str(), &sb) != 0) {
+        fprintf(stderr, "Creating output directory.\n\n");
+        mkdir(dir.c_str(), 0777);
+    }
+    char *canon = realpath(dir.c_str(), nullptr);
+    if (!canon) { fprintf(stderr, "ERROR: cannot resolve the output directory %s\n", dir.c_str()); return 1; }
+    const std::string prefix = std::string(canon) + "/";
+    free(canon);
+    fprintf(stderr, "Loading input MAT file %s.\n", mat.c_str());
+    uh::Tree T;
+    std::string err;
+    if (!uh::load_mat(mat, T, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+    T.uncondense_leaves();
+    RelativesJob J;
+    if (!fsamples.empty()) {
+        J.names = read_sample_names(fsamples);
+        if (J.names.empty()) { fprintf(stderr, "ERROR: Sample file is empty or unparseable!"); return 1; }
+    } else {
+        J.names = leaf_ids(T);
+    }
+    for (const std::string &s : J.names) J.nodes.push_back(must_get(T, s));   // (the reference dereferences the null pointer)
+    if (!fclosest.empty()) J.closest_path = prefix + fclosest;
+    if (!fwithin.empty()) J.within_path = prefix + fwithin;
+    J.break_ties = break_ties;
+    J.threshold = (size_t)threshold;
+    if (!fclosest.empty()) {
+        fprintf(stderr, "Per-sample closest relative(s) requested. Computing...\n");
+        if (break_ties) fprintf(stderr, "Storing one closest relative per sample.\n");
+    }
+    if (!fwithin.empty()) fprintf(stderr, "Computing per-sample relatives within %ld mutations...\n", threshold);
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = host ? host_relatives(J) : device_relatives(T, J, device);
+    if (rc) return rc;
+    fprintf(stderr, "Relatives of %zu samples written in %.3f msec.\n\n", J.nodes.size(),
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -2192,6 +2492,7 @@ int main(int argc, char **argv) {
     // matUtils summary runs as `summarize`: the spelling `summary` stays refused, as it has been since the tool's first release
     if (!strcmp(argv[1], "summarize")) return summary(argc - 2, argv + 2);
     if (!strcmp(argv[1], "translate")) return translate(argc - 2, argv + 2);
-    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate, extract, summarize, translate)\n", argv[1]);
+    if (!strcmp(argv[1], "relatives")) return relatives(argc - 2, argv + 2);
+    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate, extract, summarize, translate, relatives)\n", argv[1]);
     return 1;
 }

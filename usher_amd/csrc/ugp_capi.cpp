@@ -30,6 +30,7 @@
 #include "ugp_uncertainty.hpp"
 #include "ugp_annotate.hpp"
 #include "ugp_nearest.hpp"
+#include "ugp_relatives.hpp"
 #include "ugp_genotypes.hpp"
 #include "ugp_summary.hpp"
 #include "ugp_translate.hpp"
@@ -302,6 +303,7 @@ struct ugp_mat {
     ugp::RipState *rip = nullptr;    // RIPPLES tables (ugp_ripples_attach), or none
     ugp::AnnState *ann = nullptr;    // matUtils annotate tables (ugp_annotate_attach), or none
     ugp::NearState *near = nullptr;  // matUtils extract nearest-k tables (ugp_nearest_attach), or none
+    ugp::RelState *rel = nullptr;    // matUtils extract relatives tables (ugp_relatives_attach), or none
     ugp::GtState *gt = nullptr;      // matUtils extract -v tables (ugp_genotypes_attach), or none
     ugp::SmState *sm = nullptr;      // matUtils summary tables (ugp_summary_attach), or none
     ugp::TrState *tr = nullptr;      // matUtils summary --translate tables (ugp_translate_attach), or none
@@ -1427,6 +1429,7 @@ void ugp_mat_destroy(ugp_mat *m) {
     ugp::rip_free(m->rip);
     ugp::ann_free(m->ann);
     ugp::nk_free(m->near);
+    ugp::rel_free(m->rel);
     ugp::gt_free(m->gt);
     ugp::sm_free(m->sm);
     ugp::tr_free(m->tr);
@@ -1928,6 +1931,50 @@ int ugp_nearest_k_chunked(ugp_mat *m, uint64_t n_queries, const uint32_t *nodes,
 int ugp_nearest_k(ugp_mat *m, uint64_t n_queries, const uint32_t *nodes, const uint32_t *k, uint32_t out_stride, uint32_t *out_nodes,
                   uint32_t *out_dist, ugp_nearest_info *info) {
     return ugp_nearest_k_chunked(m, n_queries, nodes, k, out_stride, out_nodes, out_dist, info, 0);
+}
+
+// ---- matUtils extract: per-sample relatives (ugp_relatives.hip) ----------------------------------------------------------
+
+int ugp_relatives_attach(ugp_mat *m, const ugp_tree_desc *tree, const uint32_t *name_rank) {
+    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
+    if (int rc = check_handle_tree(m, tree)) return rc;
+    return ugp::rel_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, name_rank, &m->dfs, &m->rel);
+}
+
+int ugp_relatives_closest_chunked(ugp_mat *m, uint64_t n, const uint32_t *nodes, ugp_rel_info *info, uint64_t *out_off, uint32_t *out_nodes,
+                                  uint64_t cap, uint64_t *n_out, uint32_t chunk_samples) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::rel_run(m->rel, false, n, nodes, 0, info, out_off, out_nodes, cap, n_out, chunk_samples, nullptr);
+}
+
+int ugp_relatives_closest(ugp_mat *m, uint64_t n, const uint32_t *nodes, ugp_rel_info *info, uint64_t *out_off, uint32_t *out_nodes,
+                          uint64_t cap, uint64_t *n_out) {
+    return ugp_relatives_closest_chunked(m, n, nodes, info, out_off, out_nodes, cap, n_out, 0);
+}
+
+int ugp_relatives_within_chunked(ugp_mat *m, uint64_t n, const uint32_t *nodes, uint32_t threshold, ugp_rel_info *info, uint64_t *out_off,
+                                 uint32_t *out_nodes, uint64_t cap, uint64_t *n_out, uint32_t chunk_samples) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::rel_run(m->rel, true, n, nodes, threshold, info, out_off, out_nodes, cap, n_out, chunk_samples, nullptr);
+}
+
+int ugp_relatives_within(ugp_mat *m, uint64_t n, const uint32_t *nodes, uint32_t threshold, ugp_rel_info *info, uint64_t *out_off,
+                         uint32_t *out_nodes, uint64_t cap, uint64_t *n_out) {
+    return ugp_relatives_within_chunked(m, n, nodes, threshold, info, out_off, out_nodes, cap, n_out, 0);
+}
+
+int ugp_relatives_time(ugp_mat *m, uint64_t n, const uint32_t *nodes, int within, uint32_t threshold, uint32_t reps, double *count_ms,
+                       double *fill_ms) {
+    if (!m || !reps || !count_ms || !fill_ms) return fail(UGP_ERR_INVALID, "null argument");
+    double ms[2], sum[2] = {0, 0};
+    uint64_t total = 0;
+    for (uint32_t r = 0; r <= reps; r++) {   // the first run warms up
+        if (int rc = ugp::rel_run(m->rel, within != 0, n, nodes, threshold, nullptr, nullptr, nullptr, 0, &total, 0, ms)) return rc;
+        if (r) { sum[0] += ms[0]; sum[1] += ms[1]; }
+    }
+    *count_ms = sum[0] / reps;
+    *fill_ms = sum[1] / reps;
+    return UGP_OK;
 }
 
 // ---- matUtils extract -v: genotypes of a selection (ugp_genotypes.hip) -------------------------------------------------

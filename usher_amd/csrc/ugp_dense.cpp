@@ -14,7 +14,7 @@ namespace ugp {
 
 int dfs_tables_same_arrays(const DfsTables &T, const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const char *who) {
     const std::string other = std::string("the handle's depth-first tables were built from other mutation arrays (an earlier uncertainty, annotate, "
-                                          "nearest, genotypes, summary or translate attach): ") + who + " needs the arrays of that attach, or a handle of its own";
+                                          "nearest, genotypes, summary, translate or relatives attach): ") + who + " needs the arrays of that attach, or a handle of its own";
     const uint64_t M = tree->mut_off[tree->n_nodes];
     if (T.m != M || T.n != tree->n_nodes) return set_error(UGP_ERR_INVALID, other);
     if (hipSetDevice(T.device) != hipSuccess) return set_error(UGP_ERR_HIP, "hipSetDevice failed");

@@ -544,6 +544,78 @@ class Placer:
         self._ck(self._L.ugp_translate_time(self._h, int(reps), C.byref(ms)))
         return float(ms.value)
 
+    # ---- matUtils extract --closest-relatives / --within-distance (ugp_relatives_*) ---------------------------------------
+    REL_INFO = np.dtype([("dist", np.uint32), ("count", np.uint32), ("levels", np.uint32), ("best", np.uint32)])
+    REL_BLOCK = 16   # UGP_REL_BLOCK: leaves per block of the range minima (the tests aim at its edges)
+
+    @staticmethod
+    def name_ranks(names) -> np.ndarray:
+        """The name_rank of relatives_attach: names[j]'s place in the order of std::string::operator<, which compares unsigned
+        bytes (equal names, which a tree does not have, keep their index order)."""
+        keys = [s if isinstance(s, bytes) else str(s).encode() for s in names]
+        order = sorted(range(len(keys)), key=lambda j: (keys[j], j))
+        rank = np.empty(len(keys), np.uint32)
+        rank[order] = np.arange(len(keys), dtype=np.uint32)
+        return rank
+
+    def relatives_attach(self, name_rank=None, arrays: Optional[Dict] = None):
+        """ugp_relatives_attach with the placer's own tree, or with other mutation arrays on the same topology: the leaf tables,
+        range minima and (cum, leaf) order of the relatives calls.  name_rank [n] by BFS index (name_ranks(names)) lets
+        relatives_closest report the relative with the smallest name; None: no ranks.  A later attach replaces the tables.  The
+        depth-first tables are shared as genotypes_attach describes."""
+        rank = None if name_rank is None else np.ascontiguousarray(name_rank, dtype=np.uint32)
+        if rank is not None and len(rank) != self.n_nodes:
+            raise UgpError(-1, "name_rank holds one rank per node")
+        t = self._t if arrays is None else _TreeArrays(arrays)
+        self._ck(self._L.ugp_relatives_attach(self._h, C.byref(t.desc), None if rank is None else _ptr(rank)))
+        self._rel_ready = True
+
+    def _relatives(self, call, nodes, lists, cap):
+        if not getattr(self, "_rel_ready", False):
+            self.relatives_attach()
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
+        n = len(nodes)
+        info = np.zeros(n, self.REL_INFO)
+        n_out = C.c_uint64(0)
+        if not lists:
+            self._ck(call(_ptr(nodes) if n else None, n, _ptr(info) if n else None, None, None, 0, C.byref(n_out)))
+            self._rel_n_out = int(n_out.value)
+            return info, None, None
+        off = np.zeros(n + 1, np.uint64)
+        room = int(cap) if cap is not None else max(4 * n, 1024)
+        while True:   # grow and retry: the call reports the true total
+            out = np.full(room, 0xFFFFFFFF, np.uint32)
+            self._ck(call(_ptr(nodes) if n else None, n, _ptr(info) if n else None, _ptr(off), _ptr(out) if room else None, room, C.byref(n_out)))
+            self._rel_n_out = int(n_out.value)
+            if cap is not None or self._rel_n_out <= room:
+                return info, off, out[:min(room, self._rel_n_out)]
+            room = self._rel_n_out
+
+    def relatives_closest(self, nodes, lists: bool = True, chunk_samples: int = 0, cap: Optional[int] = None):
+        """matUtils extract --closest-relatives (get_closest_samples with fixed_k = false, select.cpp:577-714) for tree nodes given
+        by BFS index.  Returns (info, off, nodes): info a REL_INFO array (dist, count, levels, best -- the closest relative with
+        the smallest name rank, 0xFFFFFFFF without ranks or relatives); the relatives of sample i are nodes[off[i]:off[i + 1]]
+        (BFS indices), level by level in depth-first order.  lists=False: only info (off and nodes are None).  chunk_samples
+        (test hook): samples per workspace chunk; cap (test hook): room for that many list entries only, the true total is then
+        in _rel_n_out.  The tables are made on the first call (relatives_attach without ranks)."""
+        fn = self._L.ugp_relatives_closest_chunked
+        return self._relatives(lambda nd, n, info, off, out, room, n_out: fn(self._h, n, nd, info, off, out, room, n_out, int(chunk_samples)),
+                               nodes, lists, cap)
+
+    def relatives_within(self, nodes, threshold: int, lists: bool = True, chunk_samples: int = 0, cap: Optional[int] = None):
+        """matUtils extract --within-distance (get_closest_samples with fixed_k = true): the leaves within `threshold` mutation
+        entries of each node, as relatives_closest returns them; dist is 0 and best 0xFFFFFFFF."""
+        fn = self._L.ugp_relatives_within_chunked
+        return self._relatives(lambda nd, n, info, off, out, room, n_out: fn(self._h, n, nd, int(threshold), info, off, out, room, n_out,
+                                                                            int(chunk_samples)), nodes, lists, cap)
+
+    def relatives_time(self, nodes, within: bool = False, threshold: int = 0, reps: int = 5):
+        """Bench hook: (count_ms, fill_ms), the device time of the two passes alone over these nodes, no copy to the host."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
+        a, b = C.c_double(0), C.c_double(0)
+        self._ck(self._L.ugp_relatives_time(self._h, len(nodes), _ptr(nodes), int(bool(within)), int(threshold), int(reps), C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
+
     RIPPLES_EVENT = np.dtype([("branch", np.uint64), ("i", np.uint32), ("j", np.uint32), ("donor", np.uint32), ("acceptor", np.uint32),
                               ("donor_count", np.uint32), ("acceptor_count", np.uint32), ("donor_score", np.int32),
                               ("acceptor_score", np.int32), ("donor_sibling", np.uint8), ("acceptor_sibling", np.uint8),
