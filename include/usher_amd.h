@@ -443,6 +443,34 @@ int ugp_relatives_within_chunked(ugp_mat *mat, uint64_t n, const uint32_t *nodes
  * within = 0: closest mode (threshold ignored). */
 int ugp_relatives_time(ugp_mat *mat, uint64_t n, const uint32_t *nodes, int within, uint32_t threshold, uint32_t reps, double *count_ms,
                        double *fill_ms);
+/* matUtils extract's sample selectors (matUtils/select.cpp: get_mutation_samples :67-111, get_leaves_ids under get_clade_samples and
+ * -I, get_mrca_samples :570-575) as bitmaps over LEAF RANKS: leaf r is the r-th leaf of the depth-first expansion, bit r & 63 of
+ * word r >> 6; a bitmap has (n_leaves + 63) / 64 words and the bits past the last leaf are zero in every bitmap written here.
+ * ugp_select_attach shares the depth-first tables of `tree` (the handle's tree; arrays are copied; tables built from other mutation
+ * arrays: UGP_ERR_INVALID, nothing changed) and builds, once per handle, the leaves in depth-first order and per node the half-open
+ * range of leaf ranks below it.  A second attach replaces the first.  A call before the attach is UGP_ERR_INVALID.
+ * ugp_select_leaves: bfs_by_rank[r] = the BFS index of leaf r (NULL: not written); *n_leaves = their number (NULL: not written).
+ * ugp_select_mutations: leaf l is selected by query q = (pos, nuc) exactly when the nearest node on l's root path, l included, with
+ *   a non-masked entry at pos has mut_nuc == nuc in the FIRST such entry it stores (equality of the stored code, no bit test).  A
+ *   leaf with no such node is not selected whatever nuc is: a query for the reference base selects only leaves under a
+ *   back-mutation (get_mutation_samples read literally).  pos < 0 and positions above every entry select nobody.  words = the OR
+ *   over all queries, counts[q] = the leaves of query q alone.
+ * ugp_select_subtrees: words = the union of the leaves below the given nodes (a leaf node selects itself), counts[i] = the leaves
+ *   below node i alone.  A node out of range is UGP_ERR_INVALID before anything is written.
+ * ugp_select_mrca: *node = the deepest node whose subtree holds every leaf set in `words` (bits past the last leaf are ignored),
+ *   *n_below = the leaves below it.  An empty bitmap is UGP_ERR_INVALID.
+ * The _chunked twins (test hooks) set the queries, or the disjoint rank ranges, staged per launch (0: default). */
+int ugp_select_attach(ugp_mat *mat, const ugp_tree_desc *tree);
+int ugp_select_leaves(ugp_mat *mat, uint32_t *bfs_by_rank /* [n_leaves], or NULL */, uint64_t *n_leaves /* or NULL */);
+int ugp_select_mutations(ugp_mat *mat, uint64_t n_mut, const int32_t *pos, const uint8_t *nuc, uint64_t *words, uint64_t *counts /* [n_mut] */);
+int ugp_select_mutations_chunked(ugp_mat *mat, uint64_t n_mut, const int32_t *pos, const uint8_t *nuc, uint64_t *words, uint64_t *counts,
+                                 uint32_t chunk_queries);
+int ugp_select_subtrees(ugp_mat *mat, uint64_t n, const uint32_t *nodes /* BFS, any node */, uint64_t *words, uint64_t *counts /* [n] */);
+int ugp_select_subtrees_chunked(ugp_mat *mat, uint64_t n, const uint32_t *nodes, uint64_t *words, uint64_t *counts, uint32_t chunk_ranges);
+int ugp_select_mrca(ugp_mat *mat, const uint64_t *words, uint32_t *node /* BFS */, uint64_t *n_below);
+/* Bench hook: milliseconds of device time of the mutation kernel alone over these queries (the bitmap and the counts stay on the
+ * device); mean of `reps` runs after one warm-up run. */
+int ugp_select_time(ugp_mat *mat, uint64_t n_mut, const int32_t *pos, const uint8_t *nuc, uint32_t reps, double *ms);
 /* RIPPLES (ripples/main.cpp): the options of :22-44 that the search reads. branch_len >= 1 and parsimony_improvement >= 0
  * (UGP_ERR_INVALID otherwise: the reference's size_t arithmetic of :445-453 is not reproduced for negative values). */
 typedef struct ugp_ripples_opts {

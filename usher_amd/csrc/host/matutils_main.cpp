@@ -7,6 +7,7 @@
 //   matutils-amd summarize -i tree.pb [-s -c -C -m -a -R file ...] [-A] [-M] [-d dir] [--host]
 //   matutils-amd translate -i tree.pb -g genes.gtf -f ref.fa -t out.tsv [-d dir] [--host]
 //   matutils-amd relatives -i tree.pb [-s samples.txt] [-V closest.tsv [-q]] [--within-distance within.tsv [--distance-threshold n]] [--host]
+//   matutils-amd select   extract's options and [-I node] [-c clades] [-m mutations] [-H regex] [-e n] [-U] [-p] [--host]
 //
 // uncertainty_main / findEPPs_wrapper (uncertainty.cpp:279-339, 541-560): load the MAT, uncondense its leaves, read the sample
 // names, and for every sample report its equally parsimonious placements and neighborhood size (-e) and the candidate parents
@@ -24,6 +25,8 @@
 // extract --closest-relatives / --within-distance (extract.cpp:768-823), as the subcommand `relatives`: per sample its closest
 // leaves, or those within a distance (get_closest_samples, select.cpp:577-714).  The lists come from ugp_relatives.hip; --host
 // runs the reference's walk statement by statement.  `extract` itself goes on refusing the four options.
+// extract's selectors -I -c -m -H -e -U -p (extract.cpp:294-373, 411-427, 455-472), as the subcommand `select`, which shares extract's
+// body: the selections are bitmaps over leaf ranks from ugp_select.hip, -e asks ugp_uncertainty; --host runs the reference's walks.
 #include <hip/hip_runtime_api.h>
 #include <sys/stat.h>
 #include <zlib.h>
@@ -37,6 +40,7 @@
 #include <fstream>
 #include <future>
 #include <map>
+#include <regex>
 #include <set>
 #include <sstream>
 #include <string>
@@ -44,6 +48,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "driver.hpp"
 #include "mat.hpp"
 #include "usher_amd.h"
 
@@ -60,7 +65,7 @@ void usage(FILE *f) {
             "      --device             HIP device ordinal [0]\n"
             "  (-d / --dropout-mutations is not supported)\n"
             "       matutils-amd annotate --help | matutils-amd extract --help | matutils-amd summarize --help | matutils-amd translate --help\n"
-            "       matutils-amd relatives --help\n");
+            "       matutils-amd relatives --help | matutils-amd select --help\n");
 }
 
 int uncertainty(int argc, char **argv) {
@@ -1285,11 +1290,390 @@ int make_vcf(uh::Tree &T, const std::string &path, bool no_genotypes, const std:
     return 0;
 }
 
-int extract(int argc, char **argv) {   // extract_main, extract.cpp:149-640, 867-888 for the options of extract_usage
+// ---- select: extract's -I -c -m -H -e -U -p (extract.cpp:294-373, 411-427, 455-472; select.cpp) ---------------------------------
+
+void select_usage(FILE *f) {
+    fprintf(f,
+            "Usage: matutils-amd select -i tree.pb [-s samples.txt] [-k sample:k] [-I node] [-c clade[,clade]] [-m mutation[,mutation]] [-H regex]\n"
+            "       [-a n] [-b n] [-P n] [-e n] [-U] [-Y y] [-p] [-u used.txt] [-t tree.nh] [-o out.pb] [-v out.vcf] [-n] [-d dir] [-T n]\n"
+            "       [--device k] [--reference-ties] [--host-genotypes] [--host]\n"
+            "  every option of matutils-amd extract (see extract --help), and the selectors, applied in this order after -s and -k:\n"
+            "  -I, --get-internal-descendents  select the samples below this internal node\n"
+            "  -c, --clade              select the samples of a clade; comma-separated names are ORed\n"
+            "  -m, --mutation           select the samples with a mutation (A123G); comma-separated mutations are ORed\n"
+            "  -H, --match              select the samples whose name matches this regular expression (std::regex_match)\n"
+            "  -e, --max-epps           (after -a -b -P) select samples with at most this many equally parsimonious placements\n"
+            "  -U, --from-mrca          widen to every sample below the most recent common ancestor of the selection\n"
+            "  -p, --prune              (last) invert the selection\n"
+            "      --host               run every selector as the reference's walk on the host (slow)\n"
+            "  Where the reference takes its order from an unordered set (-c or -m with nothing selected before), the samples are\n"
+            "  written in depth-first order.  -e with nothing selected before checks the leaves only (the reference also walks the\n"
+            "  internal nodes); with a selection it keeps its members in depth-first order.  -H is std::regex_match on both paths.\n");
+}
+
+struct SelectOpts {
+    bool on = false, mrca = false, prune = false, host = false;
+    std::string internal, clade, mutation, match;
+    long max_epps = 0;
+};
+
+// The selectors on the device: one handle, one ugp_select_attach; a selection crosses as a bitmap over leaf ranks.
+struct SelectDevice {
+    uh::Tree &T;
+    int device;
+    ugp_mat *h = nullptr;
+    std::vector<uh::Node *> bfs;
+    std::vector<uint32_t> parent, leaf_bfs, rank_of;   // rank_of by BFS index, UINT32_MAX for an internal node
+    std::vector<uint64_t> mut_off;
+    std::vector<int32_t> pos;
+    std::vector<uint8_t> ref, par, nuc;
+    ugp_tree_desc desc{};
+    bool unc_attached = false;
+    SelectDevice(uh::Tree &t, int dev) : T(t), device(dev) {}
+    ~SelectDevice() { if (h) ugp_mat_destroy(h); }
+    void up() {
+        if (h) return;
+        bfs = T.bfs();
+        const uint64_t N = bfs.size();
+        for (uint64_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
+        parent.resize(N);
+        mut_off.assign(N + 1, 0);
+        for (uint64_t j = 0; j < N; j++) {
+            parent[j] = bfs[j]->parent ? bfs[j]->parent->flat_index : UINT32_MAX;
+            for (const auto &m : bfs[j]->mutations) {
+                pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
+            }
+            mut_off[j + 1] = pos.size();
+        }
+        // the handle takes the bare topology, the select tables the mutations as they are stored (masked, repeated positions)
+        const std::vector<uint64_t> no_off(N + 1, 0);
+        if (pos.empty()) { pos.push_back(0); ref.push_back(0); par.push_back(0); nuc.push_back(0); }   // (never read: no null arrays)
+        const ugp_tree_desc bare{N, parent.data(), no_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+        desc = ugp_tree_desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+        if (ugp_mat_create(&bare, device, &h) != UGP_OK) lib_fail("ugp_mat_create");
+        if (ugp_select_attach(h, &desc) != UGP_OK) lib_fail("ugp_select_attach");
+        uint64_t nl = 0;
+        if (ugp_select_leaves(h, nullptr, &nl) != UGP_OK) lib_fail("ugp_select_leaves");
+        leaf_bfs.resize(nl);
+        if (ugp_select_leaves(h, leaf_bfs.data(), nullptr) != UGP_OK) lib_fail("ugp_select_leaves");
+        rank_of.assign(N, UINT32_MAX);
+        for (uint32_t r = 0; r < nl; r++) rank_of[leaf_bfs[r]] = r;
+    }
+    size_t n_words() const { return (leaf_bfs.size() + 63) / 64; }
+    static bool bit(const std::vector<uint64_t> &w, uint32_t r) { return (w[r >> 6] >> (r & 63)) & 1; }
+    bool has(const std::vector<uint64_t> &w, const std::string &name) const {
+        const uh::Node *n = T.get_node(name);
+        return n && rank_of[n->flat_index] != UINT32_MAX && bit(w, rank_of[n->flat_index]);
+    }
+    std::vector<uint64_t> subtrees(const std::vector<uint32_t> &nodes, std::vector<uint64_t> &counts) {
+        up();
+        std::vector<uint64_t> w(std::max<size_t>(n_words(), 1), 0);
+        counts.assign(nodes.size(), 0);
+        if (ugp_select_subtrees(h, nodes.size(), nodes.data(), w.data(), counts.data()) != UGP_OK) lib_fail("ugp_select_subtrees");
+        return w;
+    }
+    std::vector<uint64_t> mutations(const std::vector<int32_t> &qp, const std::vector<uint8_t> &qn, std::vector<uint64_t> &counts) {
+        up();
+        std::vector<uint64_t> w(std::max<size_t>(n_words(), 1), 0);
+        counts.assign(qp.size(), 0);
+        if (ugp_select_mutations(h, qp.size(), qp.data(), qn.data(), w.data(), counts.data()) != UGP_OK) lib_fail("ugp_select_mutations");
+        return w;
+    }
+    // The bitmap of names that are all leaves; false when one is not (the caller walks on the host then).
+    bool words_of(const std::vector<std::string> &names, std::vector<uint64_t> &w) {
+        up();
+        w.assign(std::max<size_t>(n_words(), 1), 0);
+        for (const std::string &s : names) {
+            const uh::Node *n = T.get_node(s);
+            if (!n || rank_of[n->flat_index] == UINT32_MAX) return false;
+            const uint32_t r = rank_of[n->flat_index];
+            w[r >> 6] |= 1ull << (r & 63);
+        }
+        return true;
+    }
+    std::vector<std::string> in_rank_order(const std::vector<uint64_t> &w) const {   // depth-first
+        std::vector<std::string> out;
+        for (uint32_t r = 0; r < leaf_bfs.size(); r++) if (bit(w, r)) out.push_back(bfs[leaf_bfs[r]]->id);
+        return out;
+    }
+    std::vector<std::string> in_leaves_order(const std::vector<uint64_t> &w, bool set) const {   // get_leaves_ids: breadth-first
+        std::vector<std::string> out;
+        for (const uh::Node *n : bfs) if (n->is_leaf() && bit(w, rank_of[n->flat_index]) == set) out.push_back(n->id);
+        return out;
+    }
+    std::vector<std::string> filter(const std::vector<std::string> &samples, const std::vector<uint64_t> &w) const {   // sample_intersect
+        std::vector<std::string> out;
+        for (const std::string &s : samples) if (has(w, s)) out.push_back(s);
+        return out;
+    }
+    std::vector<uint32_t> epps(const std::vector<uint32_t> &nodes) {
+        up();
+        if (!unc_attached && ugp_uncertainty_attach(h, &desc) != UGP_OK) lib_fail("ugp_uncertainty_attach");
+        unc_attached = true;
+        const size_t n = nodes.size();
+        std::vector<uint32_t> e(n), ns(n), ties(std::max<size_t>(n, 1)), tc(n);
+        if (n && ugp_uncertainty(h, nodes.data(), n, 1, e.data(), ns.data(), ties.data(), tc.data()) != UGP_OK) lib_fail("ugp_uncertainty");
+        return e;
+    }
+};
+
+// findEPPs' num_best (uncertainty.cpp:132-255) for one node on the host: the sample in the literal order, every other node scored
+// by mapper2_body.  0 when the node's root path has no mutation (the reference leaves the value unset there; ugp_uncertainty says 0).
+size_t host_epps(const uh::Tree &T, const std::vector<uh::Node *> &dfs, uh::Node *node) {
+    std::vector<int32_t> seen;
+    std::vector<uh::Mutation> q;
+    auto take = [&](const uh::Node *n) {
+        for (const auto &m : n->mutations)
+            if (m.masked() || std::find(seen.begin(), seen.end(), m.position) == seen.end()) {
+                q.push_back(m);
+                if (!m.masked()) seen.push_back(m.position);
+            }
+    };
+    take(node);
+    for (const uh::Node *a : T.rsearch(node, false)) take(a);
+    if (q.empty()) return 0;
+    int best = (int)(q.size() + T.root->mutations.size() + 1);
+    size_t num_best = 1;
+    uh::NodeVecs nv;
+    for (const uh::Node *n : dfs) {
+        if (n == node) continue;
+        uh::node_vecs(n, q, nv);
+        if (!nv.eligible || nv.set_difference > best) continue;
+        if (nv.set_difference < best) { best = nv.set_difference; num_best = 1; }
+        else num_best++;
+    }
+    return num_best;
+}
+
+const char *const kNoneLeft = "ERROR: No samples fulfill selected criteria. Change arguments and try again\n";
+
+std::vector<std::string> split_commas(const std::string &s) {   // std::getline(stream, item, ',')
+    std::vector<std::string> out;
+    std::stringstream ss(s);
+    std::string item;
+    while (std::getline(ss, item, ',')) out.push_back(item);
+    return out;
+}
+
+void step_time(const char *what, bool host, std::chrono::steady_clock::time_point t0) {
+    fprintf(stderr, "Selection step %s (%s): %.3f msec\n", what, host ? "host" : "device",
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+}
+
+// -I, -c, -m and -H (extract.cpp:294-373).  false: the reference exits here (the message is printed).
+bool select_before_filters(uh::Tree &T, const SelectOpts &O, SelectDevice &D, std::vector<std::string> &samples) {
+    std::vector<uint64_t> counts;
+    if (!O.internal.empty()) {
+        const auto t0 = std::chrono::steady_clock::now();
+        uh::Node *node = T.get_node(O.internal);
+        if (O.host) {
+            std::vector<std::string> ic;
+            if (node) for (const uh::Node *l : T.leaves(node)) ic.push_back(l->id);
+            if (samples.empty()) samples = ic;
+            else { const std::unordered_set<std::string> set(ic.begin(), ic.end()); std::vector<std::string> in; for (const auto &s : samples) if (set.count(s)) in.push_back(s); samples = in; }
+        } else {
+            D.up();
+            const std::vector<uint64_t> w = D.subtrees(node ? std::vector<uint32_t>{node->flat_index} : std::vector<uint32_t>{}, counts);
+            samples = samples.empty() ? D.in_leaves_order(w, true) : D.filter(samples, w);
+        }
+        step_time("-I", O.host, t0);
+    }
+    if (!O.clade.empty()) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const std::vector<std::string> clades = split_commas(O.clade);
+        std::vector<uh::Node *> roots(clades.size(), nullptr);
+        const std::vector<uh::Node *> dfs = T.dfs();
+        if (O.host) {   // get_clade_samples, once per name
+            for (size_t i = 0; i < clades.size(); i++)
+                for (uh::Node *s : dfs) {
+                    const auto &canns = s->clade_annotations;
+                    if (canns.empty() || !(canns.size() > 1 || canns[0] != "")) continue;
+                    if (std::find(canns.begin(), canns.end(), clades[i]) != canns.end()) { roots[i] = s; break; }
+                }
+        } else {        // one pass for every name
+            std::unordered_map<std::string, std::vector<size_t>> want;
+            for (size_t i = 0; i < clades.size(); i++) want[clades[i]].push_back(i);
+            size_t open = want.size();
+            for (uh::Node *s : dfs) {
+                const auto &canns = s->clade_annotations;
+                if (canns.empty() || !(canns.size() > 1 || canns[0] != "")) continue;
+                for (const std::string &c : canns) {
+                    auto it = want.find(c);
+                    if (it == want.end() || roots[it->second[0]]) continue;
+                    for (size_t i : it->second) roots[i] = s;
+                    open--;
+                }
+                if (!open) break;
+            }
+        }
+        std::vector<uint64_t> w;
+        std::unordered_set<std::string> in_clade;
+        if (!O.host) {
+            D.up();
+            std::vector<uint32_t> nodes;
+            for (const uh::Node *r : roots) if (r) nodes.push_back(r->flat_index);
+            w = D.subtrees(nodes, counts);
+        }
+        for (size_t i = 0; i < clades.size(); i++) {
+            fprintf(stderr, "Getting member samples of clade %s\n", clades[i].c_str());
+            if (!roots[i]) fprintf(stderr, "WARNING: Clade %s is not detected in the input tree!\n", clades[i].c_str());
+            else if (O.host) for (const uh::Node *l : T.leaves(roots[i])) in_clade.insert(l->id);
+        }
+        if (O.host) {
+            std::vector<std::string> out;
+            if (samples.empty()) { for (const uh::Node *n : dfs) if (in_clade.count(n->id)) out.push_back(n->id); }
+            else for (const auto &s : samples) if (in_clade.count(s)) out.push_back(s);
+            samples = out;
+        } else {
+            samples = samples.empty() ? D.in_rank_order(w) : D.filter(samples, w);
+        }
+        step_time("-c", O.host, t0);
+        if (samples.empty()) { fputs(kNoneLeft, stderr); return false; }
+    }
+    if (!O.mutation.empty()) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const std::vector<std::string> muts = split_commas(O.mutation);
+        std::vector<int32_t> qp;
+        std::vector<uint8_t> qn;
+        for (const std::string &m : muts) {
+            uh::Mutation mu;
+            if (!mutation_from_string(m, mu)) { fprintf(stderr, "ERROR: %s is not a mutation\n", m.c_str()); return false; }   // (the reference dereferences the null pointer)
+            qp.push_back(mu.position);
+            qn.push_back((uint8_t)mu.mut_nuc);
+        }
+        std::vector<uint64_t> w;
+        std::unordered_set<std::string> with_mut;
+        if (!O.host) w = D.mutations(qp, qn, counts);
+        for (size_t i = 0; i < muts.size(); i++) {
+            fprintf(stderr, "Getting samples with mutation %s\n", muts[i].c_str());
+            size_t found = O.host ? 0 : counts[i];
+            if (O.host) {   // get_mutation_samples
+                for (uh::Node *node : T.leaves()) {
+                    bool assigned = false;
+                    for (const auto &m : node->mutations)
+                        if (qp[i] == m.position) {
+                            if ((int8_t)qn[i] == m.mut_nuc) { with_mut.insert(node->id); found++; }
+                            assigned = true;
+                            break;
+                        }
+                    if (assigned) continue;
+                    for (const uh::Node *anc : T.rsearch(node, false)) {
+                        if (assigned) break;
+                        for (const auto &m : anc->mutations)
+                            if (qp[i] == m.position) {
+                                if ((int8_t)qn[i] == m.mut_nuc) { with_mut.insert(node->id); found++; }
+                                assigned = true;
+                                break;
+                            }
+                    }
+                }
+            }
+            if (!found) fprintf(stderr, "WARNING: No samples with mutation %s found in tree!\n", muts[i].c_str());
+        }
+        if (O.host) {
+            std::vector<std::string> out;
+            if (samples.empty()) { for (const uh::Node *n : T.dfs()) if (with_mut.count(n->id)) out.push_back(n->id); }
+            else for (const auto &s : samples) if (with_mut.count(s)) out.push_back(s);
+            samples = out;
+        } else {
+            samples = samples.empty() ? D.in_rank_order(w) : D.filter(samples, w);
+        }
+        step_time("-m", O.host, t0);
+        if (samples.empty()) { fputs(kNoneLeft, stderr); return false; }
+    }
+    if (!O.match.empty()) {   // get_sample_match, select.cpp:506-520: on the host on both paths
+        if (samples.empty()) samples = leaf_ids(T);
+        std::vector<std::string> out;
+        try {
+            const std::regex pat(O.match);
+            for (const std::string &s : samples) if (std::regex_match(s, pat)) out.push_back(s);
+        } catch (const std::regex_error &e) { fprintf(stderr, "ERROR: bad regular expression %s: %s\n", O.match.c_str(), e.what()); return false; }
+        samples = out;
+        if (samples.empty()) { fputs(kNoneLeft, stderr); return false; }
+    }
+    return true;
+}
+
+// -e and -U (extract.cpp:411-427), between the linear filters and -Y.
+bool select_after_filters(uh::Tree &T, const SelectOpts &O, SelectDevice &D, std::vector<std::string> &samples) {
+    if (O.max_epps > 0) {   // get_samples_epps, uncertainty.cpp:350-368
+        const auto t0 = std::chrono::steady_clock::now();
+        const std::vector<uh::Node *> dfs = T.dfs();
+        const std::unordered_set<std::string> check(samples.begin(), samples.end());
+        std::vector<uh::Node *> todo;
+        for (uh::Node *n : dfs) if (samples.empty() ? n->is_leaf() : check.count(n->id) != 0) todo.push_back(n);
+        std::vector<std::string> good;
+        if (O.host) {
+            for (uh::Node *n : todo) if (host_epps(T, dfs, n) <= (size_t)O.max_epps) good.push_back(n->id);
+        } else {
+            D.up();
+            std::vector<uint32_t> nodes;
+            for (const uh::Node *n : todo) nodes.push_back(n->flat_index);
+            const std::vector<uint32_t> e = D.epps(nodes);
+            for (size_t i = 0; i < todo.size(); i++) if (e[i] <= (uint64_t)O.max_epps) good.push_back(todo[i]->id);
+        }
+        samples = good;
+        step_time("-e", O.host, t0);
+        if (samples.empty()) { fputs(kNoneLeft, stderr); return false; }
+    }
+    if (O.mrca) {   // get_mrca_samples, select.cpp:570-575
+        const auto t0 = std::chrono::steady_clock::now();
+        if (samples.empty()) { fprintf(stderr, "ERROR: -U/--from-mrca needs a selection\n"); return false; }   // (the reference dereferences the null root)
+        std::vector<uint64_t> w, counts;
+        if (!O.host && D.words_of(samples, w)) {
+            uint32_t node = 0;
+            uint64_t below = 0;
+            if (ugp_select_mrca(D.h, w.data(), &node, &below) != UGP_OK) lib_fail("ugp_select_mrca");
+            samples = D.in_leaves_order(D.subtrees({node}, counts), true);
+        } else {   // the reference's walk; also the device path's when a selected name is not a leaf
+            uh::Tree sub;
+            std::string err;
+            if (!uh::get_subtree(T, samples, sub, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return false; }
+            uh::Node *mrca = T.get_node(sub.root->id);
+            samples.clear();
+            for (const uh::Node *l : T.leaves(mrca)) samples.push_back(l->id);
+        }
+        step_time("-U", O.host, t0);
+    }
+    return true;
+}
+
+// -p (extract.cpp:455-472), the last step.
+bool select_prune(uh::Tree &T, const SelectOpts &O, SelectDevice &D, std::vector<std::string> &samples) {
+    if (!O.prune) return true;
+    fprintf(stderr, "Sample pruning requested...\n");
+    const auto t0 = std::chrono::steady_clock::now();
+    if (O.host) {
+        const std::unordered_set<std::string> set(samples.begin(), samples.end());
+        std::vector<std::string> out;
+        for (const std::string &s : leaf_ids(T)) if (!set.count(s)) out.push_back(s);
+        samples = out;
+    } else {   // the complement of the bitmap; a selected name that is no leaf was never among the leaves
+        D.up();
+        std::vector<uint64_t> w(std::max<size_t>(D.n_words(), 1), 0);
+        for (const std::string &s : samples) {
+            const uh::Node *n = T.get_node(s);
+            if (n && D.rank_of[n->flat_index] != UINT32_MAX) w[D.rank_of[n->flat_index] >> 6] |= 1ull << (D.rank_of[n->flat_index] & 63);
+        }
+        samples = D.in_leaves_order(w, false);
+    }
+    step_time("-p", O.host, t0);
+    if (samples.empty()) {
+        fprintf(stderr, "ERROR: No samples fulfill selected criteria (tree is left empty). Change arguments and try again\n");
+        return false;
+    }
+    return true;
+}
+
+// extract_main, extract.cpp:149-640, 867-888 for the options of extract_usage; `sel`: the subcommand `select`, which adds the selectors
+int extract_or_select(int argc, char **argv, bool sel) {
     std::string in_mat, fsamples, nearest_k, fused, ftree, fmat, fvcf, dir = "./";
     int max_parsimony = -1, max_branch = -1, max_path = -1, device = 0;
     size_t select_nearest = 0;
     bool reference_ties = false, no_genotypes = false, host_genotypes = false;
+    SelectOpts S;
+    S.on = sel;
+    void (*const show_usage)(FILE *) = sel ? select_usage : extract_usage;
     static const char *const unsupported[] = {
         "-K", "--nearest-k-batch", "-j", "--write-json", "-c", "--clade", "-m", "--mutation", "-H", "--match",
         "-V", "--closest-relatives", "-q", "--break-ties", "--within-distance", "--distance-threshold", "-z", "--set-size", "-W", "--add-random",
@@ -1303,7 +1687,7 @@ int extract(int argc, char **argv) {   // extract_main, extract.cpp:149-640, 867
     for (int i = 0; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&](std::string &dst) -> bool {
-            if (i + 1 >= argc) { fprintf(stderr, "ERROR: %s needs a value\n", a.c_str()); extract_usage(stderr); return false; }
+            if (i + 1 >= argc) { fprintf(stderr, "ERROR: %s needs a value\n", a.c_str()); show_usage(stderr); return false; }
             dst = argv[++i];
             return true;
         };
@@ -1312,7 +1696,7 @@ int extract(int argc, char **argv) {   // extract_main, extract.cpp:149-640, 867
             if (!val(t)) return false;
             char *end = nullptr;
             dst = strtol(t.c_str(), &end, 10);
-            if (t.empty() || *end) { fprintf(stderr, "ERROR: bad value %s for %s\n", t.c_str(), a.c_str()); extract_usage(stderr); return false; }
+            if (t.empty() || *end) { fprintf(stderr, "ERROR: bad value %s for %s\n", t.c_str(), a.c_str()); show_usage(stderr); return false; }
             return true;
         };
         std::string tmp;
@@ -1335,7 +1719,15 @@ int extract(int argc, char **argv) {   // extract_main, extract.cpp:149-640, 867
         else if (a == "-v" || a == "--write-vcf") ok = val(fvcf);
         else if (a == "-n" || a == "--no-genotypes") no_genotypes = true;
         else if (a == "--host-genotypes") host_genotypes = true;
-        else if (a == "-h" || a == "--help") { extract_usage(stderr); return 0; }
+        else if (sel && (a == "-I" || a == "--get-internal-descendents")) ok = val(S.internal);
+        else if (sel && (a == "-c" || a == "--clade")) ok = val(S.clade);
+        else if (sel && (a == "-m" || a == "--mutation")) ok = val(S.mutation);
+        else if (sel && (a == "-H" || a == "--match")) ok = val(S.match);
+        else if (sel && (a == "-e" || a == "--max-epps")) { ok = ival(v); if (ok && v < 0) { fprintf(stderr, "ERROR: bad value %ld for %s\n", v, a.c_str()); return 1; } S.max_epps = v; }
+        else if (sel && (a == "-U" || a == "--from-mrca")) S.mrca = true;
+        else if (sel && (a == "-p" || a == "--prune")) S.prune = true;
+        else if (sel && a == "--host") S.host = true;
+        else if (a == "-h" || a == "--help") { show_usage(stderr); return 0; }
         else {
             for (const char *u : unsupported)
                 if (a == u) {
@@ -1343,12 +1735,12 @@ int extract(int argc, char **argv) {   // extract_main, extract.cpp:149-640, 867
                     return 1;
                 }
             fprintf(stderr, "ERROR: unknown option %s\n", a.c_str());
-            extract_usage(stderr);
+            show_usage(stderr);
             return 1;
         }
         if (!ok) return 1;
     }
-    if (in_mat.empty()) { fprintf(stderr, "ERROR: the option '--input-mat' is required but missing\n"); extract_usage(stderr); return 1; }
+    if (in_mat.empty()) { fprintf(stderr, "ERROR: the option '--input-mat' is required but missing\n"); show_usage(stderr); return 1; }
     struct stat sb;
     if (stat(dir.c_str(), &sb) != 0) {
         fprintf(stderr, "Creating output directory.\n\n");
@@ -1399,9 +1791,12 @@ int extract(int argc, char **argv) {   // extract_main, extract.cpp:149-640, 867
             samples = inter;
         }
     }
+    SelectDevice seldev(T, device);
+    if (sel && !select_before_filters(T, S, seldev, samples)) return 1;
     if (max_parsimony >= 0) { samples = get_parsimony_samples(T, samples, max_parsimony); if (samples.empty()) { fputs(none, stderr); return 1; } }
     if (max_branch >= 0) { samples = get_short_steppers(T, samples, max_branch); if (samples.empty()) { fputs(none, stderr); return 1; } }
     if (max_path >= 0) { samples = get_short_paths(T, samples, max_path); if (samples.empty()) { fputs(none, stderr); return 1; } }
+    if (sel && !select_after_filters(T, S, seldev, samples)) return 1;
     if (select_nearest > 0) {   // :429-440; the union in depth-first order (the reference: an unordered_set's)
         fprintf(stderr, "Selecting context samples...\n");
         std::vector<uh::Node *> qs;
@@ -1411,6 +1806,7 @@ int extract(int argc, char **argv) {   // extract_main, extract.cpp:149-640, 867
         samples.clear();
         for (const uh::Node *n : T.dfs()) if (set.count(n->id)) samples.push_back(n->id);
     }
+    if (sel && !select_prune(T, S, seldev, samples)) return 1;
     // :590-606: nothing selected = the whole tree
     uh::Tree sub;
     uh::Tree *out = &T;
@@ -1445,6 +1841,9 @@ int extract(int argc, char **argv) {   // extract_main, extract.cpp:149-640, 867
     }
     return 0;
 }
+
+int extract(int argc, char **argv) { return extract_or_select(argc, argv, false); }
+int select_samples(int argc, char **argv) { return extract_or_select(argc, argv, true); }
 
 // ---- summary (summary.cpp) ----------------------------------------------------------------------------------------
 
@@ -2493,6 +2892,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "summarize")) return summary(argc - 2, argv + 2);
     if (!strcmp(argv[1], "translate")) return translate(argc - 2, argv + 2);
     if (!strcmp(argv[1], "relatives")) return relatives(argc - 2, argv + 2);
-    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate, extract, summarize, translate, relatives)\n", argv[1]);
+    if (!strcmp(argv[1], "select")) return select_samples(argc - 2, argv + 2);
+    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate, extract, summarize, translate, relatives, select)\n", argv[1]);
     return 1;
 }

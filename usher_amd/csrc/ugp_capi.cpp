@@ -31,6 +31,7 @@
 #include "ugp_annotate.hpp"
 #include "ugp_nearest.hpp"
 #include "ugp_relatives.hpp"
+#include "ugp_select.hpp"
 #include "ugp_genotypes.hpp"
 #include "ugp_summary.hpp"
 #include "ugp_translate.hpp"
@@ -307,6 +308,7 @@ struct ugp_mat {
     ugp::GtState *gt = nullptr;      // matUtils extract -v tables (ugp_genotypes_attach), or none
     ugp::SmState *sm = nullptr;      // matUtils summary tables (ugp_summary_attach), or none
     ugp::TrState *tr = nullptr;      // matUtils summary --translate tables (ugp_translate_attach), or none
+    ugp::SelState *sel = nullptr;    // matUtils extract selector tables (ugp_select_attach), or none
     ugp::DfsTables *dfs = nullptr;   // the depth-first tables uncertainty and annotate share (their first attach), or none
     hipEvent_t kb_done = nullptr;    // behind the latest k_best8 launch of this handle ...
     hipStream_t kb_done_on = nullptr;   // ... on this stream
@@ -1433,6 +1435,7 @@ void ugp_mat_destroy(ugp_mat *m) {
     ugp::gt_free(m->gt);
     ugp::sm_free(m->sm);
     ugp::tr_free(m->tr);
+    ugp::sel_free(m->sel);
     ugp::dfs_tables_free(m->dfs);
     delete m;
 }
@@ -1975,6 +1978,48 @@ int ugp_relatives_time(ugp_mat *m, uint64_t n, const uint32_t *nodes, int within
     *count_ms = sum[0] / reps;
     *fill_ms = sum[1] / reps;
     return UGP_OK;
+}
+
+// ---- matUtils extract: sample selectors as leaf-rank bitmaps (ugp_select.hip) --------------------------------------------
+
+int ugp_select_attach(ugp_mat *m, const ugp_tree_desc *tree) {
+    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
+    if (int rc = check_handle_tree(m, tree)) return rc;
+    return ugp::sel_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->sel);
+}
+
+int ugp_select_leaves(ugp_mat *m, uint32_t *bfs_by_rank, uint64_t *n_leaves) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sel_leaves(m->sel, bfs_by_rank, n_leaves);
+}
+
+int ugp_select_mutations_chunked(ugp_mat *m, uint64_t n_mut, const int32_t *pos, const uint8_t *nuc, uint64_t *words, uint64_t *counts,
+                                 uint32_t chunk_queries) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sel_mutations(m->sel, n_mut, pos, nuc, words, counts, chunk_queries);
+}
+
+int ugp_select_mutations(ugp_mat *m, uint64_t n_mut, const int32_t *pos, const uint8_t *nuc, uint64_t *words, uint64_t *counts) {
+    return ugp_select_mutations_chunked(m, n_mut, pos, nuc, words, counts, 0);
+}
+
+int ugp_select_subtrees_chunked(ugp_mat *m, uint64_t n, const uint32_t *nodes, uint64_t *words, uint64_t *counts, uint32_t chunk_ranges) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sel_subtrees(m->sel, n, nodes, words, counts, chunk_ranges);
+}
+
+int ugp_select_subtrees(ugp_mat *m, uint64_t n, const uint32_t *nodes, uint64_t *words, uint64_t *counts) {
+    return ugp_select_subtrees_chunked(m, n, nodes, words, counts, 0);
+}
+
+int ugp_select_mrca(ugp_mat *m, const uint64_t *words, uint32_t *node, uint64_t *n_below) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sel_mrca(m->sel, words, node, n_below);
+}
+
+int ugp_select_time(ugp_mat *m, uint64_t n_mut, const int32_t *pos, const uint8_t *nuc, uint32_t reps, double *ms) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sel_time(m->sel, n_mut, pos, nuc, reps, ms);
 }
 
 // ---- matUtils extract -v: genotypes of a selection (ugp_genotypes.hip) -------------------------------------------------

@@ -133,6 +133,8 @@ struct DfsTables {
     DBuf<uint32_t> dpar, dend, depth, cum, moff, mbits, mnode, mlink, morig, poff, pent;
     DBuf<int32_t> mpos, nrp;
     DBuf<uint8_t> mflag, leaf;
+    DBuf<uint32_t> onode;      // per slot of pent the owner's node; made by the first translate or select attach (tr_owner_nodes)
+    bool have_onode = false;
     DfsView view() const {
         return DfsView{n, tp, dpar.p, dend.p, depth.p, cum.p, moff.p, mbits.p, mnode.p, mlink.p, morig.p, poff.p, pent.p,
                        mpos.p, nrp.p, mflag.p, leaf.p};

@@ -176,7 +176,7 @@ struct TrState {
     std::vector<int32_t> h_mpos;
     std::vector<uint8_t> h_mflag;
     DBuf<uint8_t> mpar;
-    DBuf<uint32_t> onode, d2b;
+    DBuf<uint32_t> d2b;
     // the codon table and its items
     bool have_codons = false;
     uint64_t nitems = 0, nnodes = 0, ndup = 0;
@@ -188,7 +188,7 @@ struct TrState {
     DBuf<uint8_t> flag;
     DBuf<uint32_t> seg, off, counters;
     DBuf<ugp_tr_record> rec, rout;
-    TrView view() const { return TrView{ient.p, icod.p, onode.p, spos.p, sinit.p, mpar.p, (uint32_t)nitems}; }
+    TrView view() const { return TrView{ient.p, icod.p, T->onode.p, spos.p, sinit.p, mpar.p, (uint32_t)nitems}; }
     ~TrState() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
@@ -198,7 +198,24 @@ void tr_free(TrState *s) {
     delete s;
 }
 
-static int tr_build(TrState *S, const ugp_tree_desc *tree) {
+int tr_owner_nodes(DfsTables *T, hipStream_t st) {
+    if (!T) return set_error(UGP_ERR_INVALID, "null argument");
+    if (T->have_onode) return UGP_OK;
+    UGP_HIP_TRY(hipSetDevice(T->device));
+    uint32_t npo = 0;
+    if (T->tp) UGP_HIP_TRY(hipMemcpyAsync(&npo, T->poff.p + T->tp, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    UGP_HIP_TRY(hipStreamSynchronize(st));
+    UGP_HIP_TRY(T->onode.alloc(npo));
+    if (npo) {
+        k_tr_onode<<<blocks_for(npo), kBlock, 0, st>>>(npo, T->pent.p, T->mnode.p, T->onode.p);
+        UGP_HIP_TRY(hipGetLastError());
+    }
+    UGP_HIP_TRY(hipStreamSynchronize(st));
+    T->have_onode = true;
+    return UGP_OK;
+}
+
+static int tr_build(TrState *S, DfsTables *tables, const ugp_tree_desc *tree) {
     const DfsTables &T = *S->T;
     const uint32_t N = T.n;
     const uint64_t M = T.m;
@@ -212,16 +229,8 @@ static int tr_build(TrState *S, const ugp_tree_desc *tree) {
     }
     UGP_HIP_TRY(S->mpar.upload(tree->mut_par, M, st));
     UGP_HIP_TRY(S->d2b.upload(S->dfs2bfs->data(), N, st));
-    uint32_t npo = 0;
-    if (T.tp) UGP_HIP_TRY(hipMemcpyAsync(&npo, T.poff.p + T.tp, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     UGP_HIP_TRY(hipStreamSynchronize(st));
-    UGP_HIP_TRY(S->onode.alloc(npo));
-    if (npo) {
-        k_tr_onode<<<blocks_for(npo), kBlock, 0, st>>>(npo, T.pent.p, T.mnode.p, S->onode.p);
-        UGP_HIP_TRY(hipGetLastError());
-    }
-    UGP_HIP_TRY(hipStreamSynchronize(st));
-    return UGP_OK;
+    return tr_owner_nodes(tables, st);
 }
 
 int tr_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
@@ -243,7 +252,7 @@ int tr_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, c
         S->T = *tables;
         S->dfs2bfs = &dfs2bfs;
         if (hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking) != hipSuccess) { delete S; return set_error(UGP_ERR_HIP, "hipStreamCreate failed"); }
-        if (int rc2 = tr_build(S, tree)) { (void)hipStreamSynchronize(S->stream); delete S; return rc2; }
+        if (int rc2 = tr_build(S, *tables, tree)) { (void)hipStreamSynchronize(S->stream); delete S; return rc2; }
         tr_free(*out);
         *out = S;
     } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }

@@ -1,6 +1,7 @@
 // ugp_translate.hpp -- matUtils summary --translate (matUtils/translate.cpp) on the device: per node the codons its mutations touch and
 // their letters before and after, over the depth-first tables of ugp_dense.hpp and their per-position owner lists.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <vector>
@@ -18,6 +19,8 @@ struct TrState;
 int tr_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
               DfsTables **tables, TrState **out);
 void tr_free(TrState *s);
+// The owners' nodes by list slot (tables->onode), made once per tables whoever asks first: translate and select both search them.
+int tr_owner_nodes(DfsTables *tables, hipStream_t stream);
 // As ugp_translate_codons / ugp_translate_chunked / ugp_translate_time document them.
 int tr_codons(TrState *s, uint64_t n_codons, const int32_t *slot_pos, const uint8_t *slot_init);
 int tr_run(TrState *s, ugp_tr_record *out, uint64_t cap, uint64_t *n_out, ugp_tr_info *info, uint64_t chunk_items);

@@ -616,6 +616,88 @@ class Placer:
         self._ck(self._L.ugp_relatives_time(self._h, len(nodes), _ptr(nodes), int(bool(within)), int(threshold), int(reps), C.byref(a), C.byref(b)))
         return float(a.value), float(b.value)
 
+    # ---- matUtils extract's selectors as leaf-rank bitmaps (ugp_select_*) ----------------------------------------------------
+    def select_attach(self, arrays: Optional[Dict] = None):
+        """ugp_select_attach with the placer's own tree, or with other mutation arrays on the same topology: the leaf-rank tables
+        of the select calls.  The depth-first tables are shared as genotypes_attach describes."""
+        t = self._t if arrays is None else _TreeArrays(arrays)
+        self._ck(self._L.ugp_select_attach(self._h, C.byref(t.desc)))
+        n = C.c_uint64(0)
+        self._ck(self._L.ugp_select_leaves(self._h, None, C.byref(n)))
+        self._sel_leaves = int(n.value)
+
+    def _sel_n(self) -> int:
+        if getattr(self, "_sel_leaves", None) is None:
+            self.select_attach()
+        return self._sel_leaves
+
+    @staticmethod
+    def _sel_mask(words, n_leaves) -> np.ndarray:
+        return np.unpackbits(words.view(np.uint8), bitorder="little")[:n_leaves].astype(bool)
+
+    @staticmethod
+    def _sel_words(mask, n_leaves) -> np.ndarray:
+        mask = np.ascontiguousarray(mask, dtype=bool)
+        if len(mask) != n_leaves:
+            raise UgpError(-1, "mask holds one flag per leaf")
+        bits = np.zeros(((n_leaves + 63) // 64) * 64, np.uint8)
+        bits[:n_leaves] = mask
+        return np.ascontiguousarray(np.packbits(bits, bitorder="little")).view(np.uint64)
+
+    def select_leaves(self) -> np.ndarray:
+        """The leaves in depth-first order, as BFS indices: leaf rank r of the select masks is select_leaves()[r]."""
+        out = np.zeros(self._sel_n(), np.uint32)
+        self._ck(self._L.ugp_select_leaves(self._h, _ptr(out) if len(out) else None, None))
+        return out
+
+    def select_mutations(self, pos, nuc, chunk_queries: int = 0):
+        """get_mutation_samples (select.cpp:67-111) for the queries (pos[q], nuc[q]): (mask, counts) -- mask a bool array by leaf
+        rank, the OR over the queries; counts[q] the leaves of query q alone.  A leaf has a mutation when the nearest node on its
+        root path, itself included, with an entry at the position carries exactly that allele there.  chunk_queries (test hook):
+        queries staged per launch.  The self._sel_words of the last call keep the raw words."""
+        nl = self._sel_n()
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        nuc = np.ascontiguousarray(nuc, dtype=np.uint8)
+        if len(pos) != len(nuc):
+            raise UgpError(-1, "pos and nuc hold one value per query")
+        words = np.full((nl + 63) // 64, 0xA5A5A5A5A5A5A5A5, np.uint64)
+        counts = np.zeros(len(pos), np.uint64)
+        self._ck(self._L.ugp_select_mutations_chunked(self._h, len(pos), _ptr(pos) if len(pos) else None, _ptr(nuc) if len(pos) else None,
+                                                      _ptr(words),
+                                                      _ptr(counts) if len(pos) else None, int(chunk_queries)))
+        self._sel_raw = words
+        return self._sel_mask(words, nl), counts
+
+    def select_subtrees(self, nodes, chunk_ranges: int = 0):
+        """(mask, counts): the union of the leaves below the nodes (BFS indices; a leaf selects itself), counts[i] per node."""
+        nl = self._sel_n()
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
+        words = np.full((nl + 63) // 64, 0xA5A5A5A5A5A5A5A5, np.uint64)
+        counts = np.zeros(len(nodes), np.uint64)
+        self._ck(self._L.ugp_select_subtrees_chunked(self._h, len(nodes), _ptr(nodes) if len(nodes) else None,
+                                                     _ptr(words),
+                                                     _ptr(counts) if len(nodes) else None, int(chunk_ranges)))
+        self._sel_raw = words
+        return self._sel_mask(words, nl), counts
+
+    def select_mrca(self, mask):
+        """(node, n_below): the deepest node (BFS index) whose subtree holds every leaf of `mask` (bool by leaf rank), and the
+        leaves below it.  An empty mask raises UgpError -1."""
+        nl = self._sel_n()
+        words = self._sel_words(mask, nl)
+        node, below = C.c_uint32(0), C.c_uint64(0)
+        self._ck(self._L.ugp_select_mrca(self._h, _ptr(words), C.byref(node), C.byref(below)))
+        return int(node.value), int(below.value)
+
+    def select_time(self, pos, nuc, reps: int = 5) -> float:
+        """Bench hook: milliseconds of device time of the mutation kernel alone over these queries."""
+        self._sel_n()
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        nuc = np.ascontiguousarray(nuc, dtype=np.uint8)
+        ms = C.c_double(0)
+        self._ck(self._L.ugp_select_time(self._h, len(pos), _ptr(pos), _ptr(nuc), int(reps), C.byref(ms)))
+        return float(ms.value)
+
     RIPPLES_EVENT = np.dtype([("branch", np.uint64), ("i", np.uint32), ("j", np.uint32), ("donor", np.uint32), ("acceptor", np.uint32),
                               ("donor_count", np.uint32), ("acceptor_count", np.uint32), ("donor_score", np.int32),
                               ("acceptor_score", np.int32), ("donor_sibling", np.uint8), ("acceptor_sibling", np.uint8),
