@@ -609,6 +609,13 @@ int ugp_get_timing_sum(ugp_mat *mat, ugp_timing *sum, uint32_t *n_calls);
  * call built them: cum_over / cum_under per block of 16 packed-stream words.  *n_blocks = entries per tile (0: that call did not
  * use the bound); with over == NULL only the count is returned.  Blocking; the caller checks `tile` against its own batch. */
 int ugp_debug_bound3_tables(ugp_mat *mat, uint32_t tile, uint16_t *over, uint16_t *under, uint64_t cap, uint64_t *n_blocks);
+/* Test hook: builds the third bound's tables from nibbles the caller supplies, as the tile builders would have left them:
+ * useful[n_tiles][(n_sites + 7) / 8], one nibble per site (bit a: allele a is useful for the tile), 1..96 tiles.  Runs the three
+ * table kernels into buffers of its own (never the ones a placement call reads) and returns, tile-major, over / under
+ * [n_tiles][n_blocks] and the maxima l1 [n_tiles][ceil(n_blocks / 64)], l2 [..][ceil(that / 64)], l3 likewise.  *n_blocks = blocks per
+ * tile; with every output NULL only that is returned.  Blocking.  UGP_ERR_UNSUPPORTED for a handle without event lists. */
+int ugp_debug_bound3_build(ugp_mat *mat, const uint32_t *useful, uint32_t n_tiles, uint8_t *over, uint8_t *under, uint8_t *l1, uint8_t *l2, uint8_t *l3,
+                           uint64_t *n_blocks);
 /* Test hook: only the locality pre-pass of a batch, by method (0: the walk of the coarse tree, 1: the pass from the samples' own
  * rows, refused with UGP_ERR_UNSUPPORTED where a call would not take it).  Blocking.  cost / coarse_node: [n_queries]; kept_bfs
  * (optional, room for kept_cap): the BFS indices of the coarse tree's nodes, which coarse_node indexes. */

@@ -141,6 +141,7 @@ SYMBOLS = {
     "ugp_get_timing": (C.c_int, [P, C.POINTER(ugp_timing)]),
     "ugp_get_timing_sum": (C.c_int, [P, C.POINTER(ugp_timing), C.POINTER(C.c_uint32)]),
     "ugp_debug_bound3_tables": (C.c_int, [P, C.c_uint32, P, P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ugp_debug_bound3_build": (C.c_int, [P, P, C.c_uint32, P, P, P, P, P, C.POINTER(C.c_uint64)]),
     "ugp_debug_coarse_pass": (C.c_int, [P, P, C.c_int, P, P, P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ugp_debug_last_prepass": (C.c_int, [P]),
     "ugp_last_error": (C.c_char_p, []),

@@ -2841,6 +2841,38 @@ int ugp_debug_bound3_tables(ugp_mat *m, uint32_t tile, uint16_t *over, uint16_t 
     return UGP_OK;
 }
 
+// Test hook: the three table kernels (ugp_bound3.hip) on nibbles the caller hands over, blocking.  Everything lives in buffers of the
+// hook's own -- the walk caches the addresses of the workspace's tables in B3Dev, and a call in flight may be reading them.
+int ugp_debug_bound3_build(ugp_mat *m, const uint32_t *useful, uint32_t n_tiles, uint8_t *over, uint8_t *under, uint8_t *l1, uint8_t *l2, uint8_t *l3,
+                           uint64_t *n_blocks) {
+    if (!m || !n_blocks) return fail(UGP_ERR_INVALID, "null argument");
+    if (!m->d_b3_events.p) return fail(UGP_ERR_UNSUPPORTED, "this handle has no event lists");
+    const uint32_t nb = ugp::b3_blocks(m->stream8_dwords), n_l1 = ugp::b3_div64(nb), n_l2 = ugp::b3_div64(n_l1), n_l3 = ugp::b3_div64(n_l2);
+    *n_blocks = nb;
+    if (!over && !under && !l1 && !l2 && !l3) return UGP_OK;   // (only the size)
+    if (!useful || !over || !under || !l1 || !l2 || !l3) return fail(UGP_ERR_INVALID, "null argument");
+    if (!n_tiles || n_tiles > 96) return fail(UGP_ERR_INVALID, "n_tiles must be 1..96");
+    HIP_TRY(hipSetDevice(m->device));
+    const uint32_t n_sites = m->flat.n_sites, useful_words = (n_sites + 7) / 8;
+    DevBuf<uint32_t> d_useful, d_pairmask;
+    DevBuf<uint8_t> d_over, d_under, d_l1, d_l2, d_l3;
+    HIP_TRY(d_useful.reserve((size_t)n_tiles * useful_words));
+    HIP_TRY(d_pairmask.reserve((size_t)((n_tiles + 31) / 32) * n_sites * 4));
+    HIP_TRY(d_over.reserve((size_t)n_tiles * nb)); HIP_TRY(d_under.reserve((size_t)n_tiles * nb));
+    HIP_TRY(d_l1.reserve((size_t)n_tiles * n_l1)); HIP_TRY(d_l2.reserve((size_t)n_tiles * n_l2)); HIP_TRY(d_l3.reserve((size_t)n_tiles * n_l3));
+    HIP_TRY(hipMemcpy(d_useful.p, useful, (size_t)n_tiles * useful_words * 4, hipMemcpyHostToDevice));
+    // (0xEE in front: an entry the kernels leave out shows)
+    HIP_TRY(hipMemset(d_over.p, 0xEE, (size_t)n_tiles * nb)); HIP_TRY(hipMemset(d_under.p, 0xEE, (size_t)n_tiles * nb));
+    HIP_TRY(hipMemset(d_l1.p, 0xEE, (size_t)n_tiles * n_l1)); HIP_TRY(hipMemset(d_l2.p, 0xEE, (size_t)n_tiles * n_l2)); HIP_TRY(hipMemset(d_l3.p, 0xEE, (size_t)n_tiles * n_l3));
+    HIP_TRY(ugp::launch_b3_tables(d_useful.p, useful_words, n_sites, n_tiles, m->d_b3_group_off.p, m->d_b3_events.p, nb, d_pairmask.p, d_over.p, d_under.p, d_l1.p,
+                                  d_l2.p, d_l3.p, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(over, d_over.p, (size_t)n_tiles * nb, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(under, d_under.p, (size_t)n_tiles * nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(l1, d_l1.p, (size_t)n_tiles * n_l1, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(l2, d_l2.p, (size_t)n_tiles * n_l2, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(l3, d_l3.p, (size_t)n_tiles * n_l3, hipMemcpyDeviceToHost));
+    return UGP_OK;
+}
+
 // Test hook: only the pre-pass of a batch, by the method the caller names (0: the walk of the coarse tree, 1: k_coarse_sparse, refused
 // where the plan would not take it), blocking.  Per sample the cost and the coarse node (an index into the kept nodes); kept_bfs, if
 // given, receives the kept nodes' BFS indices in the full tree.

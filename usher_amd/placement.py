@@ -801,6 +801,23 @@ class Placer:
         self._ck(self._L.ugp_debug_coarse_pass(self._h, qset, {"walked": 0, "sparse": 1}[method], _ptr(cost), _ptr(node), _ptr(kept), len(kept), C.byref(n)))
         return cost, node, kept[:int(n.value)].copy()
 
+    def bound3_build(self, useful: np.ndarray) -> Dict[str, np.ndarray]:
+        """ugp_debug_bound3_build (test hook): the third bound's tables from useful[n_tiles][(n_sites + 7) // 8] (uint32, one nibble per
+        site, as the tile builders leave them).  Returns over / under [n_tiles][n_blocks] and the maxima l1 / l2 / l3 (uint8)."""
+        useful = np.ascontiguousarray(useful, np.uint32)
+        n_tiles = useful.shape[0]
+        if useful.ndim != 2 or useful.shape[1] != (int(self.info()["n_sites"]) + 7) // 8:
+            raise ValueError("useful must be [n_tiles][(n_sites + 7) // 8]")
+        n = C.c_uint64()
+        self._ck(self._L.ugp_debug_bound3_build(self._h, None, n_tiles, None, None, None, None, None, C.byref(n)))
+        sizes = [int(n.value)]
+        for _ in range(3):
+            sizes.append((sizes[-1] + 63) // 64)
+        out = {k: np.zeros((n_tiles, s), np.uint8) for k, s in zip(("over", "under", "l1", "l2", "l3"), [sizes[0]] + sizes)}
+        self._ck(self._L.ugp_debug_bound3_build(self._h, _ptr(useful), n_tiles, _ptr(out["over"]), _ptr(out["under"]), _ptr(out["l1"]), _ptr(out["l2"]),
+                                                _ptr(out["l3"]), C.byref(n)))
+        return out
+
     def last_prepass(self) -> str:
         """ugp_debug_last_prepass (test hook): the pre-pass the latest placement call took."""
         return ("none", "walked", "sparse")[int(self._L.ugp_debug_last_prepass(self._h))]
