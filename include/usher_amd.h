@@ -471,6 +471,41 @@ int ugp_select_mrca(ugp_mat *mat, const uint64_t *words, uint32_t *node /* BFS *
 /* Bench hook: milliseconds of device time of the mutation kernel alone over these queries (the bitmap and the counts stay on the
  * device); mean of `reps` runs after one warm-up run. */
 int ugp_select_time(ugp_mat *mat, uint64_t n_mut, const int32_t *pos, const uint8_t *nuc, uint32_t reps, double *ms);
+/* matUtils mask (matUtils/mask.cpp: restrictSamples :802-905, restrictMutationsLocally :703-800), both in closed form over the
+ * depth-first ranges.  A mutation's KEY is (position, parent allele as stored, allele); entries are those of the mutation CSR.
+ * ugp_mask_attach shares the depth-first tables of `tree` (the handle's tree; arrays are copied; tables built from other mutation
+ * arrays: UGP_ERR_INVALID, nothing changed; an allele above 15: UGP_ERR_UNSUPPORTED) and builds, once per handle, the leaf-rank
+ * ranges and per entry its stored alleles.  A second attach replaces the first.  A call before the attach is UGP_ERR_INVALID.
+ * ugp_mask_restricted: the n named nodes (BFS; one given twice counts once; n = 0 and a node out of range are UGP_ERR_INVALID before
+ *   anything is written) must be leaves: a named internal node is UGP_ERR_UNSUPPORTED (roots can nest then; the caller walks), and so
+ *   is a tree whose positions reach past the bounded key table.  With full(v): every leaf below v is named, and F: the inner nodes
+ *   that are full and have a leaf child, the restricted roots are the nodes of F with no proper ancestor in F and the named leaves
+ *   whose parent is not full (or absent).  roots_bfs = the first min(roots_cap, *n_roots) of them in depth-first order.
+ *   entry_masked[e] = 1 exactly when entry e is non-masked, lies at or below a root, and no non-masked entry with the same key lies
+ *   on a node below no root; else 0.  *n_masked = their number.  The tree arrays are not changed.
+ * ugp_mask_mutations: line l = (pos, par, nuc, node_bfs, excluded nodes excl_bfs[excl_off[l] .. excl_off[l + 1])); par and nuc are
+ *   4-bit codes, 15 matches any.  Line l matches a non-masked entry on node v when the position is equal, par and nuc match the
+ *   stored parent allele and allele, v lies at or below the line's node, and v lies at or below no excluded node that is a strict
+ *   descendant of the line's node (other excluded nodes, and indices that are no node, have no effect).  first_line[e] = the first
+ *   line in the order given that matches entry e, or UINT32_MAX; entries with skip[e] != 0 (skip may be NULL) never match.
+ *   counts[l] = the entries with first_line == l.  A line's node out of range, an allele above 15 or offsets that do not ascend
+ *   from 0 are UGP_ERR_INVALID before anything is written.  The _chunked twin (test hook) sets the lines staged per launch
+ *   (0: default). */
+int ugp_mask_attach(ugp_mat *mat, const ugp_tree_desc *tree);
+int ugp_mask_restricted(ugp_mat *mat, uint64_t n, const uint32_t *leaves_bfs, uint8_t *entry_masked /* [n_muts] */,
+                        uint32_t *roots_bfs /* [roots_cap] */, uint64_t roots_cap, uint64_t *n_roots, uint64_t *n_masked);
+int ugp_mask_mutations(ugp_mat *mat, uint64_t n_lines, const int32_t *pos, const uint8_t *par, const uint8_t *nuc, const uint32_t *node_bfs,
+                       const uint64_t *excl_off /* [n_lines + 1] */, const uint32_t *excl_bfs, const uint8_t *skip /* [n_muts], or NULL */,
+                       uint32_t *first_line /* [n_muts] */, uint64_t *counts /* [n_lines] */);
+int ugp_mask_mutations_chunked(ugp_mat *mat, uint64_t n_lines, const int32_t *pos, const uint8_t *par, const uint8_t *nuc,
+                               const uint32_t *node_bfs, const uint64_t *excl_off, const uint32_t *excl_bfs, const uint8_t *skip,
+                               uint32_t *first_line, uint64_t *counts, uint32_t chunk_lines);
+/* Bench hook: milliseconds of device time of the passes alone, no copies: *restricted_ms for the n named leaves (n = 0: not run, 0),
+ * *mutations_ms for the lines (n_lines = 0: not run, 0; no more than one default batch); each the mean of `reps` runs after one
+ * warm-up run. */
+int ugp_mask_time(ugp_mat *mat, uint64_t n, const uint32_t *leaves_bfs, uint64_t n_lines, const int32_t *pos, const uint8_t *par,
+                  const uint8_t *nuc, const uint32_t *node_bfs, const uint64_t *excl_off, const uint32_t *excl_bfs, uint32_t reps,
+                  double *restricted_ms, double *mutations_ms);
 /* RIPPLES (ripples/main.cpp): the options of :22-44 that the search reads. branch_len >= 1 and parsimony_improvement >= 0
  * (UGP_ERR_INVALID otherwise: the reference's size_t arithmetic of :445-453 is not reproduced for negative values). */
 typedef struct ugp_ripples_opts {

@@ -217,6 +217,15 @@ Node *Tree::get_node(const std::string &id) const {
     return all_nodes.find(id);
 }
 
+bool Tree::rename_node(const std::string &old_id, const std::string &new_id) {   // :802-816
+    Node *n = all_nodes.find(old_id);
+    if (!n || all_nodes.find(new_id)) return false;
+    all_nodes.erase(old_id);
+    n->id = new_id;
+    all_nodes.set(new_id, n);
+    return true;
+}
+
 Node *Tree::create_node(const std::string &id, Node *parent, float branch_length) {   // :881-910
     if (parent) {
         if (all_nodes.find(id)) return nullptr;   // "already in the tree"

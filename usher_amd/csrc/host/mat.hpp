@@ -97,6 +97,7 @@ struct Tree {                 // mutation_annotated_tree.hpp:113-161
     Node *get_node(const std::string &id) const;
     size_t num_annotations() const { return root ? root->clade_annotations.size() : 0; }
     Node *create_node(const std::string &id, Node *parent, float branch_length = -1.0f);   // :881-910
+    bool rename_node(const std::string &old_id, const std::string &new_id);   // :802-816; false (no change): unknown old or taken new name
     std::vector<Node *> bfs() const;   // :1225-1251
     std::vector<Node *> dfs(Node *from = nullptr) const;   // :1253-1273
     std::vector<Node *> rsearch(Node *n, bool include_self) const;   // :931-948

@@ -8,6 +8,7 @@
 //   matutils-amd translate -i tree.pb -g genes.gtf -f ref.fa -t out.tsv [-d dir] [--host]
 //   matutils-amd relatives -i tree.pb [-s samples.txt] [-V closest.tsv [-q]] [--within-distance within.tsv [--distance-threshold n]] [--host]
 //   matutils-amd select   extract's options and [-I node] [-c clades] [-m mutations] [-H regex] [-e n] [-U] [-p] [--host]
+//   matutils-amd mask -i tree.pb -o out.pb [-s samples.txt] [-m mutations.tsv] [-r rename.tsv] [-c] [--host]
 //
 // uncertainty_main / findEPPs_wrapper (uncertainty.cpp:279-339, 541-560): load the MAT, uncondense its leaves, read the sample
 // names, and for every sample report its equally parsimonious placements and neighborhood size (-e) and the candidate parents
@@ -27,6 +28,8 @@
 // runs the reference's walk statement by statement.  `extract` itself goes on refusing the four options.
 // extract's selectors -I -c -m -H -e -U -p (extract.cpp:294-373, 411-427, 455-472), as the subcommand `select`, which shares extract's
 // body: the selections are bitmaps over leaf ranks from ugp_select.hip, -e asks ugp_uncertainty; --host runs the reference's walks.
+// mask_main (mask.cpp:68-159), as the subcommand `mask`: -s (restrictSamples) and -m (restrictMutationsLocally) ask ugp_mask.hip which
+// entries to mask or remove and apply the answer to the host tree; -r, -c and the writer run on the host; --host walks as the reference.
 #include <hip/hip_runtime_api.h>
 #include <sys/stat.h>
 #include <zlib.h>
@@ -65,7 +68,7 @@ void usage(FILE *f) {
             "      --device             HIP device ordinal [0]\n"
             "  (-d / --dropout-mutations is not supported)\n"
             "       matutils-amd annotate --help | matutils-amd extract --help | matutils-amd summarize --help | matutils-amd translate --help\n"
-            "       matutils-amd relatives --help | matutils-amd select --help\n");
+            "       matutils-amd relatives --help | matutils-amd select --help | matutils-amd mask --help\n");
 }
 
 int uncertainty(int argc, char **argv) {
@@ -2881,6 +2884,375 @@ int relatives(int argc, char **argv) {
     return 0;
 }
 
+// ---- mask (mask.cpp) ---------------------------------------------------------------------------------------------
+
+void mask_usage(FILE *f) {
+    fprintf(f,
+            "Usage: matutils-amd mask -i tree.pb -o out.pb [-s samples.txt] [-m mutations.tsv] [-r rename.tsv] [-c] [-T n] [--device k] [--host]\n"
+            "  -i, --input-mat          input mutation-annotated tree [REQUIRED]\n"
+            "  -o, --output-mat         output mutation-annotated tree [REQUIRED]\n"
+            "  -s, --restricted-samples sample names, one per line: mutations private to them are masked\n"
+            "  -m, --mask-mutations     lines of mutation[<TAB>node[<TAB>excluded;excluded]] (commas when the name contains .csv): the\n"
+            "                           mutation is removed below the node (the root when none is given), not below the excluded nodes\n"
+            "  -r, --rename-samples     two-column tsv: old name, new name\n"
+            "  -c, --condense-tree      collapse the tree and condense identical leaves before it is written\n"
+            "  -T, --threads            accepted for compatibility\n"
+            "      --device             HIP device ordinal [0]\n"
+            "      --host               run -s and -m as the reference's walks on the host (slow)\n"
+            "  The steps run in the reference's order: -s, -m, -r, -c.  'Masking mutation' lines come in depth-first order.\n"
+            "  (-S / --simplify, -M / --move-nodes, -D / --max-snp-distance and -f / --maple-file are not supported)\n");
+}
+
+struct MaskLine {
+    uh::Mutation mut;
+    uh::Node *node = nullptr;
+    std::set<std::string> exclude;
+};
+
+// The tree flattened for both paths: breadth-first nodes (flat_index), and per breadth-first index the depth-first position and
+// the end of the subtree's depth-first range.
+struct MaskFlat {
+    std::vector<uh::Node *> bfs, dfs;
+    std::vector<uint32_t> dpos, dend;
+    void make(const uh::Tree &T) {
+        bfs = T.bfs();
+        dfs = T.dfs();
+        const size_t N = bfs.size();
+        for (size_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
+        dpos.resize(N);
+        dend.resize(N);
+        for (size_t i = 0; i < N; i++) dpos[dfs[i]->flat_index] = (uint32_t)i;
+        std::vector<uint32_t> sz(N, 1);
+        for (size_t i = N; i-- > 1;) sz[dpos[dfs[i]->parent->flat_index]] += sz[i];
+        for (size_t i = 0; i < N; i++) dend[dfs[i]->flat_index] = (uint32_t)i + sz[i];
+    }
+};
+
+// restrictSamples' three loops (:820-904) statement by statement.  `marks` receives (node, entry) of every entry to mask; the
+// leaves below an ancestor are enumerated breadth-first as get_leaves_ids does, up to the first one that is not named.
+size_t host_restricted(const uh::Tree &T, const MaskFlat &F, const std::vector<std::string> &names,
+                       std::vector<std::pair<uh::Node *, size_t>> &marks) {
+    std::unordered_set<std::string> restricted(names.begin(), names.end());
+    std::unordered_set<uh::Node *> roots;
+    std::unordered_map<std::string, bool> visited;
+    for (const auto &s : restricted) visited[s] = false;
+    std::vector<uh::Node *> queue;
+    for (uh::Node *cn : F.bfs) {
+        if (!restricted.count(cn->id) || visited[cn->id]) continue;
+        uh::Node *curr = cn;
+        for (uh::Node *n : T.rsearch(cn, false)) {
+            bool found_unrestricted = false;
+            queue.assign(1, n);
+            for (size_t h = 0; h < queue.size() && !found_unrestricted; h++) {
+                if (queue[h]->is_leaf()) found_unrestricted = !restricted.count(queue[h]->id);
+                else queue.insert(queue.end(), queue[h]->children.begin(), queue[h]->children.end());
+            }
+            if (!found_unrestricted) {
+                for (uh::Node *l : queue) if (l->is_leaf()) visited[l->id] = true;
+                curr = n;
+                break;
+            }
+        }
+        roots.insert(curr);
+    }
+    std::unordered_map<std::string, int> counts;
+    for (uh::Node *n : F.dfs)
+        for (const auto &m : n->mutations) if (!m.masked()) counts[m.str()] += 1;
+    std::vector<uh::Node *> ordered(roots.begin(), roots.end());   // depth-first order, where the reference iterates the set
+    std::sort(ordered.begin(), ordered.end(), [&](uh::Node *a, uh::Node *b) { return F.dpos[a->flat_index] < F.dpos[b->flat_index]; });
+    for (uh::Node *r : ordered)
+        for (uh::Node *n : T.dfs(r))
+            for (const auto &m : n->mutations) if (!m.masked()) counts[m.str()] -= 1;
+    std::unordered_set<const uh::Mutation *> done;   // an entry below two nested roots is masked on the first visit
+    for (uh::Node *r : ordered)
+        for (uh::Node *n : T.dfs(r))
+            for (size_t k = 0; k < n->mutations.size(); k++) {
+                const auto &m = n->mutations[k];
+                if (m.masked() || counts[m.str()] != 0 || !done.insert(&m).second) continue;
+                marks.emplace_back(n, k);
+            }
+    return roots.size();
+}
+
+bool mask_match(const uh::Mutation &target, const uh::Mutation &query) {   // match_mutations, :703-721
+    if (target.position != query.position) return false;
+    if (target.ref_nuc != 0b1111 && target.par_nuc != query.par_nuc) return false;
+    if (target.mut_nuc != 0b1111 && target.mut_nuc != query.mut_nuc) return false;
+    return true;
+}
+
+size_t host_mask_on_branch(uh::Node *node, const MaskLine &L) {   // mask_mutation_on_branch, :723-744
+    size_t masked = 0;
+    auto &ms = node->mutations;
+    for (size_t k = 0; k < ms.size();)
+        if (mask_match(L.mut, ms[k])) { masked++; ms.erase(ms.begin() + k); } else k++;
+    for (uh::Node *child : node->children) {
+        if (!L.exclude.count(child->id)) masked += host_mask_on_branch(child, L);
+        else fprintf(stderr, "Excluding %s for position %d\n", child->id.c_str(), L.mut.position);
+    }
+    return masked;
+}
+
+struct MaskDevice {
+    std::vector<uint32_t> parent;
+    std::vector<uint64_t> mut_off;
+    std::vector<int32_t> pos;
+    std::vector<uint8_t> ref, par, nuc;
+    ugp_mat *h = nullptr;
+    ~MaskDevice() { if (h) ugp_mat_destroy(h); }
+    void up(const MaskFlat &F, int device) {
+        const uint64_t N = F.bfs.size();
+        parent.resize(N);
+        mut_off.assign(N + 1, 0);
+        for (uint64_t j = 0; j < N; j++) {
+            parent[j] = F.bfs[j]->parent ? F.bfs[j]->parent->flat_index : UINT32_MAX;
+            for (const auto &m : F.bfs[j]->mutations) {
+                pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
+            }
+            mut_off[j + 1] = pos.size();
+        }
+        // the handle takes the bare topology, the mask tables the mutations as they are stored (masked, repeated positions)
+        const std::vector<uint64_t> no_off(N + 1, 0);
+        if (pos.empty()) { pos.push_back(0); ref.push_back(0); par.push_back(0); nuc.push_back(0); }   // (never read: no null arrays)
+        const ugp_tree_desc bare{N, parent.data(), no_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+        const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+        if (ugp_mat_create(&bare, device, &h) != UGP_OK) lib_fail("ugp_mat_create");
+        if (ugp_mask_attach(h, &desc) != UGP_OK) lib_fail("ugp_mask_attach");
+    }
+};
+
+int mask(int argc, char **argv) {   // mask_main, :68-159
+    std::string mat, out, samples, mutations, rename;
+    bool recondense = false, host = false;
+    int device = 0;
+    for (int i = 0; i < argc; i++) {
+        const std::string a = argv[i];
+        auto val = [&](std::string &dst) -> bool {
+            if (i + 1 >= argc) { fprintf(stderr, "ERROR: %s needs a value\n", a.c_str()); mask_usage(stderr); return false; }
+            dst = argv[++i];
+            return true;
+        };
+        std::string tmp;
+        bool ok = true;
+        if (a == "-i" || a == "--input-mat") ok = val(mat);
+        else if (a == "-o" || a == "--output-mat") ok = val(out);
+        else if (a == "-s" || a == "--restricted-samples") ok = val(samples);
+        else if (a == "-m" || a == "--mask-mutations") ok = val(mutations);
+        else if (a == "-r" || a == "--rename-samples") ok = val(rename);
+        else if (a == "-c" || a == "--condense-tree") recondense = true;
+        else if (a == "-T" || a == "--threads") ok = val(tmp);
+        else if (a == "--device") { ok = val(tmp); device = atoi(tmp.c_str()); }
+        else if (a == "--host") host = true;
+        else if (a == "-h" || a == "--help") { mask_usage(stdout); return 0; }
+        else if (a == "-S" || a == "--simplify" || a == "-M" || a == "--move-nodes" || a == "-D" || a == "--max-snp-distance" || a == "-f" ||
+                 a == "--maple-file") {
+            fprintf(stderr, "ERROR: %s is not supported by matutils-amd mask (use the reference matUtils)\n", a.c_str());
+            return 1;
+        }
+        else { fprintf(stderr, "ERROR: unknown option %s\n", a.c_str()); mask_usage(stderr); return 1; }
+        if (!ok) return 1;
+    }
+    if (mat.empty()) { fprintf(stderr, "ERROR: the option '--input-mat' is required but missing\n"); mask_usage(stderr); return 1; }
+    if (out.empty()) { fprintf(stderr, "ERROR: the option '--output-mat' is required but missing\n"); mask_usage(stderr); return 1; }
+    auto clock = [] { return std::chrono::steady_clock::now(); };
+    auto done = [&](std::chrono::steady_clock::time_point t0, const char *end) {
+        fprintf(stderr, "Completed in %ld msec %s", (long)std::chrono::duration_cast<std::chrono::milliseconds>(clock() - t0).count(), end);
+    };
+    fprintf(stderr, "Loading input MAT file %s.\n", mat.c_str());
+    auto t0 = clock();
+    uh::Tree T;
+    std::string err;
+    if (!uh::load_mat(mat, T, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+    done(t0, "\n\n");
+    if (!T.condensed_nodes.empty()) {
+        fprintf(stderr, "Uncondensing condensed nodes...\n");
+        t0 = clock();
+        T.uncondense_leaves();
+        done(t0, "\n\n");
+    }
+    MaskFlat F;
+    MaskDevice D;
+    if (!samples.empty() || !mutations.empty()) {
+        F.make(T);
+        if (!host) {
+            t0 = clock();
+            D.up(F, device);
+            fprintf(stderr, "Tree on device %d in %ld msec\n", device, (long)std::chrono::duration_cast<std::chrono::milliseconds>(clock() - t0).count());
+        }
+    }
+    std::vector<uint8_t> entry_masked;   // per entry of D's CSR: -s masked it
+    if (!samples.empty()) {   // restrictSamples, :802-905
+        fprintf(stderr, "Performing masking...\n");
+        std::ifstream in(samples);
+        if (!in) { fprintf(stderr, "ERROR: Could not open the restricted samples file: %s!\n", samples.c_str()); return 1; }
+        std::vector<std::string> names;
+        std::vector<uint32_t> named;
+        std::string sample;
+        bool leaves_only = true;
+        while (std::getline(in, sample)) {
+            fprintf(stderr, "Checking for sample %s\n", sample.c_str());
+            const uh::Node *n = T.get_node(sample);
+            if (!n) { fprintf(stderr, "ERROR: Sample missing in input MAT!\n\n"); return 1; }
+            leaves_only = leaves_only && n->is_leaf();
+            named.push_back(n->flat_index);
+            names.push_back(sample);
+        }
+        if (names.empty()) { fprintf(stderr, "ERROR: the restricted samples file %s names no sample\n", samples.c_str()); return 1; }
+        t0 = clock();
+        std::vector<std::pair<uh::Node *, size_t>> marks;
+        size_t n_roots = 0;
+        bool on_device = !host;
+        if (on_device) {
+            if (!leaves_only) fprintf(stderr, "A restricted node is internal: restricted roots can nest, walking on the host.\n");
+            entry_masked.assign(std::max<size_t>(D.pos.size(), 1), 0);
+            uint64_t nr = 0, nm = 0;
+            const int rc = leaves_only ? ugp_mask_restricted(D.h, named.size(), named.data(), entry_masked.data(), nullptr, 0, &nr, &nm) : UGP_ERR_UNSUPPORTED;
+            if (rc == UGP_ERR_UNSUPPORTED) {
+                if (leaves_only) fprintf(stderr, "%s\n", ugp_last_error());
+                on_device = false;
+            } else if (rc != UGP_OK) lib_fail("ugp_mask_restricted");
+            else {
+                n_roots = nr;
+                for (uh::Node *n : F.dfs) {
+                    const uint64_t e0 = D.mut_off[n->flat_index];
+                    for (size_t k = 0; k < n->mutations.size(); k++) if (entry_masked[e0 + k]) marks.emplace_back(n, k);
+                }
+            }
+        }
+        if (!on_device) {
+            n_roots = host_restricted(T, F, names, marks);
+            if (!host) {
+                std::fill(entry_masked.begin(), entry_masked.end(), 0);
+                for (const auto &mk : marks) entry_masked[D.mut_off[mk.first->flat_index] + mk.second] = 1;
+            }
+        }
+        fprintf(stderr, "Restricted roots size: %zu\n\n", n_roots);
+        for (const auto &mk : marks) {
+            uh::Mutation &m = mk.first->mutations[mk.second];
+            fprintf(stderr, "Masking mutation %s at node %s\n", m.str().c_str(), mk.first->id.c_str());
+            m.position = -1;
+            m.ref_nuc = m.par_nuc = m.mut_nuc = 0;
+        }
+        fprintf(stderr, "Restricted samples %s in %ld msec\n", on_device ? "on the device" : "on the host",
+                (long)std::chrono::duration_cast<std::chrono::milliseconds>(clock() - t0).count());
+    }
+    if (!mutations.empty()) {   // restrictMutationsLocally, :746-800
+        fprintf(stderr, "Masking mutations...\n");
+        std::ifstream in(mutations);
+        if (!in) { fprintf(stderr, "ERROR: Could not open the file: %s!\n", mutations.c_str()); return 1; }
+        const char delim = mutations.find(".csv") != std::string::npos ? ',' : '\t';
+        std::vector<MaskLine> lines;
+        std::string line;
+        while (std::getline(in, line)) {
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            std::vector<std::string> words;
+            split_delim(line, delim, words);
+            if (words.empty()) { fprintf(stderr, "ERROR: Empty line in the mutations file: %s!\n", mutations.c_str()); return 1; }
+            MaskLine L;
+            if (!mutation_from_string(words[0], L.mut)) return 1;
+            const std::string target = words.size() == 1 ? T.root->id : words[1];
+            if (words.size() > 2) {
+                std::vector<std::string> ids;
+                split_delim(words[2], ';', ids);
+                L.exclude.insert(ids.begin(), ids.end());
+            }
+            L.node = T.get_node(target);
+            if (!L.node) {
+                fprintf(stderr, "ERROR: Internal node %s requested for masking does not exist in the tree. Exiting\n", target.c_str());
+                return 1;
+            }
+            lines.push_back(std::move(L));
+        }
+        t0 = clock();
+        size_t total_masked = 0;
+        if (host) {
+            for (const auto &L : lines) total_masked += host_mask_on_branch(L.node, L);
+        } else {
+            const size_t nl = lines.size(), M = D.mut_off.back();
+            std::vector<int32_t> lpos(nl);
+            std::vector<uint8_t> lpar(nl), lnuc(nl);
+            std::vector<uint32_t> lnode(nl), excl, first(std::max<size_t>(M, 1), UINT32_MAX);
+            std::vector<uint64_t> excl_off(nl + 1, 0), counts(std::max<size_t>(nl, 1), 0);
+            std::vector<uint32_t> met;
+            for (size_t l = 0; l < nl; l++) {
+                const MaskLine &L = lines[l];
+                lpos[l] = L.mut.position;
+                lpar[l] = L.mut.ref_nuc == 0b1111 ? 15 : (uint8_t)L.mut.par_nuc;
+                lnuc[l] = (uint8_t)L.mut.mut_nuc;
+                lnode[l] = L.node->flat_index;
+                // the excluded nodes the walk would meet: strict descendants of the target, none below another of them
+                const uint32_t tlo = F.dpos[lnode[l]], thi = F.dend[lnode[l]];
+                met.clear();
+                for (const auto &id : L.exclude) {
+                    const uh::Node *x = T.get_node(id);
+                    if (!x) continue;
+                    excl.push_back(x->flat_index);
+                    if (F.dpos[x->flat_index] > tlo && F.dpos[x->flat_index] < thi) met.push_back(x->flat_index);
+                }
+                excl_off[l + 1] = excl.size();
+                std::sort(met.begin(), met.end(), [&](uint32_t a, uint32_t b) { return F.dpos[a] < F.dpos[b]; });
+                uint32_t covered = 0;   // the end of the last printed node's range
+                for (uint32_t x : met) {
+                    if (F.dpos[x] < covered) continue;
+                    fprintf(stderr, "Excluding %s for position %d\n", F.bfs[x]->id.c_str(), L.mut.position);
+                    covered = F.dend[x];
+                }
+            }
+            if (ugp_mask_mutations(D.h, nl, lpos.data(), lpar.data(), lnuc.data(), lnode.data(), excl_off.data(), excl.data(),
+                                   entry_masked.empty() ? nullptr : entry_masked.data(), first.data(), counts.data()) != UGP_OK)
+                lib_fail("ugp_mask_mutations");
+            for (size_t j = 0; j < F.bfs.size(); j++) {
+                auto &ms = F.bfs[j]->mutations;
+                const uint64_t e0 = D.mut_off[j];
+                size_t keep = 0;
+                for (size_t k = 0; k < ms.size(); k++) {
+                    if (first[e0 + k] != UINT32_MAX) { total_masked++; continue; }
+                    if (keep != k) ms[keep] = ms[k];
+                    keep++;
+                }
+                ms.resize(keep);
+            }
+        }
+        done(t0, "\n");
+        fprintf(stderr, "Masked a total of %lu mutations. Collapsing tree...\n", (unsigned long)total_masked);
+        t0 = clock();
+        T.collapse_tree();
+        done(t0, "\n");
+    }
+    if (!rename.empty()) {   // renameSamples, :679-701
+        fprintf(stderr, "Renaming...\n");
+        std::ifstream in(rename);
+        if (!in) { fprintf(stderr, "ERROR: Could not open the renaming file: %s!\n", rename.c_str()); return 1; }
+        std::string line;
+        while (std::getline(in, line)) {
+            std::vector<std::string> words;
+            split_delim(line, '\t', words);
+            if (words.size() != 2) { fprintf(stderr, "ERROR: Incorrect format for the renaming file: %s!\n", rename.c_str()); return 1; }
+            if (!T.get_node(words[0])) { fprintf(stderr, "WARNING: Node %s not found in the MAT.\n", words[0].c_str()); continue; }
+            fprintf(stderr, "Renaming node %s to %s.\n", words[0].c_str(), words[1].c_str());
+            if (!T.rename_node(words[0], words[1])) {
+                fprintf(stderr, "ERROR: rename_node: node with id '%s' already exists.\n", words[1].c_str());
+                return 1;
+            }
+        }
+    }
+    if (recondense) {
+        t0 = clock();
+        fprintf(stderr, "Collapsing tree...\n");
+        T.collapse_tree();
+        done(t0, "\n\n");
+        t0 = clock();
+        fprintf(stderr, "Condensing leaves...\n");
+        T.condense_leaves();
+        done(t0, "\n\n");
+    }
+    fprintf(stderr, "Saving final tree to %s\n", out.c_str());
+    t0 = clock();
+    if (!uh::save_mat(T, out, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+    done(t0, "\n\n");
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -2893,6 +3265,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "translate")) return translate(argc - 2, argv + 2);
     if (!strcmp(argv[1], "relatives")) return relatives(argc - 2, argv + 2);
     if (!strcmp(argv[1], "select")) return select_samples(argc - 2, argv + 2);
-    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate, extract, summarize, translate, relatives, select)\n", argv[1]);
+    if (!strcmp(argv[1], "mask")) return mask(argc - 2, argv + 2);
+    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate, extract, summarize, translate, relatives, select, mask)\n", argv[1]);
     return 1;
 }

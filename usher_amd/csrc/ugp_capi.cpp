@@ -31,6 +31,7 @@
 #include "ugp_annotate.hpp"
 #include "ugp_nearest.hpp"
 #include "ugp_relatives.hpp"
+#include "ugp_mask.hpp"
 #include "ugp_select.hpp"
 #include "ugp_genotypes.hpp"
 #include "ugp_summary.hpp"
@@ -309,6 +310,7 @@ struct ugp_mat {
     ugp::SmState *sm = nullptr;      // matUtils summary tables (ugp_summary_attach), or none
     ugp::TrState *tr = nullptr;      // matUtils summary --translate tables (ugp_translate_attach), or none
     ugp::SelState *sel = nullptr;    // matUtils extract selector tables (ugp_select_attach), or none
+    ugp::MskState *msk = nullptr;    // matUtils mask tables (ugp_mask_attach), or none
     ugp::DfsTables *dfs = nullptr;   // the depth-first tables uncertainty and annotate share (their first attach), or none
     hipEvent_t kb_done = nullptr;    // behind the latest k_best8 launch of this handle ...
     hipStream_t kb_done_on = nullptr;   // ... on this stream
@@ -1436,6 +1438,7 @@ void ugp_mat_destroy(ugp_mat *m) {
     ugp::sm_free(m->sm);
     ugp::tr_free(m->tr);
     ugp::sel_free(m->sel);
+    ugp::msk_free(m->msk);
     ugp::dfs_tables_free(m->dfs);
     delete m;
 }
@@ -2020,6 +2023,39 @@ int ugp_select_mrca(ugp_mat *m, const uint64_t *words, uint32_t *node, uint64_t 
 int ugp_select_time(ugp_mat *m, uint64_t n_mut, const int32_t *pos, const uint8_t *nuc, uint32_t reps, double *ms) {
     if (!m) return fail(UGP_ERR_INVALID, "null argument");
     return ugp::sel_time(m->sel, n_mut, pos, nuc, reps, ms);
+}
+
+// ---- matUtils mask: restricted samples and masked mutations in closed form (ugp_mask.hip) ---------------------------------
+
+int ugp_mask_attach(ugp_mat *m, const ugp_tree_desc *tree) {
+    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
+    if (int rc = check_handle_tree(m, tree)) return rc;
+    return ugp::msk_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->msk);
+}
+
+int ugp_mask_restricted(ugp_mat *m, uint64_t n, const uint32_t *leaves_bfs, uint8_t *entry_masked, uint32_t *roots_bfs, uint64_t roots_cap,
+                        uint64_t *n_roots, uint64_t *n_masked) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::msk_restricted(m->msk, n, leaves_bfs, entry_masked, roots_bfs, roots_cap, n_roots, n_masked);
+}
+
+int ugp_mask_mutations_chunked(ugp_mat *m, uint64_t n_lines, const int32_t *pos, const uint8_t *par, const uint8_t *nuc,
+                               const uint32_t *node_bfs, const uint64_t *excl_off, const uint32_t *excl_bfs, const uint8_t *skip,
+                               uint32_t *first_line, uint64_t *counts, uint32_t chunk_lines) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::msk_mutations(m->msk, n_lines, pos, par, nuc, node_bfs, excl_off, excl_bfs, skip, first_line, counts, chunk_lines);
+}
+
+int ugp_mask_mutations(ugp_mat *m, uint64_t n_lines, const int32_t *pos, const uint8_t *par, const uint8_t *nuc, const uint32_t *node_bfs,
+                       const uint64_t *excl_off, const uint32_t *excl_bfs, const uint8_t *skip, uint32_t *first_line, uint64_t *counts) {
+    return ugp_mask_mutations_chunked(m, n_lines, pos, par, nuc, node_bfs, excl_off, excl_bfs, skip, first_line, counts, 0);
+}
+
+int ugp_mask_time(ugp_mat *m, uint64_t n, const uint32_t *leaves_bfs, uint64_t n_lines, const int32_t *pos, const uint8_t *par,
+                  const uint8_t *nuc, const uint32_t *node_bfs, const uint64_t *excl_off, const uint32_t *excl_bfs, uint32_t reps,
+                  double *restricted_ms, double *mutations_ms) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::msk_time(m->msk, n, leaves_bfs, n_lines, pos, par, nuc, node_bfs, excl_off, excl_bfs, reps, restricted_ms, mutations_ms);
 }
 
 // ---- matUtils extract -v: genotypes of a selection (ugp_genotypes.hip) -------------------------------------------------

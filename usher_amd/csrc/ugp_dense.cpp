@@ -37,6 +37,23 @@ int dfs_tables_same_arrays(const DfsTables &T, const ugp_tree_desc *tree, const 
     return UGP_OK;
 }
 
+void leaf_ranks(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, LeafRanks *out) {
+    const uint32_t N = (uint32_t)dfs2bfs.size();
+    std::vector<uint8_t> inner(N, 0);
+    for (uint32_t j = 1; j < N; j++) inner[tree->parent[dfs2bfs[j]]] = 1;   // by BFS index
+    out->leaf_dfs.clear();
+    out->lbefore.resize((size_t)N + 1);
+    for (uint32_t i = 0; i < N; i++) {
+        out->lbefore[i] = (uint32_t)out->leaf_dfs.size();
+        if (!inner[dfs2bfs[i]]) out->leaf_dfs.push_back(i);
+    }
+    out->lbefore[N] = (uint32_t)out->leaf_dfs.size();
+    std::vector<uint32_t> sz(N, 1);   // subtree ends by a reverse sweep
+    for (uint32_t i = N; i-- > 1;) sz[bfs2dfs[tree->parent[dfs2bfs[i]]]] += sz[i];
+    out->dend.resize(N);
+    for (uint32_t i = 0; i < N; i++) out->dend[i] = i + sz[i];
+}
+
 void dfs_tables_free(DfsTables *t) {
     if (!t) return;
     (void)hipSetDevice(t->device);

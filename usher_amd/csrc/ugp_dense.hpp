@@ -149,6 +149,11 @@ void dfs_tables_free(DfsTables *t);
 // built from exactly the mutation arrays of `tree` (compared entry by entry), else UGP_ERR_INVALID naming the call `who`.
 int dfs_tables_same_arrays(const DfsTables &t, const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const char *who);
 
+// The leaf-rank ranges select and mask read: leaf r is the r-th leaf in depth-first order, lbefore[i] ([n + 1]) the leaves in front of
+// depth-first position i, dend[i] ([n]) the end of position i's subtree, leaf_dfs[r] the depth-first position of leaf r.
+struct LeafRanks { std::vector<uint32_t> lbefore, dend, leaf_dfs; };
+void leaf_ranks(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, LeafRanks *out);
+
 // ---- the literal score: loop 1 run literally, loops 2 and 3 in closed form, the eligibility ------------------------
 
 // Row-cost policies.  A handle h != 0 stands for the sample's rows at one position (0: no row there).

@@ -139,23 +139,12 @@ int sel_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, 
         S->device = device;
         S->T = *tables;
         S->dfs2bfs = &dfs2bfs;
-        const uint32_t N = (*tables)->n;
-        // the leaves in depth-first order and, per position, the leaves in front of it; subtree ends by a reverse sweep
-        std::vector<uint8_t> inner(N, 0);
-        for (uint32_t j = 1; j < N; j++) inner[tree->parent[dfs2bfs[j]]] = 1;   // by BFS index
-        std::vector<uint32_t> leaf_dfs;
-        S->h_lbefore.resize((size_t)N + 1);
-        for (uint32_t i = 0; i < N; i++) {
-            S->h_lbefore[i] = (uint32_t)leaf_dfs.size();
-            if (!inner[dfs2bfs[i]]) { leaf_dfs.push_back(i); S->h_bfs_by_rank.push_back(dfs2bfs[i]); }
-        }
-        S->h_lbefore[N] = (uint32_t)leaf_dfs.size();
-        {
-            std::vector<uint32_t> sz(N, 1);
-            for (uint32_t i = N; i-- > 1;) sz[bfs2dfs[tree->parent[dfs2bfs[i]]]] += sz[i];
-            S->h_dend.resize(N);
-            for (uint32_t i = 0; i < N; i++) S->h_dend[i] = i + sz[i];
-        }
+        LeafRanks R;
+        leaf_ranks(tree, dfs2bfs, bfs2dfs, &R);
+        const std::vector<uint32_t> &leaf_dfs = R.leaf_dfs;
+        S->h_lbefore = std::move(R.lbefore);
+        S->h_dend = std::move(R.dend);
+        for (uint32_t i : leaf_dfs) S->h_bfs_by_rank.push_back(dfs2bfs[i]);
         S->nleaf = (uint32_t)leaf_dfs.size();
         S->nwords = (S->nleaf + 63u) / 64u;
         auto fail = [&](int code, const std::string &msg) { (void)hipStreamSynchronize(S->stream); delete S; return set_error(code, msg); };

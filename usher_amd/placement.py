@@ -698,6 +698,80 @@ class Placer:
         self._ck(self._L.ugp_select_time(self._h, len(pos), _ptr(pos), _ptr(nuc), int(reps), C.byref(ms)))
         return float(ms.value)
 
+    # ---- matUtils mask in closed form (ugp_mask_*) -----------------------------------------------------------------------------
+    def mask_attach(self, arrays: Optional[Dict] = None):
+        """ugp_mask_attach with the placer's own tree, or with other mutation arrays on the same topology (masked entries, two
+        entries at one position on a node).  The depth-first tables are shared as genotypes_attach describes."""
+        t = self._t if arrays is None else _TreeArrays(arrays)
+        self._ck(self._L.ugp_mask_attach(self._h, C.byref(t.desc)))
+        self._msk_shape = (int(t.n), int(t.mut_off[t.n]))
+
+    def _msk(self):
+        if getattr(self, "_msk_shape", None) is None:
+            self.mask_attach()
+        return self._msk_shape
+
+    def mask_restricted(self, leaves):
+        """restrictSamples (mask.cpp:802-905) for named LEAVES (BFS indices): (roots, entry_masked) -- the restricted roots as BFS
+        indices in depth-first order, and per entry of the mutation CSR whether the reference masks it.  A named internal node
+        raises UgpError -2 (the caller walks); an empty list or a node out of range -1."""
+        n_nodes, n_ent = self._msk()
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint32)
+        masked = np.full(n_ent, 0xA5, np.uint8)
+        roots = np.zeros(max(len(leaves), 1), np.uint32)   # disjoint roots, each with a named leaf below: never more than names
+        nr, nm = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self._L.ugp_mask_restricted(self._h, len(leaves), _ptr(leaves) if len(leaves) else None, _ptr(masked) if n_ent else None,
+                                             _ptr(roots), len(roots), C.byref(nr), C.byref(nm)))
+        self._msk_n_masked = int(nm.value)
+        return roots[:int(nr.value)], masked.astype(bool)
+
+    @staticmethod
+    def _msk_lines(pos, par, nuc, node, excl):
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        par = np.ascontiguousarray(par, dtype=np.uint8)
+        nuc = np.ascontiguousarray(nuc, dtype=np.uint8)
+        node = np.ascontiguousarray(node, dtype=np.uint32)
+        excl = [np.asarray(x, dtype=np.uint32).ravel() for x in (excl if excl is not None else [[]] * len(pos))]
+        if not (len(pos) == len(par) == len(nuc) == len(node) == len(excl)):
+            raise UgpError(-1, "pos, par, nuc, node and excl hold one value per line")
+        off = np.zeros(len(pos) + 1, np.uint64)
+        off[1:] = np.cumsum([len(x) for x in excl], dtype=np.uint64)
+        flat = np.ascontiguousarray(np.concatenate(excl) if excl and int(off[-1]) else np.zeros(0, np.uint32), dtype=np.uint32)
+        return pos, par, nuc, node, off, flat
+
+    def mask_mutations(self, pos, par, nuc, node, excl=None, skip=None, chunk_lines: int = 0):
+        """restrictMutationsLocally (mask.cpp:703-800) for the lines (pos, par, nuc, node, excl)[l]: par / nuc are 4-bit codes with 15
+        for N, node a BFS index, excl[l] the excluded nodes of line l (BFS indices; anything out of range has no effect).  Returns
+        (first_line, counts): per entry of the mutation CSR the first line that removes it (UINT32_MAX: none), and per line the
+        entries it removes.  skip: per entry, set for entries that never match.  chunk_lines (test hook): lines per launch."""
+        _, n_ent = self._msk()
+        pos, par, nuc, node, off, flat = self._msk_lines(pos, par, nuc, node, excl)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.uint8)
+            if len(skip) != n_ent:
+                raise UgpError(-1, "skip holds one flag per mutation entry")
+        first = np.full(n_ent, 0xA5A5A5A5, np.uint32)
+        counts = np.zeros(len(pos), np.uint64)
+        nl = len(pos)
+        self._ck(self._L.ugp_mask_mutations_chunked(self._h, nl, _ptr(pos) if nl else None, _ptr(par) if nl else None,
+                                                    _ptr(nuc) if nl else None, _ptr(node) if nl else None, _ptr(off),
+                                                    _ptr(flat) if len(flat) else None, _ptr(skip) if skip is not None and n_ent else None,
+                                                    _ptr(first) if n_ent else None, _ptr(counts) if nl else None, int(chunk_lines)))
+        return first, counts
+
+    def mask_time(self, leaves=None, pos=(), par=(), nuc=(), node=(), excl=None, reps: int = 5):
+        """Bench hook: (restricted_ms, mutations_ms), milliseconds of device time of the passes alone (no copies) for the named
+        leaves and for the lines; what is not given is not run and reads 0."""
+        self._msk()
+        leaves = np.ascontiguousarray(leaves if leaves is not None else [], dtype=np.uint32)
+        pos, par, nuc, node, off, flat = self._msk_lines(pos, par, nuc, node, excl)
+        nl = len(pos)
+        a, b = C.c_double(0), C.c_double(0)
+        self._ck(self._L.ugp_mask_time(self._h, len(leaves), _ptr(leaves) if len(leaves) else None, nl, _ptr(pos) if nl else None,
+                                       _ptr(par) if nl else None, _ptr(nuc) if nl else None, _ptr(node) if nl else None, _ptr(off),
+                                       _ptr(flat) if len(flat) else None, int(reps), C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
+
     RIPPLES_EVENT = np.dtype([("branch", np.uint64), ("i", np.uint32), ("j", np.uint32), ("donor", np.uint32), ("acceptor", np.uint32),
                               ("donor_count", np.uint32), ("acceptor_count", np.uint32), ("donor_score", np.int32),
                               ("acceptor_score", np.int32), ("donor_sibling", np.uint8), ("acceptor_sibling", np.uint8),
