@@ -506,6 +506,62 @@ int ugp_mask_mutations_chunked(ugp_mat *mat, uint64_t n_lines, const int32_t *po
 int ugp_mask_time(ugp_mat *mat, uint64_t n, const uint32_t *leaves_bfs, uint64_t n_lines, const int32_t *pos, const uint8_t *par,
                   const uint8_t *nuc, const uint32_t *node_bfs, const uint64_t *excl_off, const uint32_t *excl_bfs, uint32_t reps,
                   double *restricted_ms, double *mutations_ms);
+/* matUtils summary --haplotype (matUtils/summary.cpp: count_haplotypes :182-218, write_haplotype_table :244-264): the distinct
+ * HAPLOTYPES of the leaves with the number of leaves that carry each.  The reference walks the nodes in depth-first order with a
+ * std::map<int,int8_t> per node: a node starts from its parent's map (the root from an empty one) and applies its entries in stored
+ * order -- an entry with mut_nuc == its own stored ref_nuc erases the position, any other sets map[position] = mut_nuc; mut_par
+ * plays no part.  Masked entries (mut_pos < 0) are skipped: they erase a negative position that nothing sets.  So the STATE of a
+ * position at a node is that of the last non-masked entry at it on the deepest node of the root path (the node included) that has
+ * one; it is OFF THE REFERENCE when that entry's mut_nuc differs from that entry's ref_nuc, and the haplotype of a node is the set
+ * of (position, mut_nuc) of the positions off the reference.  Every leaf counts for its haplotype (a tree that is only a root counts
+ * the root); internal nodes are never counted.
+ * ugp_haplotypes_attach shares the depth-first tables of `tree` exactly as ugp_summary_attach does (the handle's tree; arrays are
+ * copied; mut_par is not read; tables built from other mutation arrays: UGP_ERR_INVALID, nothing changed) and builds, once per
+ * handle, the leaves in depth-first order.  A second attach replaces the first.  A call before the attach is UGP_ERR_INVALID and
+ * names the missing call.  A node with two non-masked entries at one position is a DUPLICATE node (the walk takes its last entry,
+ * the tables' owner is its first): with any, ugp_haplotype_groups and ugp_haplotype_sets return UGP_ERR_UNSUPPORTED, *n_out = 0 and
+ * nothing is written; the caller walks the tree serially instead.
+ * ugp_haplotype_groups: one record per distinct haplotype: leaf = the BFS index of its first leaf in depth-first order, count = its
+ *   leaves, size = its (position, allele) pairs; records ascend by the depth-first position of `leaf`.  out[0 .. min(cap, *n_out))
+ *   is written and *n_out is the true count.  The groups are the runs of a sort of the leaves by a 128-bit FINGERPRINT of their
+ *   haplotype (a sum, modulo 2^64 in each of two lanes, of a fixed mix of every pair of the set), and every leaf that is not the
+ *   first of its run is then compared exactly with the leaf in front of it: every position with an entry on either leaf's path
+ *   below their lowest common ancestor must have the same state for both, and the sizes must agree.  A leaf that differs is a
+ *   COLLISION: with any the call returns UGP_ERR_UNSUPPORTED, *n_out = 0 and nothing is written -- no table is returned that has
+ *   not been verified.  `info` (may be NULL) is filled by every call that ran, also when it refuses; first_duplicate is the first
+ *   duplicate node in depth-first order (BFS index), UINT32_MAX when there is none; n_visited the entries the comparison read.
+ * ugp_haplotype_groups_hashed (test hook): only the low hash_bits (0 .. 128; more is UGP_ERR_INVALID) of the fingerprint take part
+ *   in the sort and in the runs; 128 is the plain call, 0 puts every leaf into one run.
+ * ugp_haplotype_sets: the haplotypes of the n given leaves (BFS; an index out of range or an internal node is UGP_ERR_INVALID before
+ *   anything is written) as a CSR: off[n + 1] is always complete, set i is pos / nuc[off[i] .. off[i + 1]), ascending by position,
+ *   nuc the stored 4-bit code.  pos / nuc[0 .. min(cap, *n_out)) are written and *n_out = off[n] is the true total.  The leaves run
+ *   in launch windows; the _chunked twin (test hook) sets the leaves per window (0: default). */
+typedef struct ugp_hp_group {
+    uint32_t leaf;               /* BFS index of the first leaf of the group       */
+    uint32_t count;              /* leaves with this haplotype                     */
+    uint32_t size;               /* (position, allele) pairs of the haplotype      */
+    uint32_t pad;
+} ugp_hp_group;
+typedef struct ugp_hp_info {
+    uint64_t n_leaves;
+    uint64_t n_groups;           /* runs of the sort, also when the call refuses   */
+    uint64_t n_collisions;       /* leaves that differ from the leaf in front      */
+    uint64_t n_duplicate;        /* nodes with a position twice                    */
+    uint64_t n_visited;          /* entries read by the exact comparison           */
+    uint32_t first_duplicate;    /* BFS index of the node                          */
+    uint32_t pad;
+} ugp_hp_info;
+int ugp_haplotypes_attach(ugp_mat *mat, const ugp_tree_desc *tree);
+int ugp_haplotype_groups(ugp_mat *mat, ugp_hp_group *out, uint64_t cap, uint64_t *n_out, ugp_hp_info *info);
+int ugp_haplotype_groups_hashed(ugp_mat *mat, ugp_hp_group *out, uint64_t cap, uint64_t *n_out, ugp_hp_info *info, uint32_t hash_bits);
+int ugp_haplotype_sets(ugp_mat *mat, const uint32_t *leaves /* BFS */, uint64_t n, uint64_t *off /* [n + 1] */, int32_t *pos, uint8_t *nuc,
+                       uint64_t cap, uint64_t *n_out);
+int ugp_haplotype_sets_chunked(ugp_mat *mat, const uint32_t *leaves, uint64_t n, uint64_t *off, int32_t *pos, uint8_t *nuc, uint64_t cap,
+                               uint64_t *n_out, uint64_t chunk_leaves);
+/* Bench hook: milliseconds of device time of the passes of ugp_haplotype_groups alone (no copies): the differences with their scan,
+ * the two sorts of the leaves by fingerprint with the run heads, and the exact comparison; each the mean of `reps` runs after one
+ * warm-up run. */
+int ugp_haplotype_time(ugp_mat *mat, uint32_t reps, double *scan_ms, double *sort_ms, double *verify_ms);
 /* RIPPLES (ripples/main.cpp): the options of :22-44 that the search reads. branch_len >= 1 and parsimony_improvement >= 0
  * (UGP_ERR_INVALID otherwise: the reference's size_t arithmetic of :445-453 is not reproduced for negative values). */
 typedef struct ugp_ripples_opts {

@@ -125,6 +125,12 @@ SYMBOLS = {
     "ugp_mask_mutations": (C.c_int, [P, C.c_uint64, P, P, P, P, P, P, P, P, P]),
     "ugp_mask_mutations_chunked": (C.c_int, [P, C.c_uint64, P, P, P, P, P, P, P, P, P, C.c_uint32]),
     "ugp_mask_time": (C.c_int, [P, C.c_uint64, P, C.c_uint64, P, P, P, P, P, P, C.c_uint32, P, P]),
+    "ugp_haplotypes_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc)]),
+    "ugp_haplotype_groups": (C.c_int, [P, P, C.c_uint64, P, P]),
+    "ugp_haplotype_groups_hashed": (C.c_int, [P, P, C.c_uint64, P, P, C.c_uint32]),
+    "ugp_haplotype_sets": (C.c_int, [P, P, C.c_uint64, P, P, P, C.c_uint64, P]),
+    "ugp_haplotype_sets_chunked": (C.c_int, [P, P, C.c_uint64, P, P, P, C.c_uint64, P, C.c_uint64]),
+    "ugp_haplotype_time": (C.c_int, [P, C.c_uint32, P, P, P]),
     "ugp_ripples_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc), P]),
     "ugp_ripples": (C.c_int, [P, C.POINTER(ugp_ripples_opts), P, C.c_uint64, P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ugp_subtree_mask": (C.c_int, [P, C.c_uint32, C.c_uint32, C.c_uint32, P]),

@@ -53,6 +53,7 @@
 
 #include "driver.hpp"
 #include "mat.hpp"
+#include "par.hpp"
 #include "usher_amd.h"
 
 namespace {
@@ -68,7 +69,7 @@ void usage(FILE *f) {
             "      --device             HIP device ordinal [0]\n"
             "  (-d / --dropout-mutations is not supported)\n"
             "       matutils-amd annotate --help | matutils-amd extract --help | matutils-amd summarize --help | matutils-amd translate --help\n"
-            "       matutils-amd relatives --help | matutils-amd select --help | matutils-amd mask --help\n");
+            "       matutils-amd relatives --help | matutils-amd select --help | matutils-amd mask --help | matutils-amd haplotypes --help\n");
 }
 
 int uncertainty(int argc, char **argv) {
@@ -2589,6 +2590,215 @@ int translate(int argc, char **argv) {   // summary_main's --translate branch (s
     return 0;
 }
 
+// ---- haplotypes (summary --haplotype: summary.cpp:182-264) -----------------------------------------------------------
+
+void haplotypes_usage(FILE *f) {
+    fprintf(f,
+            "Usage: matutils-amd haplotypes -i tree.pb -H out.tsv [-d dir] [-T n] [--device k] [--host]\n"
+            "  -i, --input-mat          input mutation-annotated tree [REQUIRED]\n"
+            "  -H, --haplotype          tsv of every distinct set of mutations off the reference that a sample carries, and its samples [REQUIRED]\n"
+            "  -d, --output-directory   directory of the output file [./]\n"
+            "  -T, --threads            accepted for compatibility (the table runs on the device)\n"
+            "      --device             HIP device ordinal [0]\n"
+            "      --host               the reference's serial walk on the host (slow; no device)\n");
+}
+
+typedef std::map<int, int8_t> HapSet;   // summary.cpp:184
+
+void hap_line(std::string &out, const int32_t *pos, const uint8_t *nuc, size_t n, size_t count) {   // :252-261
+    if (!n) out += "reference";   // (the reference calls pop_back() on the empty string first; this is what it evidently means)
+    for (size_t k = 0; k < n; k++) {
+        if (k) out += ',';
+        out += std::to_string(pos[k]);
+        out += uh::nuc_char((int8_t)nuc[k]);
+    }
+    out += '\t';
+    out += std::to_string(count);
+    out += '\n';
+}
+
+// --host: count_haplotypes (:182-218) and write_haplotype_table (:244-264), statement by statement.  The reference keeps the map of
+// every internal node, by name, for the whole walk; here an internal node's map is freed when the walk has left its subtree (the
+// maps of the current root path are all a later node can ask for).
+void host_haplotypes(const uh::Tree &T, std::ofstream &f) {
+    std::map<HapSet, size_t> hapcount;
+    std::vector<std::pair<const uh::Node *, HapSet>> hapmap;   // the internal nodes of the current root path
+    for (const uh::Node *s : T.dfs()) {
+        HapSet mset;
+        if (!s->is_root()) {
+            while (hapmap.back().first != s->parent) hapmap.pop_back();
+            mset = hapmap.back().second;
+        }
+        for (const auto &m : s->mutations) {
+            if (m.mut_nuc == m.ref_nuc) {
+                auto iter = mset.find(m.position);
+                if (iter != mset.end()) mset.erase(iter);
+            } else {
+                mset[m.position] = m.mut_nuc;
+            }
+        }
+        if (s->is_leaf()) hapcount[mset]++;
+        else hapmap.emplace_back(s, std::move(mset));
+    }
+    f << "mutation_set\tsample_count\n";
+    std::string out;
+    std::vector<int32_t> pos;
+    std::vector<uint8_t> nuc;
+    for (const auto &hapc : hapcount) {
+        pos.clear(); nuc.clear();
+        for (const auto &m : hapc.first) { pos.push_back(m.first); nuc.push_back((uint8_t)m.second); }
+        hap_line(out, pos.data(), nuc.data(), pos.size(), hapc.second);
+        if (out.size() > (1u << 20)) { f << out; out.clear(); }
+    }
+    f << out;
+}
+
+// The device path: the groups and the sets of their first leaves from ugp_haplotypes.hip, ordered here as the std::map orders them.
+// False (with a line on stderr) when the library refuses the tree: the caller walks it on the host.
+bool device_haplotypes(uh::Tree &T, int device, std::ofstream &f) {
+    const std::vector<uh::Node *> bfs = T.bfs();
+    const uint64_t N = bfs.size();
+    for (uint64_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
+    std::vector<uint32_t> parent(N);
+    std::vector<uint64_t> mut_off(N + 1, 0);
+    std::vector<int32_t> pos;
+    std::vector<uint8_t> ref, par, nuc;
+    for (uint64_t j = 0; j < N; j++) {
+        parent[j] = bfs[j]->parent ? bfs[j]->parent->flat_index : UINT32_MAX;
+        for (const auto &m : bfs[j]->mutations) {
+            pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
+        }
+        mut_off[j + 1] = pos.size();
+    }
+    const std::vector<uint64_t> no_off(N + 1, 0);
+    if (pos.empty()) { pos.push_back(0); ref.push_back(0); par.push_back(0); nuc.push_back(0); }   // (never read: no null arrays)
+    const ugp_tree_desc bare{N, parent.data(), no_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+    const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+    struct Handle { ugp_mat *h = nullptr; ~Handle() { if (h) ugp_mat_destroy(h); } } H;
+    if (ugp_mat_create(&bare, device, &H.h) != UGP_OK) lib_fail("ugp_mat_create");
+    int rc = ugp_haplotypes_attach(H.h, &desc);
+    if (rc == UGP_ERR_UNSUPPORTED) {
+        fprintf(stderr, "The device does not take this tree (%s); walking it on the host.\n", ugp_last_error());
+        return false;
+    }
+    if (rc != UGP_OK) lib_fail("ugp_haplotypes_attach");
+    // USHER_AMD_HAPLOTYPE_HASH_BITS (test switch): only that many bits of the fingerprint group the leaves, so that the exact
+    // comparison finds collisions and the table is refused.  (No file reaches the other refusal: the loader's add_mutation merges
+    // two entries at one position of a node, as the reference's does.)
+    uint32_t hash_bits = 128;
+    if (const char *e = getenv("USHER_AMD_HAPLOTYPE_HASH_BITS")) hash_bits = (uint32_t)std::max(0, std::min(128, atoi(e)));
+    uint64_t n = 0;
+    ugp_hp_info info;
+    rc = ugp_haplotype_groups_hashed(H.h, nullptr, 0, &n, &info, hash_bits);
+    if (rc == UGP_ERR_UNSUPPORTED) {
+        fprintf(stderr, "The closed form does not hold for this tree: %llu nodes with a position twice", (unsigned long long)info.n_duplicate);
+        if (info.n_duplicate) fprintf(stderr, " (first: %s)", bfs[info.first_duplicate]->id.c_str());
+        fprintf(stderr, ", %llu fingerprint collisions among %llu samples; walking it on the host.\n", (unsigned long long)info.n_collisions,
+                (unsigned long long)info.n_leaves);
+        return false;
+    }
+    if (rc != UGP_OK) lib_fail("ugp_haplotype_groups");
+    std::vector<ugp_hp_group> groups(n);
+    if (n && ugp_haplotype_groups_hashed(H.h, groups.data(), n, &n, &info, hash_bits) != UGP_OK) lib_fail("ugp_haplotype_groups");
+    // the sets of the groups' first leaves (the library runs them in launch windows)
+    std::vector<uint32_t> reps(n);
+    for (uint64_t g = 0; g < n; g++) reps[g] = groups[g].leaf;
+    std::vector<uint64_t> off(n + 1, 0);
+    uint64_t total = 0;
+    if (ugp_haplotype_sets(H.h, reps.data(), n, off.data(), nullptr, nullptr, 0, &total) != UGP_OK) lib_fail("ugp_haplotype_sets");
+    std::vector<int32_t> spos(total);
+    std::vector<uint8_t> snuc(total);
+    if (total && ugp_haplotype_sets(H.h, reps.data(), n, off.data(), spos.data(), snuc.data(), total, &total) != UGP_OK) lib_fail("ugp_haplotype_sets");
+    // std::map<std::map<int,int8_t>,size_t> order: lexicographic over the (position, allele) pairs, a proper prefix first
+    std::vector<uint32_t> order(n);
+    for (uint64_t g = 0; g < n; g++) order[g] = (uint32_t)g;
+    auto before = [&](uint32_t x, uint32_t y) {
+        const uint64_t nx = off[x + 1] - off[x], ny = off[y + 1] - off[y];
+        const int32_t *px = spos.data() + off[x], *py = spos.data() + off[y];
+        const uint8_t *cx = snuc.data() + off[x], *cy = snuc.data() + off[y];
+        for (uint64_t k = 0; k < nx && k < ny; k++) {
+            if (px[k] != py[k]) return px[k] < py[k];
+            if (cx[k] != cy[k]) return (int8_t)cx[k] < (int8_t)cy[k];
+        }
+        return nx < ny;
+    };
+    // sorted pieces on the host threads, then merged pair by pair
+    const uint64_t grain = getenv("USHER_AMD_GRAIN") ? (uint64_t)std::max(1, atoi(getenv("USHER_AMD_GRAIN"))) : (1u << 16);   // as par.hpp reads it
+    const uint64_t pieces = std::max<uint64_t>(1, std::min<uint64_t>(uh::host_threads(), n / grain));
+    std::vector<uint64_t> cut;
+    for (uint64_t i = 0; i <= pieces; i++) cut.push_back(n * i / pieces);
+    uh::parallel_for(pieces, [&](uint64_t b, uint64_t e, unsigned) {
+        for (uint64_t k = b; k < e; k++) std::sort(order.begin() + cut[k], order.begin() + cut[k + 1], before);
+    }, 1);
+    while (cut.size() > 2) {
+        const size_t pairs = (cut.size() - 1) / 2;
+        uh::parallel_for(pairs, [&](uint64_t b, uint64_t e, unsigned) {
+            for (uint64_t k = b; k < e; k++) std::inplace_merge(order.begin() + cut[2 * k], order.begin() + cut[2 * k + 1], order.begin() + cut[2 * k + 2], before);
+        }, 1);
+        std::vector<uint64_t> next;
+        for (size_t k = 0; k < cut.size(); k += 2) next.push_back(cut[k]);
+        if ((cut.size() - 1) % 2) next.push_back(cut.back());
+        cut.swap(next);
+    }
+    std::string out = "mutation_set\tsample_count\n";
+    for (uint32_t g : order) {
+        hap_line(out, spos.data() + off[g], snuc.data() + off[g], off[g + 1] - off[g], groups[g].count);
+        if (out.size() > (1u << 20)) { f << out; out.clear(); }
+    }
+    f << out;
+    return true;
+}
+
+int haplotypes(int argc, char **argv) {   // summary_main's --haplotype branch (summary.cpp:725-728)
+    std::string mat, dir = "./", table;
+    bool host = false;
+    int device = 0;
+    for (int i = 0; i < argc; i++) {
+        const std::string a = argv[i];
+        auto val = [&](std::string &dst) -> bool {
+            if (i + 1 >= argc) { fprintf(stderr, "ERROR: %s needs a value\n", a.c_str()); haplotypes_usage(stderr); return false; }
+            dst = argv[++i];
+            return true;
+        };
+        std::string tmp;
+        bool ok = true;
+        if (a == "-i" || a == "--input-mat") ok = val(mat);
+        else if (a == "-d" || a == "--output-directory") ok = val(dir);
+        else if (a == "-H" || a == "--haplotype") ok = val(table);
+        else if (a == "-T" || a == "--threads") ok = val(tmp);
+        else if (a == "--device") { ok = val(tmp); device = atoi(tmp.c_str()); }
+        else if (a == "--host") host = true;
+        else if (a == "-h" || a == "--help") { haplotypes_usage(stdout); return 0; }
+        else { fprintf(stderr, "ERROR: unknown option %s\n", a.c_str()); haplotypes_usage(stderr); return 1; }
+        if (!ok) return 1;
+    }
+    if (mat.empty()) { fprintf(stderr, "ERROR: the option '--input-mat' is required but missing\n"); haplotypes_usage(stderr); return 1; }
+    if (table.empty()) { fprintf(stderr, "ERROR: the option '--haplotype' is required but missing\n"); haplotypes_usage(stderr); return 1; }
+    struct stat sb;
+    if (stat(dir.c_str(), &sb) != 0) {
+        fprintf(stderr, "Creating output directory.\n\n");
+        mkdir(dir.c_str(), 0777);
+    }
+    char *canon = realpath(dir.c_str(), nullptr);
+    if (!canon) { fprintf(stderr, "ERROR: cannot resolve the output directory %s\n", dir.c_str()); return 1; }
+    const std::string path = std::string(canon) + "/" + table;
+    free(canon);
+    fprintf(stderr, "Loading input MAT file %s.\n", mat.c_str());
+    uh::Tree T;
+    std::string err;
+    if (!uh::load_mat(mat, T, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+    T.uncondense_leaves();
+    fprintf(stderr, "Writing haplotype frequencies to output %s\n", path.c_str());
+    const auto t0 = std::chrono::steady_clock::now();
+    std::ofstream f(path, std::ios::binary);
+    if (!f) { fprintf(stderr, "ERROR: Could not open file for writing: %s!\n", path.c_str()); return 1; }
+    if (host || !device_haplotypes(T, device, f)) host_haplotypes(T, f);
+    f.close();
+    if (!f) { fprintf(stderr, "ERROR: could not write %s\n", path.c_str()); return 1; }
+    fprintf(stderr, "Completed in %ld msec \n\n", (long)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count());
+    return 0;
+}
+
 // ---- relatives (extract --closest-relatives / --within-distance: extract.cpp:768-823, select.cpp:577-714) -------------
 
 void relatives_usage(FILE *f) {
@@ -3266,6 +3476,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "relatives")) return relatives(argc - 2, argv + 2);
     if (!strcmp(argv[1], "select")) return select_samples(argc - 2, argv + 2);
     if (!strcmp(argv[1], "mask")) return mask(argc - 2, argv + 2);
-    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate, extract, summarize, translate, relatives, select, mask)\n", argv[1]);
+    if (!strcmp(argv[1], "haplotypes")) return haplotypes(argc - 2, argv + 2);
+    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate, extract, summarize, haplotypes, translate, relatives, select, mask)\n", argv[1]);
     return 1;
 }

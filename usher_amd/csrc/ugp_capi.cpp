@@ -31,6 +31,7 @@
 #include "ugp_annotate.hpp"
 #include "ugp_nearest.hpp"
 #include "ugp_relatives.hpp"
+#include "ugp_haplotypes.hpp"
 #include "ugp_mask.hpp"
 #include "ugp_select.hpp"
 #include "ugp_genotypes.hpp"
@@ -311,6 +312,7 @@ struct ugp_mat {
     ugp::TrState *tr = nullptr;      // matUtils summary --translate tables (ugp_translate_attach), or none
     ugp::SelState *sel = nullptr;    // matUtils extract selector tables (ugp_select_attach), or none
     ugp::MskState *msk = nullptr;    // matUtils mask tables (ugp_mask_attach), or none
+    ugp::HpState *hp = nullptr;      // matUtils summary --haplotype tables (ugp_haplotypes_attach), or none
     ugp::DfsTables *dfs = nullptr;   // the depth-first tables uncertainty and annotate share (their first attach), or none
     hipEvent_t kb_done = nullptr;    // behind the latest k_best8 launch of this handle ...
     hipStream_t kb_done_on = nullptr;   // ... on this stream
@@ -1439,6 +1441,7 @@ void ugp_mat_destroy(ugp_mat *m) {
     ugp::tr_free(m->tr);
     ugp::sel_free(m->sel);
     ugp::msk_free(m->msk);
+    ugp::hp_free(m->hp);
     ugp::dfs_tables_free(m->dfs);
     delete m;
 }
@@ -2153,6 +2156,38 @@ int ugp_translate(ugp_mat *m, ugp_tr_record *out, uint64_t cap, uint64_t *n_out,
 int ugp_translate_time(ugp_mat *m, uint32_t reps, double *ms) {
     if (!m) return fail(UGP_ERR_INVALID, "null argument");
     return ugp::tr_time(m->tr, reps, ms);
+}
+
+// ---- matUtils summary --haplotype: the distinct haplotypes of the leaves (ugp_haplotypes.hip) ----------------------------
+
+int ugp_haplotypes_attach(ugp_mat *m, const ugp_tree_desc *tree) {
+    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
+    if (int rc = check_handle_tree(m, tree)) return rc;
+    return ugp::hp_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->hp);
+}
+
+int ugp_haplotype_groups_hashed(ugp_mat *m, ugp_hp_group *out, uint64_t cap, uint64_t *n_out, ugp_hp_info *info, uint32_t hash_bits) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::hp_groups(m->hp, out, cap, n_out, info, hash_bits);
+}
+
+int ugp_haplotype_groups(ugp_mat *m, ugp_hp_group *out, uint64_t cap, uint64_t *n_out, ugp_hp_info *info) {
+    return ugp_haplotype_groups_hashed(m, out, cap, n_out, info, 128);
+}
+
+int ugp_haplotype_sets_chunked(ugp_mat *m, const uint32_t *leaves, uint64_t n, uint64_t *off, int32_t *pos, uint8_t *nuc, uint64_t cap,
+                               uint64_t *n_out, uint64_t chunk_leaves) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::hp_sets(m->hp, leaves, n, off, pos, nuc, cap, n_out, chunk_leaves);
+}
+
+int ugp_haplotype_sets(ugp_mat *m, const uint32_t *leaves, uint64_t n, uint64_t *off, int32_t *pos, uint8_t *nuc, uint64_t cap, uint64_t *n_out) {
+    return ugp_haplotype_sets_chunked(m, leaves, n, off, pos, nuc, cap, n_out, 0);
+}
+
+int ugp_haplotype_time(ugp_mat *m, uint32_t reps, double *scan_ms, double *sort_ms, double *verify_ms) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::hp_time(m->hp, reps, scan_ms, sort_ms, verify_ms);
 }
 
 // ---- RIPPLES (ugp_ripples.hip) -----------------------------------------------------------------------------------------

@@ -772,6 +772,72 @@ class Placer:
                                        _ptr(flat) if len(flat) else None, int(reps), C.byref(a), C.byref(b)))
         return float(a.value), float(b.value)
 
+    # ---- matUtils summary --haplotype (ugp_haplotypes_attach / ugp_haplotype_groups / _sets) --------------------------------------
+    HP_GROUP = np.dtype([("leaf", np.uint32), ("count", np.uint32), ("size", np.uint32), ("pad", np.uint32)])
+    HP_INFO = np.dtype([("n_leaves", np.uint64), ("n_groups", np.uint64), ("n_collisions", np.uint64), ("n_duplicate", np.uint64),
+                        ("n_visited", np.uint64), ("first_duplicate", np.uint32), ("pad", np.uint32)])
+
+    def haplotypes_attach(self, arrays: Optional[Dict] = None):
+        """ugp_haplotypes_attach with the placer's own tree, or with other mutation arrays on the same topology (masked entries,
+        ambiguous alleles, a position twice on one node: trees the placement tables refuse).  The depth-first tables are shared as
+        genotypes_attach describes."""
+        t = self._t if arrays is None else _TreeArrays(arrays)
+        self._ck(self._L.ugp_haplotypes_attach(self._h, C.byref(t.desc)))
+
+    def haplotype_groups(self, hash_bits: int = 128, cap: Optional[int] = None, out: Optional[np.ndarray] = None):
+        """matUtils summary -H (summary.cpp:182-264): (groups, info) -- an HP_GROUP array, one record per distinct haplotype of the
+        leaves (the BFS index of its first leaf in depth-first order, its leaves, its pairs), ascending by the depth-first position
+        of that leaf, and an HP_INFO scalar.  A tree with a position twice on one node, or a fingerprint that groups leaves the
+        exact comparison tells apart, raises UgpError -2; the HP_INFO of the last call, refused or not, stays in _hp_info and the
+        count it reported in _hp_n_out.  hash_bits (test hook): the low bits of the fingerprint that take part; cap (test hook):
+        room for that many records only; out (test hook): the HP_GROUP buffer to write into (its length is the cap)."""
+        info = np.zeros(1, self.HP_INFO)
+        self._hp_info = None
+        n_out = C.c_uint64(0)
+
+        def call(buf, room):
+            rc = self._L.ugp_haplotype_groups_hashed(self._h, _ptr(buf) if room else None, int(room), C.byref(n_out), _ptr(info), int(hash_bits))
+            self._hp_n_out = int(n_out.value)
+            if rc != -1:   # (an invalid call fills nothing)
+                self._hp_info = info[0].copy()
+            self._ck(rc)
+
+        if out is not None:
+            cap = len(out)
+        elif cap is None:   # the two-call convention: the count, then the records
+            call(None, 0)
+            cap = int(n_out.value)
+        if out is None:
+            out = np.zeros(int(cap), self.HP_GROUP)
+        call(out, cap)
+        return out[:min(int(cap), self._hp_n_out)], info[0].copy()
+
+    def haplotype_sets(self, leaves, chunk_leaves: int = 0, cap: Optional[int] = None):
+        """ugp_haplotype_sets: (off, pos, nuc) -- the haplotypes of the given leaves (BFS) as a CSR: set i is pos / nuc[off[i] ..
+        off[i + 1]), ascending by position, nuc the stored 4-bit code.  An internal node in the list raises UgpError -1.
+        chunk_leaves (test hook): leaves per launch window; cap (test hook): room for that many pairs only, the true total is
+        off[-1] and in _hp_n_out."""
+        lv = np.ascontiguousarray(leaves, dtype=np.uint32)
+        off = np.zeros(len(lv) + 1, np.uint64)
+        n_out = C.c_uint64(0)
+        fn = self._L.ugp_haplotype_sets_chunked
+        if cap is None:   # the two-call convention: the offsets, then the pairs
+            self._ck(fn(self._h, _ptr(lv) if len(lv) else None, len(lv), _ptr(off), None, None, 0, C.byref(n_out), int(chunk_leaves)))
+            cap = int(n_out.value)
+        pos = np.zeros(int(cap), np.int32)
+        nuc = np.zeros(int(cap), np.uint8)
+        self._ck(fn(self._h, _ptr(lv) if len(lv) else None, len(lv), _ptr(off), _ptr(pos) if cap else None, _ptr(nuc) if cap else None,
+                    int(cap), C.byref(n_out), int(chunk_leaves)))
+        self._hp_n_out = int(n_out.value)
+        fill = min(int(cap), self._hp_n_out)
+        return off, pos[:fill], nuc[:fill]
+
+    def haplotype_time(self, reps: int = 5):
+        """Bench hook: (scan_ms, sort_ms, verify_ms), milliseconds of device time of the passes of haplotype_groups alone."""
+        a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._ck(self._L.ugp_haplotype_time(self._h, int(reps), C.byref(a), C.byref(b), C.byref(c)))
+        return float(a.value), float(b.value), float(c.value)
+
     RIPPLES_EVENT = np.dtype([("branch", np.uint64), ("i", np.uint32), ("j", np.uint32), ("donor", np.uint32), ("acceptor", np.uint32),
                               ("donor_count", np.uint32), ("acceptor_count", np.uint32), ("donor_score", np.int32),
                               ("acceptor_score", np.int32), ("donor_sibling", np.uint8), ("acceptor_sibling", np.uint8),
