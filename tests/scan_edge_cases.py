@@ -1,8 +1,8 @@
 """Fixtures for tests/test_scan_edges_gpu.py (and tests/test_scan_edge_cases_cpu.py, which proves with the references alone that each
-one has the property its GPU test relies on): trees that put the flag scans of matUtils summary, translate and genotypes
-(usher_amd/csrc/ugp_summary.hip, ugp_translate.hip, ugp_genotypes.hip) exactly on their edges -- an item count of one segment less
-one, one segment, one more, one segment and one pass, two segments, two and one item -- with chosen flags on both sides of the
-seam between the first two segments.  Every generator takes its count and the place of the seam as parameters, so that the CPU
+one has the property its GPU test relies on): trees that put the segmented flag scan of usher_amd/csrc/ugp_scan.hpp, as matUtils
+summary, translate, genotypes, nearest and relatives launch it (ugp_summary.hip, ugp_translate.hip, ugp_genotypes.hip,
+ugp_nearest.hip, ugp_relatives.hip), exactly on its edges -- an item count of one segment less one, one segment, one more, one
+segment and one pass, two segments, two and one item -- with chosen flags on both sides of the seam between the first two segments.  Every generator takes its count and the place of the seam as parameters, so that the CPU
 module runs the same shapes small against the literal references.  Everything is built here, nothing is read from disk."""
 import collections
 import functools
@@ -167,6 +167,22 @@ def leaf_prefix_marks(N, seam=KSEG):
     if N - tail > seam + 21:
         return chain, seam - 10
     return chain, (chain[0] if N > seam else None)
+
+
+LEAF_QUERY_EDGES = (KSEG - 1, KSEG, KSEG + 1, 2 * KSEG + 1)
+NEAREST_KS = (1, 4, 30, 45, 1000)      # below, at and above the 30 leaves of the hub at the seam and the 38 of the chain
+WITHIN_KS = (0, 1, 2, 5)
+
+
+def leaf_prefix_queries(arrays, N, seam=KSEG):
+    """Breadth-first indices of the nodes the nearest and relatives tests ask about on leaf_prefix_tree(N, True): the leaves at
+    depth-first positions seam - 1 and seam (where N has them), the first and the last leaf, and the chain [c1, c2, c3]."""
+    d2b = dfs_to_bfs(arrays)
+    leaf = np.ones(N, bool)
+    leaf[np.asarray(arrays["parent"])[1:]] = False
+    leaf_dfs = np.flatnonzero(leaf[d2b])
+    want = [seam - 1, seam, int(leaf_dfs[0]), int(leaf_dfs[-1])] + leaf_prefix_marks(N, seam)[0]
+    return d2b[[d for d in dict.fromkeys(want) if d < N]]
 
 
 def node_selection(N, seam=KSEG, extra=300):

@@ -7,7 +7,7 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "usher_amd", "csrc")
 SCAN = 4 * 4   # block_incl_scan: one int per wave
-LDS = {"k_gt_e2x": 0, "k_gt_owner": 0, "k_gt_mark": 0, "k_gt_segsum": SCAN, "k_gt_rank": SCAN, "k_gt_count": 0, "k_gt_flag": 0,
+LDS = {"k_gt_e2x": 0, "k_gt_owner": 0, "k_gt_mark": 0, "k_flag_segsum": SCAN, "k_gt_rank": SCAN, "k_gt_count": 0, "k_gt_flag": 0,
        "k_gt_compact": SCAN, "k_gt_table": 0, "k_gt_rows": 0}
 
 

@@ -7,7 +7,7 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "usher_amd", "csrc")
 SCAN = 4 * 4   # block_incl_scan: one int per wave
-LDS = {"k_nk_lpre": SCAN, "k_nk_anchor": 0, "k_nk_hist": 2048 * 4, "k_nk_pick": SCAN, "k_nk_count": SCAN, "k_nk_offsets": 0,
+LDS = {"k_flag_segsum": SCAN, "k_flag_scan": SCAN, "k_nk_anchor": 0, "k_nk_hist": 2048 * 4, "k_nk_pick": SCAN, "k_nk_count": SCAN, "k_nk_offsets": 0,
        "k_nk_write": SCAN, "k_nk_sortILb1": 4096 * 8, "k_nk_sortILb0": 0, "k_nk_tobfs": 0}
 
 

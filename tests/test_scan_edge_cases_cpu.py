@@ -3,7 +3,8 @@ alone (tests/summary_ref.py, translate_ref.py, genotypes_ref.py), so that a fixt
 letting the GPU test pass vacuously: exact item counts at every edge, the flags each variant claims on both sides of the seam
 between the first two segments, a set flag in every segment and a last segment that does not hold the whole count (so that a lost
 carry or an unwritten out[n] changes the answer), and -- with the same generators run small, the seam at 128 -- the fast references
-against the literal ones on these shapes of tree.  CPU only.
+against the literal ones on these shapes of tree.  For the leaf prefix of nearest and relatives (tests/nearest_ref.py, relatives_ref.py)
+the references themselves are run with a prefix that dropped its carry: an answer to one of the queried nodes changes.  CPU only.
 
 The carry loop of the scan kernels, `for (k = threadIdx.x; k < g; k += kBlock)`, takes a second stride only in a scan of more than
 256 * KSEG = 4,194,304 items.  The largest scan anywhere in the suite is that of test_summary_at_size's tree: M = 1,005,501 entries
@@ -16,6 +17,8 @@ import numpy as np
 import pytest
 
 from tests import genotypes_ref as GR
+from tests import nearest_ref as NR
+from tests import relatives_ref as RR
 from tests import scan_edge_cases as S
 from tests import summary_cases as SC
 from tests import summary_ref as SR
@@ -174,6 +177,40 @@ def test_leaf_prefix_trees(N):
         assert len(want.sites) > 20 and want.codes.any(axis=0)[[np.searchsorted(sel, KSEG - 1), np.searchsorted(sel, KSEG)]].all()
 
 
+def nearest_answers(F, nodes):
+    return [F.query(int(v), k) for v in nodes for k in S.NEAREST_KS]
+
+
+def relatives_answers(F, nodes):
+    return [F.closest(int(v)) for v in nodes] + [F.within(int(v), k) for k in S.WITHIN_KS for v in nodes]
+
+
+def name_ranks(N):
+    return np.random.default_rng(N).permutation(N).astype(np.uint32)
+
+
+@pytest.mark.parametrize("N", S.LEAF_QUERY_EDGES)
+def test_leaf_prefix_queries(N):
+    """What test_scan_edges_gpu asks nearest and relatives: the two seam leaves and a node behind the seam are among the queries,
+    and a leaf prefix without its carry gives another answer to at least one of them, from either reference."""
+    arrays = S.leaf_prefix_tree(N, True)
+    nodes = S.leaf_prefix_queries(arrays, N)
+    F = SR.Fast(arrays)
+    asked = F.pre[nodes].tolist()
+    chain, _ = S.leaf_prefix_marks(N)
+    assert len(set(asked)) == len(asked) and set(chain) <= set(asked) and N - 1 in asked and F.leaf[nodes].sum() == len(nodes) - 3
+    assert {d for d in (KSEG - 1, KSEG) if d < N} <= set(asked)
+    leaf_dfs = F.leaf[np.argsort(F.pre)].astype(np.int64)
+    for fast, answers in ((NR.Fast(arrays), nearest_answers), (RR.Fast(arrays, name_ranks(N)), relatives_answers)):
+        assert fast.lpre.tolist() == model_scan(leaf_dfs, KSEG).tolist()
+        right = answers(fast, nodes)
+        assert sum(w["count"] > 0 for w in right) > len(right) // 2
+        if N > KSEG:
+            assert max(asked) >= KSEG                           # a node in the second segment
+            fast.lpre = model_scan(leaf_dfs, KSEG, "no_carry")
+            assert answers(fast, nodes) != right
+
+
 # ---- RoHo ---------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("variant", S.VARIANTS)
@@ -309,6 +346,17 @@ def test_references_agree_on_small_leaf_prefix_trees(N):
         lit, fast = GR.literal(arrays, sel), G.run(sel)
         assert GR.site_rows(lit.sites) == GR.site_rows(fast.sites) and len(lit.sites) > 5
         assert np.array_equal(lit.codes, fast.codes) and np.array_equal(lit.columns, fast.columns)
+
+
+@pytest.mark.parametrize("N", [SMALL + 1, SMALL + 100, 500])
+def test_references_agree_on_small_leaf_prefix_queries(N):
+    arrays = S.leaf_prefix_tree(N, True, seam=SMALL)
+    nodes = S.leaf_prefix_queries(arrays, N, SMALL)
+    rank = name_ranks(N)
+    NT, RT = NR.Tree(arrays), RR.Tree(arrays)
+    assert nearest_answers(NR.Fast(arrays), nodes) == [NR.literal(NT, int(v), k) for v in nodes for k in S.NEAREST_KS]
+    assert relatives_answers(RR.Fast(arrays, rank), nodes) == ([RR.literal(RT, int(v), False, 0, rank) for v in nodes] +
+                                                                [RR.literal(RT, int(v), True, k) for k in S.WITHIN_KS for v in nodes])
 
 
 @pytest.mark.parametrize("variant", S.VARIANTS)

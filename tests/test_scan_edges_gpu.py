@@ -1,8 +1,9 @@
-"""The segmented flag scans of matUtils summary, translate and genotypes (k_sm_segsum / k_sm_scan, k_tr_segsum / k_tr_scan,
-k_gt_segsum / k_gt_rank, the tiles of k_gt_compact) and the 16-column store of k_gt_rows exactly on their edges: item counts of a
-segment less one, a segment, one more, a segment and a pass, two segments, two and one item; launch windows of a segment less one,
-a segment, one more and two; `cap` cutting the records at the seam between two windows; chosen flags on both sides of the seam.
-Every field that comes back is compared with summary_ref.Fast, translate_ref.Fast and genotypes_ref.Fast, exactly;
+"""The segmented flag scan of usher_amd/csrc/ugp_scan.hpp (k_flag_segsum / k_flag_scan, and k_gt_rank on the same body) as matUtils
+summary, translate, genotypes, nearest and relatives launch it, the tiles of k_gt_compact and the 16-column store of k_gt_rows
+exactly on their edges: item counts of a segment less one, a segment, one more, a segment and a pass, two segments, two and one
+item; launch windows of a segment less one, a segment, one more and two; `cap` cutting the records at the seam between two
+windows; chosen flags on both sides of the seam.  Every field that comes back is compared with summary_ref.Fast,
+translate_ref.Fast, genotypes_ref.Fast, nearest_ref.Fast and relatives_ref.Fast, exactly;
 tests/test_scan_edge_cases_cpu.py proves that the fixtures of tests/scan_edge_cases.py have the properties relied on here and that
 those references follow the literal ones on these shapes of tree."""
 import ctypes as C
@@ -12,6 +13,8 @@ import pytest
 
 from tests import genotypes_cases as GC
 from tests import genotypes_ref as GR
+from tests import nearest_ref as NR
+from tests import relatives_ref as RR
 from tests import scan_edge_cases as S
 from tests import summary_cases as SC
 from tests import summary_ref as SR
@@ -88,6 +91,34 @@ def test_leaf_prefix(N):
     assert SR.device_roho_fast(F, pl.summary_roho()) == F.roho()[0]
     assert mutation_rows(pl.summary_mutations()) == F.mutations()
     pl.close()
+
+
+# ---- nearest and relatives: the leaf prefix over the N nodes -----------------------------------------------------------------------
+
+@pytest.mark.parametrize("N", S.LEAF_QUERY_EDGES)
+def test_nearest_leaf_prefix(N):
+    arrays = S.leaf_prefix_tree(N, True)
+    nodes = np.repeat(S.leaf_prefix_queries(arrays, N), len(S.NEAREST_KS))
+    ks = np.tile(S.NEAREST_KS, len(nodes) // len(S.NEAREST_KS))
+    want = CPU.nearest_answers(NR.Fast(arrays), S.leaf_prefix_queries(arrays, N))
+    pl = Placer(arrays)
+    got = pl.nearest_k(nodes, ks)
+    pl.close()
+    for i, w in enumerate(want):
+        NR.check(got, w, i, max(S.NEAREST_KS))
+
+
+@pytest.mark.parametrize("N", S.LEAF_QUERY_EDGES)
+def test_relatives_leaf_prefix(N):
+    arrays = S.leaf_prefix_tree(N, True)
+    nodes, rank = S.leaf_prefix_queries(arrays, N), CPU.name_ranks(N)
+    want = CPU.relatives_answers(RR.Fast(arrays, rank), nodes)
+    pl = Placer(arrays)
+    pl.relatives_attach(rank)
+    got = [pl.relatives_closest(nodes)] + [pl.relatives_within(nodes, k) for k in S.WITHIN_KS]
+    pl.close()
+    for i, w in enumerate(want):
+        RR.check(got[i // len(nodes)], w, i % len(nodes))
 
 
 # ---- summary: the records of every RoHo window -------------------------------------------------------------------------------------

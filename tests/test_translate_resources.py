@@ -7,7 +7,7 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "usher_amd", "csrc")
 SCAN = 4 * 4   # block_incl_scan: one int per wave
-LDS = {"k_tr_onode": 0, "k_tr_items": 0, "k_tr_segsum": SCAN, "k_tr_scan": SCAN, "k_tr_emit": 0}
+LDS = {"k_tr_onode": 0, "k_tr_items": 0, "k_flag_segsum": SCAN, "k_flag_scan": SCAN, "k_tr_emit": 0}
 
 
 def test_translate_kernels_do_not_spill(tmp_path):

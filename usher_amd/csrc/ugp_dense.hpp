@@ -1,5 +1,5 @@
 // ugp_dense.hpp -- what the dense searches of ugp_uncertainty.hip and ugp_annotate.hip share, and the helpers RIPPLES
-// (ugp_ripples.hip) reads too: device buffers, the error macro, the entry bits and loop 2 of mapper2_body, block scans, the
+// (ugp_ripples.hip) reads too: device buffers, the error macro, the entry bits and loop 2 of mapper2_body, the scans (ugp_scan.hpp), the
 // depth-first tables of a handle's tree and the literal score of one node against one sample.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -72,30 +72,13 @@ __host__ __device__ __forceinline__ int row_cost(uint32_t a, uint32_t r, uint32_
     return ((a & r) ? r : lowbit4(a)) != s ? 1 : 0;
 }
 
-// ---- scans --------------------------------------------------------------------------------------------------------
+}  // namespace ugp
 
-__device__ __forceinline__ int wave_incl_scan(int v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-// Inclusive scan over the block (kBlock threads); *total = block sum.  Uses sh[kBlock / 64].
-__device__ __forceinline__ int block_incl_scan(int v, int *sh, int *total) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int x = wave_incl_scan(v);
-    if (lane == 63) sh[w] = x;
-    __syncthreads();
-    int pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < (int)(kBlock / 64); k++) { const int s = sh[k]; if (k < w) pre += s; tot += s; }
-    __syncthreads();
-    *total = tot;
-    return x + pre;
-}
+// ---- scans: block_incl_scan, k_segsum, seg_carry, the flag scan and the launch sizes ------------------------------
+#include "ugp_scan.hpp"
+
+namespace ugp {
+
 // First index in [lo, hi) of the sorted xs with xs[k] >= v.
 __device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t *xs, uint32_t lo, uint32_t hi, uint32_t v) {
     while (lo < hi) {
@@ -279,21 +262,6 @@ __device__ __forceinline__ void score_segment(const DfsView &t, const Rows &R, c
         for (int k = 1; k < (int)(kBlock / 64); k++) m = min(m, smin[k]);
         if (m != kNone) atomicMin(mn, m);
     }
-}
-
-// One block per (segment blockIdx.x, sample blockIdx.y): the sum of the sample's difference array over the segment.  (A
-// template only so that it is compiled where it is launched.)
-template <typename = void>
-__global__ void __launch_bounds__(kBlock) k_segsum(uint32_t n, uint32_t nseg, const int32_t *diff, int32_t *seg) {
-    __shared__ int sh[kBlock / 64];
-    const uint32_t g = blockIdx.x, s = blockIdx.y;
-    const uint32_t lo = g * kSeg, hi = min(n, lo + kSeg);
-    diff += (size_t)s * n;
-    int acc = 0;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += kBlock) acc += diff[i];
-    int tot;
-    (void)block_incl_scan(acc, sh, &tot);
-    if (threadIdx.x == 0) seg[(size_t)s * nseg + g] = tot;
 }
 
 // The positions i of segment g with sc[i] == m, in ascending order, to ties[base ..] while below cap; f(i) sees every one.

@@ -12,7 +12,8 @@
 // Summed per allele that is  cnt[allele(e)] += len(e), cnt[allele(owner above e)] -= len(e)  (DESIGN.md 12): no walk per column.
 //   k_gt_e2x / k_gt_owner          attach: per owner its node, the owner above, the allele of the LAST non-masked entry of the
 //                                  position on the node, mut_par of the first;
-//   k_gt_mark / k_gt_segsum / k_gt_rank   the selection flags in depth-first order, their prefix count and the column -> node list;
+//   k_gt_mark / k_flag_segsum / k_gt_rank   the selection flags in depth-first order, their prefix count (the flag scan of
+//                                  ugp_scan.hpp with a callable of its own) and the column -> node list;
 //   k_gt_count                     the closed-form counts, the covered columns and the first owner with columns (REF);
 //   k_gt_flag / k_gt_compact / k_gt_table   positions with an alternate, in ascending order: the site table and a 16-byte
 //                                  allele -> code map per site;
@@ -64,38 +65,13 @@ __global__ void k_gt_mark(const uint32_t *pos, uint32_t nsel, uint8_t *flag) {
     if (i < nsel) flag[pos[i]] = 1;
 }
 
-// One block per segment: the selected nodes of the segment.
-__global__ void __launch_bounds__(kBlock) k_gt_segsum(uint32_t n, const uint8_t *flag, uint32_t *seg) {
-    __shared__ int sh[kBlock / 64];
-    const uint32_t lo = blockIdx.x * kSeg, hi = min(n, lo + kSeg);
-    int acc = 0;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += kBlock) acc += flag[i] ? 1 : 0;
-    int tot;
-    (void)block_incl_scan(acc, sh, &tot);
-    if (threadIdx.x == 0) seg[blockIdx.x] = (uint32_t)tot;
-}
-
 // One block per segment: rank[i] = selected nodes before i (the carry: the segments before), rank[n] = all; column -> node.
 __global__ void __launch_bounds__(kBlock) k_gt_rank(uint32_t n, const uint8_t *flag, const uint32_t *seg, uint32_t *rank, uint32_t *coldfs) {
-    __shared__ int sh[kBlock / 64];
-    const uint32_t g = blockIdx.x, lo = g * kSeg, hi = min(n, lo + kSeg);
-    int acc = 0;
-    for (uint32_t k = threadIdx.x; k < g; k += kBlock) acc += (int)seg[k];
-    int tot;
-    (void)block_incl_scan(acc, sh, &tot);
-    uint32_t carry = (uint32_t)tot;
-    for (uint32_t t0 = lo; t0 < hi; t0 += kBlock) {
-        const uint32_t i = t0 + threadIdx.x;
-        const int f = (i < hi && flag[i]) ? 1 : 0;
-        const int incl = block_incl_scan(f, sh, &tot);
-        if (i < hi) {
-            const uint32_t r = carry + (uint32_t)(incl - f);
-            rank[i] = r;
-            if (f) coldfs[r] = i;
-        }
-        carry += (uint32_t)tot;
-    }
-    if (hi == n && threadIdx.x == 0) rank[n] = carry;
+    const uint32_t all = scan_flag_segment(n, flag, seg, blockIdx.x, [&](uint32_t i, uint32_t before, bool set) {
+        rank[i] = before;
+        if (set) coldfs[before] = i;
+    });
+    if (last_segment(n, blockIdx.x) && threadIdx.x == 0) rank[n] = all;
 }
 
 // One thread per owner: its columns to its allele and from the allele of the owner above (none: to the covered columns).
@@ -215,8 +191,6 @@ __global__ void __launch_bounds__(kBlock) k_gt_rows(DfsView t, uint32_t ncols, u
     *reinterpret_cast<uint4 *>(out + ((size_t)r * gw + g) * kCellsPerThread) = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
-
 }  // namespace
 
 struct GtState {
@@ -334,7 +308,7 @@ int gt_select(GtState *S, const uint32_t *nodes, uint64_t nsel, uint32_t *n_cols
         UGP_HIP_TRY(S->coldfs.alloc(nsel ? std::min<uint64_t>(nsel, N) : N));
         UGP_HIP_TRY(S->cnt.alloc((size_t)np * 16)); UGP_HIP_TRY(S->cov.alloc(np)); UGP_HIP_TRY(S->first.alloc(np));
         UGP_HIP_TRY(S->pflag.alloc(np)); UGP_HIP_TRY(S->sitej.alloc(np)); UGP_HIP_TRY(S->nsites_d.alloc(1));
-        k_gt_segsum<<<nseg, kBlock, 0, st>>>(N, flag, S->seg.p);
+        k_flag_segsum<<<nseg, kBlock, 0, st>>>(N, flag, S->seg.p);
         k_gt_rank<<<nseg, kBlock, 0, st>>>(N, flag, S->seg.p, S->rank.p, S->coldfs.p);
         UGP_HIP_TRY(hipGetLastError());
         UGP_HIP_TRY(hipMemsetAsync(S->nsites_d.p, 0, sizeof(uint32_t), st));

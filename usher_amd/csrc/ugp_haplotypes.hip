@@ -9,17 +9,17 @@
 // -d(v) at dend[v], d(v) the sum of the node's own differences.  All sums wrap modulo 2^64, so their order is free.
 //   k_hp_diff                      per node d(v) in three lanes (two of the mix, one the size of the set), added at v and taken away at
 //                                  dend[v] with integer atomics;
-//   k_hp_segsum / k_hp_scan        the inclusive scan over the depth-first positions, in place, kSeg positions per block;
+//   k_segsum / k_hp_scan           the inclusive scan over the depth-first positions, in place, kSeg positions per block (the
+//                                  segment sums, the carry and the block scan are those of ugp_scan.hpp, over 64-bit wrapping sums);
 //   k_hp_gather / (rocprim radix sort, twice)     the leaves ordered by (fingerprint, depth-first rank): the low lane, then stably
 //                                  the high lane;
-//   k_hp_heads / k_hp_fsegsum + k_hp_fscan        the first leaf of every run of equal fingerprints and the runs in front of each;
+//   k_hp_heads / (scan_flags, ugp_scan.hpp)       the first leaf of every run of equal fingerprints and the runs in front of each;
 //   k_hp_verify                    every other leaf against the leaf in front of it, exactly: up both paths to the lowest common
 //                                  ancestor, every entry's position looked up for both leaves among the position's owners;
 //   k_hp_runs / (radix sort) / k_hp_emit          one record per run, in depth-first order of the run's first leaf;
 //   k_hp_sizes / k_hp_fill / (rocprim segmented sort)     the sets of given leaves: sizes from the third lane, pairs by a climb of the
 //                                  root path that keeps an entry when the lookup from the leaf names that very entry.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include <algorithm>
@@ -29,6 +29,7 @@
 
 #include "ugp_dense.hpp"
 #include "ugp_haplotypes.hpp"
+#include "ugp_sort.hpp"
 #include "ugp_translate.hpp"
 
 namespace ugp {
@@ -69,54 +70,16 @@ __global__ void k_hp_diff(DfsView t, unsigned long long *xa, unsigned long long 
     if (end < t.n) { atomicAdd(&xa[end], 0ull - da); atomicAdd(&xb[end], 0ull - db); atomicAdd(&xs[end], 0ull - ds); }
 }
 
-__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = __shfl_up((unsigned long long)v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-// block_incl_scan of ugp_dense.hpp over 64-bit wrapping sums.  Uses sh[kBlock / 64].
-__device__ __forceinline__ uint64_t block_incl_scan64(uint64_t v, uint64_t *sh, uint64_t *total) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint64_t x = wave_incl_scan64(v);
-    if (lane == 63) sh[w] = x;
-    __syncthreads();
-    uint64_t pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < (int)(kBlock / 64); k++) { const uint64_t s = sh[k]; if (k < w) pre += s; tot += s; }
-    __syncthreads();
-    *total = tot;
-    return x + pre;
-}
-
-// One block per (segment, lane blockIdx.y): the sum of the lane's array over the segment.
-__global__ void __launch_bounds__(kBlock) k_hp_segsum(uint32_t n, uint32_t nseg, const uint64_t *x, uint64_t *seg) {
-    __shared__ uint64_t sh[kBlock / 64];
-    const uint32_t lo = blockIdx.x * kSeg, hi = min(n, lo + kSeg);
-    x += (size_t)blockIdx.y * n;
-    uint64_t acc = 0;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += kBlock) acc += x[i];
-    uint64_t tot;
-    (void)block_incl_scan64(acc, sh, &tot);
-    if (threadIdx.x == 0) seg[(size_t)blockIdx.y * nseg + blockIdx.x] = tot;
-}
-
 // One block per (segment, lane): the inclusive scan of the lane's array, in place (the carry: the segments before).
 __global__ void __launch_bounds__(kBlock) k_hp_scan(uint32_t n, uint32_t nseg, uint64_t *x, const uint64_t *seg) {
     __shared__ uint64_t sh[kBlock / 64];
     const uint32_t g = blockIdx.x, lo = g * kSeg, hi = min(n, lo + kSeg);
     x += (size_t)blockIdx.y * n;
     seg += (size_t)blockIdx.y * nseg;
-    uint64_t acc = 0, tot;
-    for (uint32_t k = threadIdx.x; k < g; k += kBlock) acc += seg[k];
-    (void)block_incl_scan64(acc, sh, &tot);
-    uint64_t carry = tot;
+    uint64_t carry = seg_carry(seg, g, sh), tot;
     for (uint32_t t0 = lo; t0 < hi; t0 += kBlock) {
         const uint32_t i = t0 + threadIdx.x;
-        const uint64_t incl = block_incl_scan64(i < hi ? x[i] : 0, sh, &tot);
+        const uint64_t incl = block_incl_scan<uint64_t>(i < hi ? x[i] : 0, sh, &tot);
         if (i < hi) x[i] = carry + incl;
         carry += tot;
     }
@@ -142,36 +105,6 @@ __global__ void k_hp_heads(uint32_t nl, const uint32_t *ldfs, const uint32_t *or
         h = (((fa[u] ^ fa[v]) & ma) | ((fb[u] ^ fb[v]) & mb)) ? 1 : 0;
     }
     head[x] = h;
-}
-
-// One block per segment: the flags set in it.
-__global__ void __launch_bounds__(kBlock) k_hp_fsegsum(uint32_t n, const uint8_t *flag, uint32_t *seg) {
-    __shared__ int sh[kBlock / 64];
-    const uint32_t lo = blockIdx.x * kSeg, hi = min(n, lo + kSeg);
-    int acc = 0;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += kBlock) acc += flag[i] ? 1 : 0;
-    int tot;
-    (void)block_incl_scan(acc, sh, &tot);
-    if (threadIdx.x == 0) seg[blockIdx.x] = (uint32_t)tot;
-}
-
-// One block per segment: out[i] = flags set before i (the carry: the segments before), out[n] = all of them.
-__global__ void __launch_bounds__(kBlock) k_hp_fscan(uint32_t n, const uint8_t *flag, const uint32_t *seg, uint32_t *out) {
-    __shared__ int sh[kBlock / 64];
-    const uint32_t g = blockIdx.x, lo = g * kSeg, hi = min(n, lo + kSeg);
-    int acc = 0;
-    for (uint32_t k = threadIdx.x; k < g; k += kBlock) acc += (int)seg[k];
-    int tot;
-    (void)block_incl_scan(acc, sh, &tot);
-    uint32_t carry = (uint32_t)tot;
-    for (uint32_t t0 = lo; t0 < hi; t0 += kBlock) {
-        const uint32_t i = t0 + threadIdx.x;
-        const int f = (i < hi && flag[i]) ? 1 : 0;
-        const int incl = block_incl_scan(f, sh, &tot);
-        if (i < hi) out[i] = carry + (uint32_t)(incl - f);
-        carry += (uint32_t)tot;
-    }
-    if (hi == n && threadIdx.x == 0) out[n] = carry;
 }
 
 // The owner (kNil: none) in force at position p for node v, v's own included: the last owner of p not behind v in depth-first
@@ -271,20 +204,7 @@ __global__ void __launch_bounds__(kBlock) k_hp_fill(DfsView t, const uint32_t *o
     if (o != end || extra) atomicAdd(wrong, 1u);
 }
 
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
-inline uint32_t segs_for(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + kSeg - 1) / kSeg); }
-inline unsigned bits_for(uint64_t v) { unsigned b = 1; while (b < 64 && (v >> b)) b++; return b; }   // v < 2^b
 inline uint64_t low_mask(uint32_t bits) { return bits >= 64 ? ~0ull : (1ull << bits) - 1; }
-
-template <typename K>
-hipError_t sort_pairs(DBuf<unsigned char> &tmp, const K *kin, K *kout, const uint32_t *vin, uint32_t *vout, size_t n, unsigned bits,
-                      hipStream_t st) {
-    size_t bytes = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, n, 0u, bits, st);
-    if (e == hipSuccess) e = tmp.alloc(bytes);
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp.p, bytes, kin, kout, vin, vout, n, 0u, bits, st);
-    return e;
-}
 
 }  // namespace
 
@@ -377,7 +297,7 @@ static int pass_scan(HpState *S) {
     UGP_HIP_TRY(hipMemsetAsync(S->f.p, 0, 3 * (size_t)N * sizeof(uint64_t), st));
     unsigned long long *x = reinterpret_cast<unsigned long long *>(S->f.p);
     k_hp_diff<<<blocks_for(N), kBlock, 0, st>>>(t, x, x + N, x + 2 * (size_t)N);
-    k_hp_segsum<<<dim3(nseg, 3), kBlock, 0, st>>>(N, nseg, S->f.p, S->seg.p);
+    k_segsum<<<dim3(nseg, 3), kBlock, 0, st>>>(N, nseg, S->f.p, S->seg.p);
     k_hp_scan<<<dim3(nseg, 3), kBlock, 0, st>>>(N, nseg, S->f.p, S->seg.p);
     UGP_HIP_TRY(hipGetLastError());
     S->have_fp = true;
@@ -449,10 +369,7 @@ int hp_groups(HpState *S, ugp_hp_group *out, uint64_t cap, uint64_t *n_out, ugp_
     if (int rc = pass_scan(S)) return rc;
     if (int rc = pass_sort(S, hash_bits)) return rc;
     if (int rc = pass_verify(S)) return rc;
-    const uint32_t nseg = segs_for(L);
-    k_hp_fsegsum<<<nseg, kBlock, 0, st>>>(L, S->head.p, S->fseg.p);
-    k_hp_fscan<<<nseg, kBlock, 0, st>>>(L, S->head.p, S->fseg.p, S->hidx.p);
-    UGP_HIP_TRY(hipGetLastError());
+    UGP_HIP_TRY(scan_flags(S->fseg, L, S->head.p, S->hidx.p, st));
     uint32_t runs = 0;
     unsigned long long counters[2] = {0, 0};
     UGP_HIP_TRY(hipMemcpyAsync(&runs, S->hidx.p + L, sizeof(uint32_t), hipMemcpyDeviceToHost, st));

@@ -4,7 +4,7 @@
 // Restricted samples, every named node a leaf.  Leaf r is the r-th leaf in depth-first order; the leaves below v are the ranks
 // [lbefore[v], lbefore[dend[v]]).  full[v]: all of them are named.  F: the inner nodes that are full and have a leaf child.
 //   k_msk_names      one lane per name: its bit of the bitmap over leaf ranks
-//   k_msk_segsum / k_msk_wordscan   the named ranks in front of every word of the bitmap
+//   k_msk_segsum / k_msk_wordscan   the named ranks in front of every word of the bitmap (seg_carry, block_incl_scan: ugp_scan.hpp)
 //   k_msk_full       one lane per node: full[v]; a node of F adds +1 at v and -1 at dend[v] to a difference array
 //   k_msk_segsum / k_msk_cover      A[v] = the nodes of F on v's root path, v included, by a scan over depth-first order.  A root is a
 //                    node of F with A = 1, or a named leaf whose parent is not full; v is covered when A >= 1 or it is such a leaf
@@ -58,15 +58,6 @@ __global__ void __launch_bounds__(kBlock) k_msk_segsum(uint32_t n, In in, int32_
     int tot;
     (void)block_incl_scan(acc, sh, &tot);
     if (threadIdx.x == 0) seg[blockIdx.x] = tot;
-}
-
-// The sum of the segments before g (the carry), by the whole block.
-__device__ __forceinline__ int seg_carry(const int32_t *seg, uint32_t g, int *sh) {
-    int acc = 0;
-    for (uint32_t k = threadIdx.x; k < g; k += kBlock) acc += seg[k];
-    int tot;
-    (void)block_incl_scan(acc, sh, &tot);
-    return tot;
 }
 
 // One block per segment: wpre[i] = the bits set in the words before word i.
@@ -178,9 +169,6 @@ __global__ void __launch_bounds__(kBlock) k_msk_mutations(DfsView t, uint32_t m,
         return;
     }
 }
-
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
-inline uint32_t segs_for(uint64_t n) { return (uint32_t)((n + kSeg - 1) / kSeg); }
 
 }  // namespace
 

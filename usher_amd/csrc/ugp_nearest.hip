@@ -11,6 +11,7 @@
 // lpre[dend[v]] - lpre[v] with lpre the prefix count of the leaf flags, and the distance is cum[l] - cum[anc].  So a query is "the
 // `need` smallest keys cum[i] - cum[anc] over the leaf positions of [anc, dend[anc]) outside (last_anc, dend[last_anc])", ties by
 // position (what a stable sort gives; the reference's std::sort leaves them to introsort):
+//   (scan_flags, ugp_scan.hpp)   attach: lpre;
 //   k_nk_anchor   one lane per query climbs dpar;
 //   k_nk_hist     one block per (segment of kSeg positions, query) that overlaps the range: an LDS histogram of one 11-bit key
 //                 digit, flushed to the query's global histogram;  k_nk_pick finds the bin that holds the need-th key.
@@ -38,7 +39,6 @@ namespace {
 constexpr uint32_t kBins = 2048;        // one 11-bit digit
 constexpr uint32_t kDigit = 11;
 constexpr uint32_t kSortLds = 4096;     // pairs the LDS sort takes
-constexpr uint32_t kLpreTile = 16;      // positions per thread of the leaf scan
 
 struct NkQ {
     uint32_t anc, last;        // depth-first positions; anc = kNil: empty result
@@ -54,26 +54,6 @@ struct NkQ {
 };
 
 struct NkItem { uint32_t q, seg; };
-
-// lpre[i] = leaves at positions < i, lpre[n] = all.  One block; a thread scans kLpreTile positions.
-__global__ void __launch_bounds__(kBlock) k_nk_lpre(uint32_t n, const uint8_t *leaf, uint32_t *lpre) {
-    __shared__ int sh[kBlock / 64];
-    uint32_t carry = 0;
-    for (uint64_t t0 = 0; t0 < n; t0 += (uint64_t)kBlock * kLpreTile) {
-        const uint64_t i0 = t0 + (uint64_t)threadIdx.x * kLpreTile;
-        uint32_t f[kLpreTile];
-        int sum = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kLpreTile; j++) { f[j] = i0 + j < n ? (leaf[i0 + j] ? 1u : 0u) : 0u; sum += (int)f[j]; }
-        int tot;
-        const int incl = block_incl_scan(sum, sh, &tot);
-        uint32_t run = carry + (uint32_t)(incl - sum);
-#pragma unroll
-        for (uint32_t j = 0; j < kLpreTile; j++) { if (i0 + j < n) lpre[i0 + j] = run; run += f[j]; }
-        carry += (uint32_t)tot;
-    }
-    if (threadIdx.x == 0) lpre[n] = carry;
-}
 
 __global__ void k_nk_anchor(DfsView t, const uint32_t *lpre, const uint32_t *node, const uint32_t *k, uint32_t nq, NkQ *Q) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -322,10 +302,8 @@ int nk_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, c
     hipError_t err = hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking);
     if (err == hipSuccess) err = S->lpre.alloc((size_t)n + 1);
     if (err == hipSuccess) err = S->d2b.upload(dfs2bfs.data(), n, S->stream);
-    if (err == hipSuccess) {
-        k_nk_lpre<<<1, kBlock, 0, S->stream>>>(n, S->T->leaf.p, S->lpre.p);
-        err = hipGetLastError();
-    }
+    DBuf<uint32_t> seg;   // read until the synchronize below
+    if (err == hipSuccess) err = scan_flags(seg, n, S->T->leaf.p, S->lpre.p, S->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(S->stream);
     if (err != hipSuccess) { delete S; return set_error(UGP_ERR_HIP, std::string("nearest tables: ") + hipGetErrorString(err)); }
     nk_free(*out);

@@ -9,7 +9,7 @@
 //     the climb stops after the first level with m_j < L_j.  The reference's pruning never changes the list.
 //   within  (fixed_k = true, threshold k): the ring leaves at distance <= k, level by level; stops after the first L_j > k.
 // Tables made at attach, all on the device:
-//   lpre            prefix count of the leaf flags: the leaf ranks of a depth-first range;
+//   lpre            prefix count of the leaf flags (scan_flags, ugp_scan.hpp): the leaf ranks of a depth-first range;
 //   lcum + rc       cum of the leaves in depth-first order with a range minimum over it: minima of blocks of UGP_REL_BLOCK
 //                   leaves, prefix / suffix minima inside the blocks and a sparse table over the block minima;
 //   srank/sbfs/boff the leaf ranks ordered by (cum, rank), their breadth-first indices, the first slot of every cum value: the
@@ -20,7 +20,6 @@
 // order inside a ring range by ranking each element against the other slices).  No pass reads a ring leaf by leaf.
 // Samples run in chunks, and a chunk's lists leave the device in windows, so the workspace stays bounded.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
 #include <new>
@@ -29,6 +28,7 @@
 
 #include "ugp_dense.hpp"
 #include "ugp_relatives.hpp"
+#include "ugp_sort.hpp"
 
 namespace ugp {
 namespace {
@@ -183,7 +183,6 @@ __global__ void __launch_bounds__(kBlock) k_rel_within(RelView v, const uint32_t
 // off[i] = cnt[0] + ... + cnt[i - 1] in 64 bits, off[ns] = all.  One block; a thread scans kScanTile values.
 __global__ void __launch_bounds__(kBlock) k_rel_scan(const uint32_t *cnt, uint32_t ns, unsigned long long *off) {
     __shared__ unsigned long long sh[kBlock / 64];
-    const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     unsigned long long carry = 0;
     for (uint64_t t0 = 0; t0 < ns; t0 += (uint64_t)kBlock * kScanTile) {
         const uint64_t i0 = t0 + (uint64_t)threadIdx.x * kScanTile;
@@ -191,19 +190,8 @@ __global__ void __launch_bounds__(kBlock) k_rel_scan(const uint32_t *cnt, uint32
         unsigned long long sum = 0;
 #pragma unroll
         for (uint32_t j = 0; j < kScanTile; j++) { f[j] = i0 + j < ns ? cnt[i0 + j] : 0u; sum += f[j]; }
-        unsigned long long x = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long o = __shfl_up(x, (unsigned)d, 64);
-            if ((int)lane >= d) x += o;
-        }
-        if (lane == 63) sh[w] = x;
-        __syncthreads();
-        unsigned long long pre = 0, tot = 0;
-#pragma unroll
-        for (uint32_t q = 0; q < kBlock / 64; q++) { const unsigned long long t = sh[q]; if (q < w) pre += t; tot += t; }
-        __syncthreads();
-        unsigned long long run = carry + pre + x - sum;
+        unsigned long long tot;
+        unsigned long long run = carry + block_incl_scan(sum, sh, &tot) - sum;
 #pragma unroll
         for (uint32_t j = 0; j < kScanTile; j++) { if (i0 + j < ns) off[i0 + j] = run; run += f[j]; }
         carry += tot;
@@ -256,26 +244,6 @@ __global__ void __launch_bounds__(kBlock) k_rel_fill(RelView v, const uint32_t *
 
 // ---- the tables ---------------------------------------------------------------------------------------------------------
 
-// lpre[i] = leaves at positions < i, lpre[n] = all.  One block; a thread scans kScanTile positions.
-__global__ void __launch_bounds__(kBlock) k_rel_lpre(uint32_t n, const uint8_t *leaf, uint32_t *lpre) {
-    __shared__ int sh[kBlock / 64];
-    uint32_t carry = 0;
-    for (uint64_t t0 = 0; t0 < n; t0 += (uint64_t)kBlock * kScanTile) {
-        const uint64_t i0 = t0 + (uint64_t)threadIdx.x * kScanTile;
-        uint32_t f[kScanTile];
-        int sum = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kScanTile; j++) { f[j] = i0 + j < n ? (leaf[i0 + j] ? 1u : 0u) : 0u; sum += (int)f[j]; }
-        int tot;
-        const int incl = block_incl_scan(sum, sh, &tot);
-        uint32_t run = carry + (uint32_t)(incl - sum);
-#pragma unroll
-        for (uint32_t j = 0; j < kScanTile; j++) { if (i0 + j < n) lpre[i0 + j] = run; run += f[j]; }
-        carry += (uint32_t)tot;
-    }
-    if (threadIdx.x == 0) lpre[n] = carry;
-}
-
 // The leaves in depth-first order: their cum, their breadth-first index, and the identity for the sort.
 __global__ void k_rel_leaves(uint32_t n, const uint8_t *leaf, const uint32_t *lpre, const uint32_t *cum, const uint32_t *d2b, uint32_t *lcum,
                              uint32_t *lbfs, uint32_t *iota) {
@@ -324,9 +292,6 @@ __global__ void k_rel_rmq_level(uint32_t nb, uint32_t l, uint32_t *sp) {
     const uint32_t *below = sp + (size_t)(l - 1) * nb;
     sp[(size_t)l * nb + b] = min(below[b], below[b + half]);
 }
-
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + kBlock - 1) / kBlock); }
-inline unsigned bits_for(uint64_t v) { unsigned b = 1; while (b < 64 && (v >> b)) b++; return b; }   // v < 2^b
 
 struct RmqBufs {
     DBuf<uint32_t> pre, suf, sp;
@@ -378,12 +343,11 @@ static int rel_build(RelState *S, const std::vector<uint32_t> &dfs2bfs, const ui
     const uint32_t n = T.n;
     hipStream_t st = S->stream;
     S->maxcum = *std::max_element(T.h_cum.begin(), T.h_cum.end());
-    DBuf<uint32_t> d2b, lbfs, iota, skey, nrank;
+    DBuf<uint32_t> d2b, lbfs, iota, skey, nrank, seg;
     DBuf<unsigned char> tmp;
     UGP_HIP_TRY(S->lpre.alloc((size_t)n + 1));
     UGP_HIP_TRY(d2b.upload(dfs2bfs.data(), n, st));
-    k_rel_lpre<<<1, kBlock, 0, st>>>(n, T.leaf.p, S->lpre.p);
-    UGP_HIP_TRY(hipGetLastError());
+    UGP_HIP_TRY(scan_flags(seg, n, T.leaf.p, S->lpre.p, st));
     UGP_HIP_TRY(hipMemcpyAsync(&S->nl, S->lpre.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     UGP_HIP_TRY(hipStreamSynchronize(st));
     const uint32_t nl = S->nl;   // at least one: the last position of a depth-first order is a leaf
@@ -392,11 +356,7 @@ static int rel_build(RelState *S, const std::vector<uint32_t> &dfs2bfs, const ui
     k_rel_leaves<<<blocks_for(n), kBlock, 0, st>>>(n, T.leaf.p, S->lpre.p, T.cum.p, d2b.p, S->lcum.p, lbfs.p, iota.p);
     UGP_HIP_TRY(hipGetLastError());
     // a radix sort is stable: equal cum values keep their depth-first order
-    size_t bytes = 0;
-    const unsigned bits = bits_for(S->maxcum);
-    UGP_HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes, S->lcum.p, skey.p, iota.p, S->srank.p, (size_t)nl, 0u, bits, st));
-    UGP_HIP_TRY(tmp.alloc(bytes));
-    UGP_HIP_TRY(rocprim::radix_sort_pairs(tmp.p, bytes, S->lcum.p, skey.p, iota.p, S->srank.p, (size_t)nl, 0u, bits, st));
+    UGP_HIP_TRY(sort_pairs(tmp, S->lcum.p, skey.p, iota.p, S->srank.p, nl, bits_for(S->maxcum), st));
     k_rel_boff<<<blocks_for((uint64_t)S->maxcum + 2), kBlock, 0, st>>>(skey.p, nl, S->maxcum + 2, S->boff.p);
     if (name_rank) {
         UGP_HIP_TRY(nrank.upload(name_rank, n, st));

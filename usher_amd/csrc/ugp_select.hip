@@ -102,8 +102,6 @@ __global__ void __launch_bounds__(kBlock) k_sel_climb(DfsView t, const uint32_t 
     out[2] = lbefore[t.dend[v]];
 }
 
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
-
 }  // namespace
 
 struct SelState {

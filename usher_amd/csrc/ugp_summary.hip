@@ -7,9 +7,9 @@
 // LIST.  The entries of the depth-first tables already follow their nodes' depth-first order, so one stable radix
 // sort by key gives that order.  A run of the list is one key; within a run the nodes ascend, so "does the key occur inside the
 // subtree of n" is a binary search for n's depth-first range [n + 1, dend[n]) inside the run.
-//   k_sm_keys / (rocprim radix sort) / k_sm_heads / k_sm_segsum + k_sm_scan / k_sm_runs     the list, its run heads, run numbers and
+//   k_sm_keys / (rocprim radix sort) / k_sm_heads / (scan_flags, ugp_scan.hpp) / k_sm_runs     the list, its run heads, run numbers and
 //                                  run starts; the list position of every entry;
-//   k_sm_nodes                     per node the leaves strictly below it (leaf prefix counts), per parent its non-leaf children, and
+//   k_sm_nodes                     per node the leaves strictly below it (leaf prefix counts: scan_flags), per parent its non-leaf children, and
 //                                  the sort key (parent, leaf count) of every non-leaf child with more than 5 leaves;
 //   k_sm_bigseg                    after that sort: where each parent's sorted leaf counts begin, and each child's place in them;
 //   k_sm_candkey                   the candidates -- the entries of non-leaf, non-root nodes -- keyed by their parent, for a stable
@@ -22,7 +22,6 @@
 //   k_sm_gather / k_sm_clade_incl / k_sm_clade_leaf     the clade tables: per (column, leaf) the predecessor among the column's
 //                                  annotated nodes in depth-first order, then the climb over the enclosing annotated nodes.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
 #include <new>
@@ -30,6 +29,7 @@
 #include <vector>
 
 #include "ugp_dense.hpp"
+#include "ugp_sort.hpp"
 #include "ugp_summary.hpp"
 
 namespace ugp {
@@ -59,36 +59,6 @@ __global__ void k_sm_heads(DfsView t, uint32_t m, const uint64_t *skey, const ui
     head[x] = (x == 0 || skey[x] != skey[x - 1]) ? 1 : 0;
     onode[x] = t.mnode[e];
     inv[e] = x;
-}
-
-// One block per segment: the flags set in it.
-__global__ void __launch_bounds__(kBlock) k_sm_segsum(uint32_t n, const uint8_t *flag, uint32_t *seg) {
-    __shared__ int sh[kBlock / 64];
-    const uint32_t lo = blockIdx.x * kSeg, hi = min(n, lo + kSeg);
-    int acc = 0;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += kBlock) acc += flag[i] ? 1 : 0;
-    int tot;
-    (void)block_incl_scan(acc, sh, &tot);
-    if (threadIdx.x == 0) seg[blockIdx.x] = (uint32_t)tot;
-}
-
-// One block per segment: out[i] = flags set before i (the carry: the segments before), out[n] = all of them.
-__global__ void __launch_bounds__(kBlock) k_sm_scan(uint32_t n, const uint8_t *flag, const uint32_t *seg, uint32_t *out) {
-    __shared__ int sh[kBlock / 64];
-    const uint32_t g = blockIdx.x, lo = g * kSeg, hi = min(n, lo + kSeg);
-    int acc = 0;
-    for (uint32_t k = threadIdx.x; k < g; k += kBlock) acc += (int)seg[k];
-    int tot;
-    (void)block_incl_scan(acc, sh, &tot);
-    uint32_t carry = (uint32_t)tot;
-    for (uint32_t t0 = lo; t0 < hi; t0 += kBlock) {
-        const uint32_t i = t0 + threadIdx.x;
-        const int f = (i < hi && flag[i]) ? 1 : 0;
-        const int incl = block_incl_scan(f, sh, &tot);
-        if (i < hi) out[i] = carry + (uint32_t)(incl - f);
-        carry += (uint32_t)tot;
-    }
-    if (hi == n && threadIdx.x == 0) out[n] = carry;
 }
 
 // hidx = heads before x.  rid[x] = the run of x; rstart[r] = its first position, rstart[runs] = m.
@@ -234,20 +204,6 @@ __global__ void k_sm_clade_leaf(DfsView t, uint32_t ncols, uint32_t nleaves, con
     if (cur != kNil) atomicAdd(&excl[aorig[cur]], 1u);
 }
 
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
-inline uint32_t segs_for(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + kSeg - 1) / kSeg); }
-inline unsigned bits_for(uint64_t v) { unsigned b = 1; while (b < 64 && (v >> b)) b++; return b; }   // v < 2^b
-
-template <typename K>
-hipError_t sort_pairs(DBuf<unsigned char> &tmp, const K *kin, K *kout, const uint32_t *vin, uint32_t *vout, size_t n, unsigned bits,
-                      hipStream_t st) {
-    size_t bytes = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, n, 0u, bits, st);
-    if (e == hipSuccess) e = tmp.alloc(bytes);
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp.p, bytes, kin, kout, vin, vout, n, 0u, bits, st);
-    return e;
-}
-
 }  // namespace
 
 struct SmState {
@@ -276,16 +232,6 @@ void sm_free(SmState *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     delete s;
-}
-
-// out[i] = flags set before i, out[n] = all (n + 1 values).
-static hipError_t scan_flags(SmState *S, uint32_t n, const uint8_t *flag, uint32_t *out) {
-    const uint32_t nseg = segs_for(n);
-    hipError_t e = S->seg.alloc(nseg);
-    if (e != hipSuccess) return e;
-    k_sm_segsum<<<nseg, kBlock, 0, S->stream>>>(n, flag, S->seg.p);
-    k_sm_scan<<<nseg, kBlock, 0, S->stream>>>(n, flag, S->seg.p, out);
-    return hipGetLastError();
 }
 
 static int sm_build(SmState *S, const ugp_tree_desc *tree) {
@@ -324,7 +270,7 @@ static int sm_build(SmState *S, const ugp_tree_desc *tree) {
         UGP_HIP_TRY(sort_pairs(S->tmp, ukey.p, S->skey.p, uval.p, sent.p, M, kKeyBits, st));
         k_sm_heads<<<blocks_for(M), kBlock, 0, st>>>(t, M, S->skey.p, sent.p, head.p, S->onode.p, S->inv.p);
         UGP_HIP_TRY(hipGetLastError());
-        UGP_HIP_TRY(scan_flags(S, M, head.p, hidx.p));
+        UGP_HIP_TRY(scan_flags(S->seg, M, head.p, hidx.p, st));
         k_sm_runs<<<blocks_for((uint64_t)M + 1), kBlock, 0, st>>>(M, head.p, hidx.p, S->rid.p, S->rstart.p);
         UGP_HIP_TRY(hipGetLastError());
         UGP_HIP_TRY(hipMemcpyAsync(&runs, hidx.p + M, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -344,7 +290,7 @@ static int sm_build(SmState *S, const ugp_tree_desc *tree) {
     UGP_HIP_TRY(hipMemsetAsync(S->bigcnt.p, 0, (size_t)N * sizeof(uint32_t), st));
     UGP_HIP_TRY(hipMemsetAsync(S->bstart.p, 0, (size_t)N * sizeof(uint32_t), st));
     UGP_HIP_TRY(hipMemsetAsync(S->brank.p, 0, (size_t)N * sizeof(uint32_t), st));
-    UGP_HIP_TRY(scan_flags(S, N, t.leaf, lpre.p));
+    UGP_HIP_TRY(scan_flags(S->seg, N, t.leaf, lpre.p, st));
     k_sm_nodes<<<blocks_for(N), kBlock, 0, st>>>(t, lpre.p, S->lbits, S->lcnt.p, S->ccount.p, S->bigcnt.p, bkey.p, bval.p);
     UGP_HIP_TRY(hipGetLastError());
     UGP_HIP_TRY(sort_pairs(S->tmp, bkey.p, S->bskey.p, bval.p, bsval.p, N, 2 * S->lbits + 1, st));
@@ -417,7 +363,7 @@ int sm_roho(SmState *S, ugp_sm_roho *out, uint64_t cap, uint64_t *n_out, uint64_
         const uint32_t cnt = (uint32_t)std::min<uint64_t>(win, S->ncand - i0);
         k_sm_roho<<<blocks_for(cnt), kBlock, 0, st>>>(t, v, (uint32_t)i0, cnt, S->flag.p, S->rec.p);
         UGP_HIP_TRY(hipGetLastError());
-        UGP_HIP_TRY(scan_flags(S, cnt, S->flag.p, S->off.p));
+        UGP_HIP_TRY(scan_flags(S->seg, cnt, S->flag.p, S->off.p, st));
         k_sm_emit<<<blocks_for(cnt), kBlock, 0, st>>>(cnt, S->flag.p, S->off.p, S->rec.p, S->d2b.p, base, room, S->rout.p);
         UGP_HIP_TRY(hipGetLastError());
         uint32_t got = 0;

@@ -15,7 +15,7 @@
 //                                  item at the lowest of them owns the record: a mutated slot takes the state before from the owner
 //                                  above its entry, an unmutated one from a binary search among the position's owners for the last
 //                                  one in front of the node and the climb over the owners above until one contains the node;
-//   k_tr_segsum / k_tr_scan        the records in front of every item of the window;
+//   (scan_flags, ugp_scan.hpp)     the records in front of every item of the window;
 //   k_tr_emit                      the records of the window, compacted in order behind those of the windows before.
 #include <hip/hip_runtime.h>
 
@@ -118,36 +118,6 @@ __global__ void __launch_bounds__(kBlock) k_tr_items(DfsView t, TrView s, uint32
     }
 }
 
-// One block per segment: the flags set in it.
-__global__ void __launch_bounds__(kBlock) k_tr_segsum(uint32_t n, const uint8_t *flag, uint32_t *seg) {
-    __shared__ int sh[kBlock / 64];
-    const uint32_t lo = blockIdx.x * kSeg, hi = min(n, lo + kSeg);
-    int acc = 0;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += kBlock) acc += flag[i] ? 1 : 0;
-    int tot;
-    (void)block_incl_scan(acc, sh, &tot);
-    if (threadIdx.x == 0) seg[blockIdx.x] = (uint32_t)tot;
-}
-
-// One block per segment: out[i] = flags set before i (the carry: the segments before), out[n] = all of them.
-__global__ void __launch_bounds__(kBlock) k_tr_scan(uint32_t n, const uint8_t *flag, const uint32_t *seg, uint32_t *out) {
-    __shared__ int sh[kBlock / 64];
-    const uint32_t g = blockIdx.x, lo = g * kSeg, hi = min(n, lo + kSeg);
-    int acc = 0;
-    for (uint32_t k = threadIdx.x; k < g; k += kBlock) acc += (int)seg[k];
-    int tot;
-    (void)block_incl_scan(acc, sh, &tot);
-    uint32_t carry = (uint32_t)tot;
-    for (uint32_t t0 = lo; t0 < hi; t0 += kBlock) {
-        const uint32_t i = t0 + threadIdx.x;
-        const int f = (i < hi && flag[i]) ? 1 : 0;
-        const int incl = block_incl_scan(f, sh, &tot);
-        if (i < hi) out[i] = carry + (uint32_t)(incl - f);
-        carry += (uint32_t)tot;
-    }
-    if (hi == n && threadIdx.x == 0) out[n] = carry;
-}
-
 // The flagged records of a window go behind the `base` records before them, the node as a breadth-first index, while below cap.
 __global__ void k_tr_emit(uint32_t cnt, const uint8_t *flag, const uint32_t *off, const ugp_tr_record *rec, const uint32_t *d2b, uint64_t base,
                           uint64_t cap, ugp_tr_record *out) {
@@ -161,9 +131,6 @@ __global__ void k_tr_emit(uint32_t cnt, const uint8_t *flag, const uint32_t *off
 #pragma unroll
     for (int k = 1; k < (int)(sizeof(ugp_tr_record) / sizeof(uint32_t)); k++) dst[k] = src[k];
 }
-
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
-inline uint32_t segs_for(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + kSeg - 1) / kSeg); }
 
 }  // namespace
 
@@ -329,10 +296,9 @@ static int tr_windows(TrState *S, uint64_t win, uint64_t room, bool count, uint6
     const TrView v = S->view();
     uint64_t base = 0;
     for (uint64_t i0 = 0; i0 < S->nitems; i0 += win) {
-        const uint32_t cnt = (uint32_t)std::min<uint64_t>(win, S->nitems - i0), nseg = segs_for(cnt);
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(win, S->nitems - i0);
         k_tr_items<<<blocks_for(cnt), kBlock, 0, st>>>(t, v, (uint32_t)i0, cnt, S->flag.p, S->rec.p, S->counters.p);
-        k_tr_segsum<<<nseg, kBlock, 0, st>>>(cnt, S->flag.p, S->seg.p);
-        k_tr_scan<<<nseg, kBlock, 0, st>>>(cnt, S->flag.p, S->seg.p, S->off.p);
+        UGP_HIP_TRY(scan_flags(S->seg, cnt, S->flag.p, S->off.p, st));
         k_tr_emit<<<blocks_for(cnt), kBlock, 0, st>>>(cnt, S->flag.p, S->off.p, S->rec.p, S->d2b.p, base, room, S->rout.p);
         UGP_HIP_TRY(hipGetLastError());
         if (!count) continue;
