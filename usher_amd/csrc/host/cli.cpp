@@ -1,6 +1,7 @@
 // cli.cpp -- command line of the usher-compatible front end: the 22 flags of the
 // reference's src/usher.cpp:47-86 (+ --version / --help), tree / MAT / VCF
 // loading (usher.cpp:132-173) and the call into the driver (usher.cpp:175-178).
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -252,21 +253,19 @@ extern "C" int uh_pb_to_arrays(const char *pb, uint64_t *counts, int64_t *parent
     std::string err;
     if (!uh::load_mat(pb, T, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
     if (!T.condensed_nodes.empty()) T.uncondense_leaves();   // (a MAT is saved with identical sequences condensed; the search runs on the full tree)
-    const std::vector<uh::Node *> bfs = T.bfs();
-    uint64_t m = 0;
-    for (const uh::Node *n : bfs) m += n->mutations.size();
-    counts[0] = bfs.size(); counts[1] = m;
+    const uh::TreeArrays A(T);
+    const uint64_t N = A.bfs.size(), M = A.mut_off[N];
+    counts[0] = N; counts[1] = M;
     if (!parent) return 0;
-    for (size_t j = 0; j < bfs.size(); j++) { bfs[j]->flat_index = (uint32_t)j; }
-    uint64_t k = 0;
-    for (size_t j = 0; j < bfs.size(); j++) {
-        const uh::Node *n = bfs[j];
-        parent[j] = n->parent ? (int64_t)n->parent->flat_index : -1;
-        mut_off[j] = (int64_t)k;
-        for (const uh::Mutation &mu : n->mutations) { pos[k] = mu.position; ref[k] = mu.ref_nuc; par[k] = mu.par_nuc; nuc[k] = mu.mut_nuc; k++; }
-        if (names24) { snprintf(names24 + j * 24, 24, "%s", n->id.c_str()); }
+    for (uint64_t j = 0; j < N; j++) {
+        parent[j] = A.parent[j] == UINT32_MAX ? -1 : (int64_t)A.parent[j];
+        if (names24) { snprintf(names24 + j * 24, 24, "%s", A.bfs[j]->id.c_str()); }
     }
-    mut_off[bfs.size()] = (int64_t)k;
+    std::copy(A.mut_off.begin(), A.mut_off.end(), mut_off);
+    std::copy(A.pos.begin(), A.pos.begin() + M, pos);
+    std::copy(A.ref.begin(), A.ref.begin() + M, ref);
+    std::copy(A.par.begin(), A.par.begin() + M, par);
+    std::copy(A.nuc.begin(), A.nuc.begin() + M, nuc);
     return 0;
 }
 

@@ -1615,6 +1615,44 @@ bool read_vcf_build(Tree &T, const std::string &path, std::vector<MissingSample>
     return true;
 }
 
+// ------------------------------------------------------- the tree for the device
+TreeArrays::TreeArrays(const Tree &T, unsigned keep) : bfs(T.bfs()) {
+    const size_t N = bfs.size();
+    uint64_t M = 0;
+    for (size_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; M += bfs[j]->mutations.size(); }
+    parent.resize(N);
+    mut_off.assign(N + 1, 0);
+    no_off.assign(N + 1, 0);
+    pos.assign(std::max<uint64_t>(M, 1), 0); ref.assign(pos.size(), 0); par.assign(pos.size(), 0); nuc.assign(pos.size(), 0);
+    if (keep & kEntries) ent.resize(M);
+    uint64_t k = 0;
+    for (size_t j = 0; j < N; j++) {
+        parent[j] = bfs[j]->parent ? bfs[j]->parent->flat_index : UINT32_MAX;
+        for (const Mutation &m : bfs[j]->mutations) {
+            pos[k] = m.position; ref[k] = (uint8_t)m.ref_nuc; par[k] = (uint8_t)m.par_nuc; nuc[k] = (uint8_t)m.mut_nuc;
+            if (keep & kEntries) ent[k] = &m;
+            k++;
+        }
+        mut_off[j + 1] = k;
+    }
+    if (!(keep & kDepthFirst)) return;
+    dfs = T.dfs();
+    dpos.resize(N);
+    dend.resize(N);
+    for (size_t i = 0; i < N; i++) dpos[dfs[i]->flat_index] = (uint32_t)i;
+    std::vector<uint32_t> sz(N, 1);
+    for (size_t i = N; i-- > 1;) sz[dpos[dfs[i]->parent->flat_index]] += sz[i];
+    for (size_t i = 0; i < N; i++) dend[dfs[i]->flat_index] = (uint32_t)i + sz[i];
+}
+
+std::vector<uint32_t> TreeArrays::name_rank() const {
+    std::vector<uint32_t> order(bfs.size()), rank(bfs.size());
+    for (size_t j = 0; j < order.size(); j++) order[j] = (uint32_t)j;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return bfs[a]->id < bfs[b]->id; });
+    for (size_t r = 0; r < order.size(); r++) rank[order[r]] = (uint32_t)r;
+    return rank;
+}
+
 // ------------------------------------------------------- bench / test utilities
 // A tree given as breadth-first arrays (the layout of ugp_tree_desc) written as parsimony.proto, and a query batch in CSR form
 // written as a VCF: the inputs of an end-to-end run of the front end on the synthetic workload (bench.py, tools/bench_addmode.py).

@@ -8,6 +8,8 @@
 #include <unordered_set>
 #include <vector>
 
+#include "usher_amd.h"
+
 namespace uh {
 
 // one-hot allele codes A=1 C=2 G=4 T=8, IUPAC = unions, N = 15
@@ -125,6 +127,30 @@ bool copy_tree(const Tree &src, Tree &dst, std::string &err);
 // get_subtree(), :1575-1681: the subtree induced by `samples` (their leaves, every pairwise most recent common
 // ancestor, mutations merged along the collapsed paths); internal node names are kept.
 bool get_subtree(const Tree &src, const std::vector<std::string> &samples, Tree &dst, std::string &err);
+
+// A tree as the breadth-first arrays of the C ABI: the one way a front end hands its tree to the library.  Building one numbers
+// the tree's nodes (Node::flat_index = breadth-first index, flat_epoch = 0).  The arrays hold the tree as it was then: entries
+// the tree gains or loses later are not followed, and `ent` points into the nodes' own vectors.
+struct TreeArrays {
+    enum : unsigned { kEntries = 1, kDepthFirst = 2 };   // what to keep beside the arrays
+    std::vector<Node *> bfs;
+    std::vector<uint32_t> parent;             // [N]      root = UINT32_MAX
+    std::vector<uint64_t> mut_off, no_off;    // [N + 1]  CSR offsets of the entries; no_off: all zero (bare())
+    std::vector<int32_t> pos;                 // the entries, mut_off[N] of them; the four arrays hold one unused entry when
+    std::vector<uint8_t> ref, par, nuc;       //          the tree has none, so that data() is never null
+    std::vector<const Mutation *> ent;        // kEntries: each entry's Mutation in the tree
+    std::vector<Node *> dfs;                  // kDepthFirst: the depth-first order, and by breadth-first index the position
+    std::vector<uint32_t> dpos, dend;         //          there and the end of the subtree's depth-first range
+    TreeArrays() = default;
+    explicit TreeArrays(const Tree &T, unsigned keep = 0);
+    TreeArrays(TreeArrays &&) = default;
+    TreeArrays &operator=(TreeArrays &&) = default;   // (no copies: nobody needs a second 10M-node set of arrays)
+    // Views computed at the call, so that none outlives a move.  bare(): the same topology with no entry on any node.
+    ugp_tree_desc desc() const { return {bfs.size(), parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()}; }
+    ugp_tree_desc bare() const { return {bfs.size(), parent.data(), no_off.data(), pos.data(), ref.data(), par.data(), nuc.data()}; }
+    // Each node's rank by id under std::string::operator<.  (Node ids are unique, so the order needs no tie-break.)
+    std::vector<uint32_t> name_rank() const;
+};
 
 // newick --------------------------------------------------------------------
 bool tree_from_newick(const std::string &nwk, Tree &out, std::string &err);   // :415-508

@@ -72,6 +72,22 @@ void usage(FILE *f) {
             "       matutils-amd relatives --help | matutils-amd select --help | matutils-amd mask --help | matutils-amd haplotypes --help\n");
 }
 
+[[noreturn]] void lib_fail(const char *what) {
+    fprintf(stderr, "ERROR: %s: %s\n", what, ugp_last_error());
+    exit(1);
+}
+
+// The library's handle of one tree (the tree itself comes as uh::TreeArrays), destroyed with its owner.
+struct Mat {
+    ugp_mat *h = nullptr;
+    Mat() = default;
+    Mat(const Mat &) = delete;
+    Mat &operator=(const Mat &) = delete;
+    ~Mat() { if (h) ugp_mat_destroy(h); }
+    void create(const ugp_tree_desc &desc, int device) { if (ugp_mat_create(&desc, device, &h) != UGP_OK) lib_fail("ugp_mat_create"); }
+    operator ugp_mat *() const { return h; }
+};
+
 int uncertainty(int argc, char **argv) {
     std::string mat, samples, fepps, flocs;
     int device = 0;
@@ -123,28 +139,15 @@ int uncertainty(int argc, char **argv) {
     }
     fprintf(stderr, "Processing %ld samples\n", (long)chosen.size());
 
-    // the tree as breadth-first arrays (the C ABI's numbering)
-    const std::vector<uh::Node *> bfs = T.bfs();
+    const uh::TreeArrays A(T);
+    const std::vector<uh::Node *> &bfs = A.bfs;
     const uint64_t N = bfs.size();
-    for (uint64_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
-    std::vector<uint32_t> parent(N);
-    std::vector<uint64_t> mut_off(N + 1, 0);
-    std::vector<int32_t> pos;
-    std::vector<uint8_t> ref, par, nuc;
-    for (uint64_t j = 0; j < N; j++) {
-        const uh::Node *n = bfs[j];
-        parent[j] = n->parent ? n->parent->flat_index : UINT32_MAX;
-        for (const auto &m : n->mutations) {
-            pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
-        }
-        mut_off[j + 1] = pos.size();
-    }
-    const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+    const ugp_tree_desc desc = A.desc();
     std::vector<uint32_t> nodes(chosen.size());
     for (size_t i = 0; i < chosen.size(); i++) nodes[i] = chosen[i]->flat_index;
 
-    ugp_mat *h = nullptr;
-    int rc = ugp_mat_create(&desc, device, &h);
+    Mat h;   // (created here and not by create(): this subcommand reports a failure without the call's name)
+    int rc = ugp_mat_create(&desc, device, &h.h);
     if (rc == UGP_OK) rc = ugp_uncertainty_attach(h, &desc);
     std::vector<uint32_t> dfs2bfs(N);
     if (rc == UGP_OK) rc = ugp_node_order(h, UGP_ORDER_DFS, dfs2bfs.data());
@@ -171,10 +174,8 @@ int uncertainty(int argc, char **argv) {
     }
     if (rc != UGP_OK) {
         fprintf(stderr, "ERROR: %s\n", ugp_last_error());
-        if (h) ugp_mat_destroy(h);
         return 1;
     }
-    ugp_mat_destroy(h);
 
     std::string eo = "sample\tequally_parsimonious_placements\tneighborhood_size\n", lo = "placement\tsample\n";
     for (size_t i = 0; i < n; i++) {
@@ -440,11 +441,6 @@ struct CladeAssignment {   // Clade_Assignments, :559-583
     }
 };
 
-[[noreturn]] void lib_fail(const char *what) {
-    fprintf(stderr, "ERROR: %s: %s\n", what, ugp_last_error());
-    exit(1);
-}
-
 // assignLineages(T, clade_names, clade_mutations, clade_paths, ...), :483-806; the searches and counts on the device
 void lineages(uh::Tree &T, const std::string &fnames, const std::string &fmuts, const std::string &fpaths, float min_freq, float mask_freq,
               float set_overlap, float clip, bool clear, const std::string &fmutsout, const std::string &fdetails, int device) {
@@ -464,23 +460,11 @@ void lineages(uh::Tree &T, const std::string &fnames, const std::string &fmuts, 
     fprintf(stderr, "Initializing annotations.\n");
     init_annotations(dfs, clear);
     const size_t na = T.num_annotations();
-    // the tree as breadth-first arrays (the C ABI's numbering); dfs_idx = position in `dfs`
-    const std::vector<uh::Node *> bfs = T.bfs();
-    std::unordered_map<const uh::Node *, uint32_t> bfs_idx, dfs_idx;
-    for (size_t j = 0; j < N; j++) { bfs_idx[bfs[j]] = (uint32_t)j; dfs_idx[dfs[j]] = (uint32_t)j; }
-    std::vector<uint32_t> parent(N);
-    std::vector<uint64_t> mut_off(N + 1, 0);
-    std::vector<int32_t> pos;
-    std::vector<uint8_t> ref, par, nuc;
-    std::vector<const uh::Mutation *> ent;
-    for (size_t j = 0; j < N; j++) {
-        parent[j] = bfs[j]->parent ? bfs_idx[bfs[j]->parent] : UINT32_MAX;
-        for (const auto &m : bfs[j]->mutations) {
-            pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
-            ent.push_back(&m);
-        }
-        mut_off[j + 1] = pos.size();
-    }
+    // flat_index = the breadth-first index (nothing below renumbers T's nodes; the copy U has its own); dfs_idx = position in `dfs`
+    const uh::TreeArrays A(T, uh::TreeArrays::kEntries);
+    const std::vector<const uh::Mutation *> &ent = A.ent;
+    std::unordered_map<const uh::Node *, uint32_t> dfs_idx;
+    for (size_t j = 0; j < N; j++) dfs_idx[dfs[j]] = (uint32_t)j;
     // leaves below each node (get_num_leaves), by depth-first position
     std::vector<size_t> leaves(N, 0);
     for (size_t k = N; k-- > 0;) {
@@ -494,11 +478,11 @@ void lineages(uh::Tree &T, const std::string &fnames, const std::string &fmuts, 
     std::map<std::string, std::vector<uh::Node *>> clade_map;   // exemplars, as nodes of T (looked up by the copy's names)
     if (!fmuts.empty()) parse_clade_mutations(fmuts, clade_muts, done);
 
-    ugp_mat *h = nullptr;
-    const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+    Mat h;
     auto device_up = [&]() {
         if (h) return;
-        if (ugp_mat_create(&desc, device, &h) != UGP_OK) lib_fail("ugp_mat_create");
+        const ugp_tree_desc desc = A.desc();
+        h.create(desc, device);
         if (ugp_annotate_attach(h, &desc) != UGP_OK) lib_fail("ugp_annotate_attach");
     };
 
@@ -536,7 +520,7 @@ void lineages(uh::Tree &T, const std::string &fnames, const std::string &fmuts, 
         std::vector<uint64_t> coff(1, 0);
         std::vector<uint32_t> xs;
         std::vector<uint32_t> dfs2bfs(N);
-        for (size_t k = 0; k < N; k++) dfs2bfs[k] = bfs_idx[dfs[k]];
+        for (size_t k = 0; k < N; k++) dfs2bfs[k] = dfs[k]->flat_index;
         for (const auto &kv : clade_copy_dfs) {
             for (uint32_t d : kv.second) xs.push_back(dfs2bfs[d]);
             coff.push_back(xs.size());
@@ -677,7 +661,7 @@ void lineages(uh::Tree &T, const std::string &fnames, const std::string &fmuts, 
         auto cm = clade_map.find(order[i]);
         if (cm == clade_map.end()) continue;
         cm_index[i] = coffT.size() - 1;
-        for (uh::Node *n : cm->second) xsT.push_back(bfs_idx[n]);
+        for (uh::Node *n : cm->second) xsT.push_back(n->flat_index);
         coffT.push_back(xsT.size());
     }
     std::map<std::pair<size_t, uint32_t>, uint32_t> num_desc;
@@ -685,7 +669,7 @@ void lineages(uh::Tree &T, const std::string &fnames, const std::string &fmuts, 
         for (size_t i = 0; i < nc; i++) {
             if (cm_index[i] == SIZE_MAX) continue;
             for (uint32_t j : ties[i])
-                for (uh::Node *a = dfs[j]; a; a = a->parent) { pc.push_back((uint32_t)cm_index[i]); pn.push_back(bfs_idx[a]); }
+                for (uh::Node *a = dfs[j]; a; a = a->parent) { pc.push_back((uint32_t)cm_index[i]); pn.push_back(a->flat_index); }
         }
         std::vector<uint32_t> out(pc.size());
         if (!pc.empty()) {
@@ -695,7 +679,6 @@ void lineages(uh::Tree &T, const std::string &fnames, const std::string &fmuts, 
         }
         for (size_t k = 0; k < pc.size(); k++) num_desc[{pc[k], pn[k]}] = out[k];
     }
-    if (h) ugp_mat_destroy(h);
 
     std::vector<CladeAssignment> cas;
     for (size_t i = 0; i < nc; i++) {
@@ -723,7 +706,7 @@ void lineages(uh::Tree &T, const std::string &fnames, const std::string &fmuts, 
             float best_freq = -1.0f;
             for (uint32_t j : ties[i]) {   // already ascending: the stable_sort of :663
                 for (uh::Node *a = dfs[j]; a; a = a->parent) {
-                    const size_t nd = num_desc[{cm_index[i], bfs_idx[a]}];
+                    const size_t nd = num_desc[{cm_index[i], a->flat_index}];
                     const float freq = static_cast<float>(nd) / leaves[dfs_idx[a]];
                     const float overlap = static_cast<float>(nd) / csize;
                     if (freq >= best_freq && overlap >= set_overlap) {
@@ -737,7 +720,7 @@ void lineages(uh::Tree &T, const std::string &fnames, const std::string &fmuts, 
             if (cas.back().best_node_frequencies.empty()) {
                 fprintf(stderr, "WARNING: %s: no placement node or ancestor passed thresholds.\n", clade.c_str());
                 for (uint32_t j : ties[i]) {
-                    const size_t nd = num_desc[{cm_index[i], bfs_idx[dfs[j]]}];
+                    const size_t nd = num_desc[{cm_index[i], dfs[j]->flat_index}];
                     fprintf(stderr, "fail node\t%s\t%s\t%f\t%f\n", clade.c_str(), dfs[j]->id.c_str(), static_cast<float>(nd) / leaves[j],
                             static_cast<float>(nd) / csize);
                 }
@@ -1001,28 +984,15 @@ struct NearestSearch {
     int device;
     bool reference_ties;
     std::vector<uh::Node *> bfs;
-    ugp_mat *h = nullptr;
+    Mat h;
     NearestSearch(uh::Tree &t, int dev, bool ties) : T(t), device(dev), reference_ties(ties) {}
-    ~NearestSearch() { if (h) ugp_mat_destroy(h); }
     void up() {
         if (h) return;
-        bfs = T.bfs();
-        const uint64_t N = bfs.size();
-        for (uint64_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
-        std::vector<uint32_t> parent(N);
-        std::vector<uint64_t> mut_off(N + 1, 0);
-        std::vector<int32_t> pos;
-        std::vector<uint8_t> ref, par, nuc;
-        for (uint64_t j = 0; j < N; j++) {
-            parent[j] = bfs[j]->parent ? bfs[j]->parent->flat_index : UINT32_MAX;
-            for (const auto &m : bfs[j]->mutations) {
-                pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
-            }
-            mut_off[j + 1] = pos.size();
-        }
-        const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
-        if (ugp_mat_create(&desc, device, &h) != UGP_OK) lib_fail("ugp_mat_create");
+        uh::TreeArrays A(T);
+        const ugp_tree_desc desc = A.desc();
+        h.create(desc, device);
         if (ugp_nearest_attach(h, &desc) != UGP_OK) lib_fail("ugp_nearest_attach");
+        bfs = std::move(A.bfs);   // the library has its copy of the arrays: only the nodes are kept
     }
     // The literal sort of one query between the device's anc and last_anc: Tree::get_leaves' order into std::sort.
     std::vector<std::string> literal(uh::Node *anc, uh::Node *last, size_t k) const {
@@ -1222,26 +1192,12 @@ int make_vcf(uh::Tree &T, const std::string &path, bool no_genotypes, const std:
         n_sites = hg.write(vcf, chrom, n_cols, !no_genotypes);
     } else {
         // the tree as arrays: the handle takes the bare topology, the genotype tables the mutations as they are stored
-        const std::vector<uh::Node *> bfs = T.bfs();
-        const uint64_t N = bfs.size();
-        for (uint64_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
-        std::vector<uint32_t> parent(N), sel;
-        std::vector<uint64_t> mut_off(N + 1, 0), no_off(N + 1, 0);
-        std::vector<int32_t> pos;
-        std::vector<uint8_t> ref, par, nuc;
-        for (uint64_t j = 0; j < N; j++) {
-            parent[j] = bfs[j]->parent ? bfs[j]->parent->flat_index : UINT32_MAX;
-            for (const auto &m : bfs[j]->mutations) {
-                pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
-            }
-            mut_off[j + 1] = pos.size();
-            if (use.count(bfs[j]->id)) sel.push_back((uint32_t)j);
-        }
-        if (pos.empty()) { pos.push_back(0); ref.push_back(0); par.push_back(0); nuc.push_back(0); }   // (never read: no null arrays)
-        const ugp_tree_desc bare{N, parent.data(), no_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
-        const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
-        ugp_mat *h = nullptr;
-        if (ugp_mat_create(&bare, device, &h) != UGP_OK) lib_fail("ugp_mat_create");
+        const uh::TreeArrays A(T);
+        std::vector<uint32_t> sel;
+        for (size_t j = 0; j < A.bfs.size(); j++) if (use.count(A.bfs[j]->id)) sel.push_back((uint32_t)j);
+        const ugp_tree_desc desc = A.desc();
+        Mat h;
+        h.create(A.bare(), device);
         if (ugp_genotypes_attach(h, &desc) != UGP_OK) lib_fail("ugp_genotypes_attach");
         uint64_t ns = 0;
         if (ugp_genotype_select(h, sel.data(), sel.size(), &n_cols, &ns) != UGP_OK) lib_fail("ugp_genotype_select");
@@ -1259,7 +1215,6 @@ int make_vcf(uh::Tree &T, const std::string &path, bool no_genotypes, const std:
                 if (hipHostMalloc((void **)&b, std::min<uint64_t>(per, ns) * n_cols, hipHostMallocDefault) != hipSuccess) {
                     fprintf(stderr, "ERROR: hipHostMalloc failed\n");
                     for (auto &f : buf) if (f) (void)hipHostFree(f);
-                    ugp_mat_destroy(h);
                     return 1;
                 }
             // (the library's error text is per thread: the fetching thread brings it along)
@@ -1281,12 +1236,10 @@ int make_vcf(uh::Tree &T, const std::string &path, bool no_genotypes, const std:
             if (!failed.empty()) {
                 fprintf(stderr, "ERROR: %s\n", failed.c_str());
                 for (auto &b : buf) (void)hipHostFree(b);
-                ugp_mat_destroy(h);
                 return 1;
             }
             for (auto &b : buf) (void)hipHostFree(b);
         }
-        ugp_mat_destroy(h);
     }
     if (!vcf.close()) { fprintf(stderr, "ERROR: could not write %s\n", path.c_str()); return 1; }
     fprintf(stderr, "VCF of %zu sites x %u samples (%s): %.1f msec\n", n_sites, n_cols, on_host ? "host" : "device",
@@ -1325,36 +1278,18 @@ struct SelectOpts {
 struct SelectDevice {
     uh::Tree &T;
     int device;
-    ugp_mat *h = nullptr;
-    std::vector<uh::Node *> bfs;
-    std::vector<uint32_t> parent, leaf_bfs, rank_of;   // rank_of by BFS index, UINT32_MAX for an internal node
-    std::vector<uint64_t> mut_off;
-    std::vector<int32_t> pos;
-    std::vector<uint8_t> ref, par, nuc;
-    ugp_tree_desc desc{};
+    Mat h;
+    uh::TreeArrays A;   // kept: -e attaches the uncertainty tables later
+    std::vector<uint32_t> leaf_bfs, rank_of;   // rank_of by BFS index, UINT32_MAX for an internal node
     bool unc_attached = false;
     SelectDevice(uh::Tree &t, int dev) : T(t), device(dev) {}
-    ~SelectDevice() { if (h) ugp_mat_destroy(h); }
     void up() {
         if (h) return;
-        bfs = T.bfs();
-        const uint64_t N = bfs.size();
-        for (uint64_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
-        parent.resize(N);
-        mut_off.assign(N + 1, 0);
-        for (uint64_t j = 0; j < N; j++) {
-            parent[j] = bfs[j]->parent ? bfs[j]->parent->flat_index : UINT32_MAX;
-            for (const auto &m : bfs[j]->mutations) {
-                pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
-            }
-            mut_off[j + 1] = pos.size();
-        }
+        A = uh::TreeArrays(T);
+        const uint64_t N = A.bfs.size();
         // the handle takes the bare topology, the select tables the mutations as they are stored (masked, repeated positions)
-        const std::vector<uint64_t> no_off(N + 1, 0);
-        if (pos.empty()) { pos.push_back(0); ref.push_back(0); par.push_back(0); nuc.push_back(0); }   // (never read: no null arrays)
-        const ugp_tree_desc bare{N, parent.data(), no_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
-        desc = ugp_tree_desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
-        if (ugp_mat_create(&bare, device, &h) != UGP_OK) lib_fail("ugp_mat_create");
+        const ugp_tree_desc desc = A.desc();
+        h.create(A.bare(), device);
         if (ugp_select_attach(h, &desc) != UGP_OK) lib_fail("ugp_select_attach");
         uint64_t nl = 0;
         if (ugp_select_leaves(h, nullptr, &nl) != UGP_OK) lib_fail("ugp_select_leaves");
@@ -1397,12 +1332,12 @@ struct SelectDevice {
     }
     std::vector<std::string> in_rank_order(const std::vector<uint64_t> &w) const {   // depth-first
         std::vector<std::string> out;
-        for (uint32_t r = 0; r < leaf_bfs.size(); r++) if (bit(w, r)) out.push_back(bfs[leaf_bfs[r]]->id);
+        for (uint32_t r = 0; r < leaf_bfs.size(); r++) if (bit(w, r)) out.push_back(A.bfs[leaf_bfs[r]]->id);
         return out;
     }
     std::vector<std::string> in_leaves_order(const std::vector<uint64_t> &w, bool set) const {   // get_leaves_ids: breadth-first
         std::vector<std::string> out;
-        for (const uh::Node *n : bfs) if (n->is_leaf() && bit(w, rank_of[n->flat_index]) == set) out.push_back(n->id);
+        for (const uh::Node *n : A.bfs) if (n->is_leaf() && bit(w, rank_of[n->flat_index]) == set) out.push_back(n->id);
         return out;
     }
     std::vector<std::string> filter(const std::vector<std::string> &samples, const std::vector<uint64_t> &w) const {   // sample_intersect
@@ -1412,6 +1347,7 @@ struct SelectDevice {
     }
     std::vector<uint32_t> epps(const std::vector<uint32_t> &nodes) {
         up();
+        const ugp_tree_desc desc = A.desc();
         if (!unc_attached && ugp_uncertainty_attach(h, &desc) != UGP_OK) lib_fail("ugp_uncertainty_attach");
         unc_attached = true;
         const size_t n = nodes.size();
@@ -2018,33 +1954,15 @@ void host_roho(const uh::Tree &T, std::ofstream &f) {   // write_roho_table with
 struct SummaryDevice {
     std::vector<uh::Node *> bfs;
     std::vector<const uh::Mutation *> ent;
-    std::vector<uint32_t> parent;
-    std::vector<uint64_t> mut_off;
-    std::vector<int32_t> pos;
-    std::vector<uint8_t> ref, par, nuc;
-    ugp_mat *h = nullptr;
-    ~SummaryDevice() { if (h) ugp_mat_destroy(h); }
+    Mat h;
     void up(const uh::Tree &T, int device) {
-        bfs = T.bfs();
-        const uint64_t N = bfs.size();
-        for (uint64_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
-        parent.resize(N);
-        mut_off.assign(N + 1, 0);
-        for (uint64_t j = 0; j < N; j++) {
-            parent[j] = bfs[j]->parent ? bfs[j]->parent->flat_index : UINT32_MAX;
-            for (const auto &m : bfs[j]->mutations) {
-                pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
-                ent.push_back(&m);
-            }
-            mut_off[j + 1] = pos.size();
-        }
+        uh::TreeArrays A(T, uh::TreeArrays::kEntries);
         // the handle takes the bare topology, the summary tables the mutations as they are stored (masked, repeated positions)
-        const std::vector<uint64_t> no_off(N + 1, 0);
-        if (pos.empty()) { pos.push_back(0); ref.push_back(0); par.push_back(0); nuc.push_back(0); }   // (never read: no null arrays)
-        const ugp_tree_desc bare{N, parent.data(), no_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
-        const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
-        if (ugp_mat_create(&bare, device, &h) != UGP_OK) lib_fail("ugp_mat_create");
+        const ugp_tree_desc desc = A.desc();
+        h.create(A.bare(), device);
         if (ugp_summary_attach(h, &desc) != UGP_OK) lib_fail("ugp_summary_attach");
+        bfs = std::move(A.bfs);   // the library has its copy of the arrays: only the nodes and the entries are kept
+        ent = std::move(A.ent);
     }
     void mutations(std::ofstream &f) {
         uint64_t n = 0;
@@ -2445,28 +2363,14 @@ void host_translate(uh::Tree &T, std::vector<TrCodon> &codons, std::ofstream &f)
 // The device path: the records of ugp_translate.hip, formatted to the same bytes.  False (with a line on stderr) when the library
 // refuses the tree: the caller walks it on the host.
 bool device_translate(uh::Tree &T, const std::vector<TrCodon> &codons, int device, std::ofstream &f) {
-    const std::vector<uh::Node *> bfs = T.bfs();
+    const uh::TreeArrays A(T, uh::TreeArrays::kEntries);
+    const std::vector<uh::Node *> &bfs = A.bfs;
+    const std::vector<uint64_t> &mut_off = A.mut_off;
+    const std::vector<const uh::Mutation *> &ent = A.ent;
     const uint64_t N = bfs.size();
-    for (uint64_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
-    std::vector<uint32_t> parent(N);
-    std::vector<uint64_t> mut_off(N + 1, 0);
-    std::vector<int32_t> pos;
-    std::vector<uint8_t> ref, par, nuc;
-    std::vector<const uh::Mutation *> ent;
-    for (uint64_t j = 0; j < N; j++) {
-        parent[j] = bfs[j]->parent ? bfs[j]->parent->flat_index : UINT32_MAX;
-        for (const auto &m : bfs[j]->mutations) {
-            pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
-            ent.push_back(&m);
-        }
-        mut_off[j + 1] = pos.size();
-    }
-    const std::vector<uint64_t> no_off(N + 1, 0);
-    if (pos.empty()) { pos.push_back(0); ref.push_back(0); par.push_back(0); nuc.push_back(0); }   // (never read: no null arrays)
-    const ugp_tree_desc bare{N, parent.data(), no_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
-    const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
-    struct Handle { ugp_mat *h = nullptr; ~Handle() { if (h) ugp_mat_destroy(h); } } H;
-    if (ugp_mat_create(&bare, device, &H.h) != UGP_OK) lib_fail("ugp_mat_create");
+    const ugp_tree_desc desc = A.desc();
+    Mat H;
+    H.create(A.bare(), device);
     int rc = ugp_translate_attach(H.h, &desc);
     if (rc == UGP_ERR_UNSUPPORTED) {
         fprintf(stderr, "The device does not take this tree (%s); walking it on the host.\n", ugp_last_error());
@@ -2656,26 +2560,11 @@ void host_haplotypes(const uh::Tree &T, std::ofstream &f) {
 // The device path: the groups and the sets of their first leaves from ugp_haplotypes.hip, ordered here as the std::map orders them.
 // False (with a line on stderr) when the library refuses the tree: the caller walks it on the host.
 bool device_haplotypes(uh::Tree &T, int device, std::ofstream &f) {
-    const std::vector<uh::Node *> bfs = T.bfs();
-    const uint64_t N = bfs.size();
-    for (uint64_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
-    std::vector<uint32_t> parent(N);
-    std::vector<uint64_t> mut_off(N + 1, 0);
-    std::vector<int32_t> pos;
-    std::vector<uint8_t> ref, par, nuc;
-    for (uint64_t j = 0; j < N; j++) {
-        parent[j] = bfs[j]->parent ? bfs[j]->parent->flat_index : UINT32_MAX;
-        for (const auto &m : bfs[j]->mutations) {
-            pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
-        }
-        mut_off[j + 1] = pos.size();
-    }
-    const std::vector<uint64_t> no_off(N + 1, 0);
-    if (pos.empty()) { pos.push_back(0); ref.push_back(0); par.push_back(0); nuc.push_back(0); }   // (never read: no null arrays)
-    const ugp_tree_desc bare{N, parent.data(), no_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
-    const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
-    struct Handle { ugp_mat *h = nullptr; ~Handle() { if (h) ugp_mat_destroy(h); } } H;
-    if (ugp_mat_create(&bare, device, &H.h) != UGP_OK) lib_fail("ugp_mat_create");
+    const uh::TreeArrays A(T);
+    const std::vector<uh::Node *> &bfs = A.bfs;
+    const ugp_tree_desc desc = A.desc();
+    Mat H;
+    H.create(A.bare(), device);
     int rc = ugp_haplotypes_attach(H.h, &desc);
     if (rc == UGP_ERR_UNSUPPORTED) {
         fprintf(stderr, "The device does not take this tree (%s); walking it on the host.\n", ugp_last_error());
@@ -2953,35 +2842,14 @@ int host_relatives(const RelativesJob &J) {
 
 // The device path: ugp_relatives_closest / ugp_relatives_within in batches of samples, formatted to the same bytes.
 int device_relatives(uh::Tree &T, const RelativesJob &J, int device) {
-    const std::vector<uh::Node *> bfs = T.bfs();
-    const uint64_t N = bfs.size();
-    for (uint64_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
-    std::vector<uint32_t> parent(N);
-    std::vector<uint64_t> mut_off(N + 1, 0);
-    std::vector<int32_t> pos;
-    std::vector<uint8_t> ref, par, nuc;
-    for (uint64_t j = 0; j < N; j++) {
-        parent[j] = bfs[j]->parent ? bfs[j]->parent->flat_index : UINT32_MAX;
-        for (const auto &m : bfs[j]->mutations) {
-            pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
-        }
-        mut_off[j + 1] = pos.size();
-    }
-    const std::vector<uint64_t> no_off(N + 1, 0);
-    if (pos.empty()) { pos.push_back(0); ref.push_back(0); par.push_back(0); nuc.push_back(0); }   // (never read: no null arrays)
+    const uh::TreeArrays A(T);
+    const std::vector<uh::Node *> &bfs = A.bfs;
     // the handle carries the topology only: the relatives tables count entries, whatever they hold
-    const ugp_tree_desc bare{N, parent.data(), no_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
-    const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
-    struct Handle { ugp_mat *h = nullptr; ~Handle() { if (h) ugp_mat_destroy(h); } } H;
-    if (ugp_mat_create(&bare, device, &H.h) != UGP_OK) lib_fail("ugp_mat_create");
+    const ugp_tree_desc desc = A.desc();
+    Mat H;
+    H.create(A.bare(), device);
     std::vector<uint32_t> rank;
-    if (J.break_ties && !J.closest_path.empty()) {   // std::string::operator<
-        std::vector<uint32_t> order(N);
-        for (uint64_t j = 0; j < N; j++) order[j] = (uint32_t)j;
-        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return bfs[a]->id != bfs[b]->id ? bfs[a]->id < bfs[b]->id : a < b; });
-        rank.resize(N);
-        for (uint64_t r = 0; r < N; r++) rank[order[r]] = (uint32_t)r;
-    }
+    if (J.break_ties && !J.closest_path.empty()) rank = A.name_rank();
     if (ugp_relatives_attach(H.h, &desc, rank.empty() ? nullptr : rank.data()) != UGP_OK) lib_fail("ugp_relatives_attach");
     const size_t n = J.nodes.size(), per = size_t(1) << 16;   // samples per call: the lists of one call are held at once
     std::vector<uint32_t> qn(n), lists;
@@ -3119,28 +2987,10 @@ struct MaskLine {
     std::set<std::string> exclude;
 };
 
-// The tree flattened for both paths: breadth-first nodes (flat_index), and per breadth-first index the depth-first position and
-// the end of the subtree's depth-first range.
-struct MaskFlat {
-    std::vector<uh::Node *> bfs, dfs;
-    std::vector<uint32_t> dpos, dend;
-    void make(const uh::Tree &T) {
-        bfs = T.bfs();
-        dfs = T.dfs();
-        const size_t N = bfs.size();
-        for (size_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
-        dpos.resize(N);
-        dend.resize(N);
-        for (size_t i = 0; i < N; i++) dpos[dfs[i]->flat_index] = (uint32_t)i;
-        std::vector<uint32_t> sz(N, 1);
-        for (size_t i = N; i-- > 1;) sz[dpos[dfs[i]->parent->flat_index]] += sz[i];
-        for (size_t i = 0; i < N; i++) dend[dfs[i]->flat_index] = (uint32_t)i + sz[i];
-    }
-};
-
 // restrictSamples' three loops (:820-904) statement by statement.  `marks` receives (node, entry) of every entry to mask; the
 // leaves below an ancestor are enumerated breadth-first as get_leaves_ids does, up to the first one that is not named.
-size_t host_restricted(const uh::Tree &T, const MaskFlat &F, const std::vector<std::string> &names,
+// (F: the tree with its depth-first side, uh::TreeArrays::kDepthFirst.)
+size_t host_restricted(const uh::Tree &T, const uh::TreeArrays &F, const std::vector<std::string> &names,
                        std::vector<std::pair<uh::Node *, size_t>> &marks) {
     std::unordered_set<std::string> restricted(names.begin(), names.end());
     std::unordered_set<uh::Node *> roots;
@@ -3203,34 +3053,6 @@ size_t host_mask_on_branch(uh::Node *node, const MaskLine &L) {   // mask_mutati
     return masked;
 }
 
-struct MaskDevice {
-    std::vector<uint32_t> parent;
-    std::vector<uint64_t> mut_off;
-    std::vector<int32_t> pos;
-    std::vector<uint8_t> ref, par, nuc;
-    ugp_mat *h = nullptr;
-    ~MaskDevice() { if (h) ugp_mat_destroy(h); }
-    void up(const MaskFlat &F, int device) {
-        const uint64_t N = F.bfs.size();
-        parent.resize(N);
-        mut_off.assign(N + 1, 0);
-        for (uint64_t j = 0; j < N; j++) {
-            parent[j] = F.bfs[j]->parent ? F.bfs[j]->parent->flat_index : UINT32_MAX;
-            for (const auto &m : F.bfs[j]->mutations) {
-                pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
-            }
-            mut_off[j + 1] = pos.size();
-        }
-        // the handle takes the bare topology, the mask tables the mutations as they are stored (masked, repeated positions)
-        const std::vector<uint64_t> no_off(N + 1, 0);
-        if (pos.empty()) { pos.push_back(0); ref.push_back(0); par.push_back(0); nuc.push_back(0); }   // (never read: no null arrays)
-        const ugp_tree_desc bare{N, parent.data(), no_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
-        const ugp_tree_desc desc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
-        if (ugp_mat_create(&bare, device, &h) != UGP_OK) lib_fail("ugp_mat_create");
-        if (ugp_mask_attach(h, &desc) != UGP_OK) lib_fail("ugp_mask_attach");
-    }
-};
-
 int mask(int argc, char **argv) {   // mask_main, :68-159
     std::string mat, out, samples, mutations, rename;
     bool recondense = false, host = false;
@@ -3280,17 +3102,20 @@ int mask(int argc, char **argv) {   // mask_main, :68-159
         T.uncondense_leaves();
         done(t0, "\n\n");
     }
-    MaskFlat F;
-    MaskDevice D;
+    uh::TreeArrays F;   // the tree for both paths: the breadth-first numbering and the depth-first ranges
+    Mat D;
     if (!samples.empty() || !mutations.empty()) {
-        F.make(T);
+        F = uh::TreeArrays(T, uh::TreeArrays::kDepthFirst);
         if (!host) {
             t0 = clock();
-            D.up(F, device);
+            // the handle takes the bare topology, the mask tables the mutations as they are stored (masked, repeated positions)
+            const ugp_tree_desc desc = F.desc();
+            D.create(F.bare(), device);
+            if (ugp_mask_attach(D, &desc) != UGP_OK) lib_fail("ugp_mask_attach");
             fprintf(stderr, "Tree on device %d in %ld msec\n", device, (long)std::chrono::duration_cast<std::chrono::milliseconds>(clock() - t0).count());
         }
     }
-    std::vector<uint8_t> entry_masked;   // per entry of D's CSR: -s masked it
+    std::vector<uint8_t> entry_masked;   // per entry of the tree arrays: -s masked it
     if (!samples.empty()) {   // restrictSamples, :802-905
         fprintf(stderr, "Performing masking...\n");
         std::ifstream in(samples);
@@ -3314,7 +3139,7 @@ int mask(int argc, char **argv) {   // mask_main, :68-159
         bool on_device = !host;
         if (on_device) {
             if (!leaves_only) fprintf(stderr, "A restricted node is internal: restricted roots can nest, walking on the host.\n");
-            entry_masked.assign(std::max<size_t>(D.pos.size(), 1), 0);
+            entry_masked.assign(std::max<size_t>(F.mut_off.back(), 1), 0);
             uint64_t nr = 0, nm = 0;
             const int rc = leaves_only ? ugp_mask_restricted(D.h, named.size(), named.data(), entry_masked.data(), nullptr, 0, &nr, &nm) : UGP_ERR_UNSUPPORTED;
             if (rc == UGP_ERR_UNSUPPORTED) {
@@ -3324,7 +3149,7 @@ int mask(int argc, char **argv) {   // mask_main, :68-159
             else {
                 n_roots = nr;
                 for (uh::Node *n : F.dfs) {
-                    const uint64_t e0 = D.mut_off[n->flat_index];
+                    const uint64_t e0 = F.mut_off[n->flat_index];
                     for (size_t k = 0; k < n->mutations.size(); k++) if (entry_masked[e0 + k]) marks.emplace_back(n, k);
                 }
             }
@@ -3333,7 +3158,7 @@ int mask(int argc, char **argv) {   // mask_main, :68-159
             n_roots = host_restricted(T, F, names, marks);
             if (!host) {
                 std::fill(entry_masked.begin(), entry_masked.end(), 0);
-                for (const auto &mk : marks) entry_masked[D.mut_off[mk.first->flat_index] + mk.second] = 1;
+                for (const auto &mk : marks) entry_masked[F.mut_off[mk.first->flat_index] + mk.second] = 1;
             }
         }
         fprintf(stderr, "Restricted roots size: %zu\n\n", n_roots);
@@ -3378,7 +3203,7 @@ int mask(int argc, char **argv) {   // mask_main, :68-159
         if (host) {
             for (const auto &L : lines) total_masked += host_mask_on_branch(L.node, L);
         } else {
-            const size_t nl = lines.size(), M = D.mut_off.back();
+            const size_t nl = lines.size(), M = F.mut_off.back();
             std::vector<int32_t> lpos(nl);
             std::vector<uint8_t> lpar(nl), lnuc(nl);
             std::vector<uint32_t> lnode(nl), excl, first(std::max<size_t>(M, 1), UINT32_MAX);
@@ -3413,7 +3238,7 @@ int mask(int argc, char **argv) {   // mask_main, :68-159
                 lib_fail("ugp_mask_mutations");
             for (size_t j = 0; j < F.bfs.size(); j++) {
                 auto &ms = F.bfs[j]->mutations;
-                const uint64_t e0 = D.mut_off[j];
+                const uint64_t e0 = F.mut_off[j];
                 size_t keep = 0;
                 for (size_t k = 0; k < ms.size(); k++) {
                     if (first[e0 + k] != UINT32_MAX) { total_masked++; continue; }

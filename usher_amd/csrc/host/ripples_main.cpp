@@ -145,9 +145,9 @@ int main(int argc, char **argv) {
     std::string err;
     if (!uh::load_mat(mat, T, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
     T.uncondense_leaves();
-    const std::vector<uh::Node *> bfs = T.bfs();
+    const uh::TreeArrays A(T);   // the tree as breadth-first arrays (the C ABI's numbering)
+    const std::vector<uh::Node *> &bfs = A.bfs;
     const uint64_t N = bfs.size();
-    for (uint64_t j = 0; j < N; j++) { bfs[j]->flat_index = (uint32_t)j; bfs[j]->flat_epoch = 0; }
 
     // the branches to consider (:196-251)
     std::unordered_set<std::string> chosen;
@@ -196,23 +196,8 @@ int main(int argc, char **argv) {
         if (E <= (long)e) e = (size_t)E;
     }
     const auto t0 = std::chrono::steady_clock::now();
-    // the tree as breadth-first arrays (the C ABI's numbering) and the name ranks
-    std::vector<uint32_t> parent(N), rank(N), order(N);
-    std::vector<uint64_t> mut_off(N + 1, 0);
-    std::vector<int32_t> pos;
-    std::vector<uint8_t> ref, par, nuc;
-    for (uint64_t j = 0; j < N; j++) {
-        const uh::Node *n = bfs[j];
-        parent[j] = n->parent ? n->parent->flat_index : UINT32_MAX;
-        for (const auto &m : n->mutations) {
-            pos.push_back(m.position); ref.push_back((uint8_t)m.ref_nuc); par.push_back((uint8_t)m.par_nuc); nuc.push_back((uint8_t)m.mut_nuc);
-        }
-        mut_off[j + 1] = pos.size();
-        order[j] = (uint32_t)j;
-    }
-    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return bfs[x]->id < bfs[y]->id; });
-    for (uint64_t k = 0; k < N; k++) rank[order[k]] = (uint32_t)k;
-    const ugp_tree_desc tdesc{N, parent.data(), mut_off.data(), pos.data(), ref.data(), par.data(), nuc.data()};
+    const std::vector<uint32_t> rank = A.name_rank();
+    const ugp_tree_desc tdesc = A.desc();
     ugp_mat *h = nullptr;
     int rc = s < e ? ugp_mat_create(&tdesc, device, &h) : UGP_OK;
     if (rc == UGP_OK && h) rc = ugp_ripples_attach(h, &tdesc, rank.data());
