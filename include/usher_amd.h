@@ -506,6 +506,56 @@ int ugp_mask_mutations_chunked(ugp_mat *mat, uint64_t n_lines, const int32_t *po
 int ugp_mask_time(ugp_mat *mat, uint64_t n, const uint32_t *leaves_bfs, uint64_t n_lines, const int32_t *pos, const uint8_t *par,
                   const uint8_t *nuc, const uint32_t *node_bfs, const uint64_t *excl_off, const uint32_t *excl_bfs, uint32_t reps,
                   double *restricted_ms, double *mutations_ms);
+/* The subtree induced by a selection (mutation_annotated_tree.cpp: get_subtree :1577-1685 with Node::add_mutation :720-752), in
+ * closed form over the depth-first ranges; no pair of samples is visited and nothing climbs.  S is the set of the n named nodes (BFS;
+ * leaf or internal; one given twice counts once).  The KEPT nodes are S and every lowest common ancestor of two members of S: v is
+ * kept exactly when it is in S or at least two of its children have a member of S at or below them.  Kept nodes come in the
+ * depth-first order of the tree.  The SUBTREE PARENT of a kept node is its nearest proper ancestor that is kept; the first kept node
+ * is the subtree's root and has none.  The CHAIN of a kept node v with subtree parent u is the path from u (exclusive) down to v
+ * (inclusive); the root's chain starts at the tree's root (inclusive).  Every node with a member of S at or below it lies in exactly
+ * one chain, whose kept node is its OWNER; every other node has none.
+ * The MERGED ENTRIES of v are what add_mutation leaves of the entries of chain(v), taken top-down and in stored order within a node.
+ * Per position the state is empty or one entry; for each entry e at that position: state empty -- the state becomes a copy of e
+ * (nothing is checked, also when e.par == e.nuc); state s with s.par != e.nuc -- s.nuc = e.nuc; s.par == e.nuc and s.nuc == e.par --
+ * the state becomes empty (a later entry opens a new one with its own ref and par); s.par == e.nuc and s.nuc != e.par -- a
+ * DISAGREEMENT: e is skipped, the state stays, and the call counts it (get_subtree ignores add_mutation's false).  Masked entries
+ * take part with their stored position (-1) and stored alleles.  The result ascends by position.  A merged entry is returned as
+ * its position, the index in the caller's CSR of the entry that OPENED its state (the caller copies ref, par and every other field
+ * from that entry) and its final allele.
+ * ugp_subtree_attach shares the depth-first tables of `tree` (the handle's tree; arrays are copied; tables built from other mutation
+ * arrays: UGP_ERR_INVALID, nothing changed; an allele above 15: UGP_ERR_UNSUPPORTED) and keeps per entry its stored alleles.  A second
+ * attach replaces the first.  A call before the attach is UGP_ERR_INVALID and names the missing call.
+ * ugp_subtree_nodes: n = 0 or a node out of range is UGP_ERR_INVALID before anything is written.  kept_bfs[k] = kept node k (BFS),
+ *   kept_parent[k] = the index in the kept list of its subtree parent (UINT32_MAX: the root), ent_off[k] = the index of its first
+ *   merged entry (its last one is in front of ent_off[k + 1], or of *n_entries for the last kept node).  [0 .. min(cap, *n_kept)) of
+ *   the three is written; *n_kept and *n_entries are always the true counts.  `info` (may be NULL): the distinct selected nodes, the
+ *   tree entries on the chains, the disagreements, the first kept node in depth-first order with one (BFS; UINT32_MAX: none) and
+ *   the nodes of the longest chain.
+ * ugp_subtree_entries: the merged entries of the last ugp_subtree_nodes call, kept node after kept node; [0 .. min(cap, *n_out)) is
+ *   written, *n_out is the true count.  ugp_subtree_owner: owner[i] = the index in the kept list of the owner of node i (BFS; any
+ *   node; out of range or n = 0: UGP_ERR_INVALID), or UINT32_MAX, for the last ugp_subtree_nodes call.  Either before any such call
+ *   is UGP_ERR_INVALID.
+ * The gather of the chains' entries and the merge run in launch windows; the _chunked twin (test hook) sets the items per window
+ * (0: default). */
+typedef struct ugp_subtree_info {
+    uint64_t n_selected;         /* distinct selected nodes                         */
+    uint64_t n_gathered;         /* tree entries on the chains                      */
+    uint64_t n_disagree;         /* entries add_mutation refuses                    */
+    uint64_t longest_chain;      /* nodes of the longest chain                      */
+    uint32_t first_disagree;     /* BFS index, UINT32_MAX: none                     */
+    uint32_t pad;
+} ugp_subtree_info;
+int ugp_subtree_attach(ugp_mat *mat, const ugp_tree_desc *tree);
+int ugp_subtree_nodes(ugp_mat *mat, uint64_t n, const uint32_t *nodes_bfs, uint32_t *kept_bfs /* [cap] */, uint32_t *kept_parent /* [cap] */,
+                      uint64_t *ent_off /* [cap] */, uint64_t cap, uint64_t *n_kept, uint64_t *n_entries, ugp_subtree_info *info /* or NULL */);
+int ugp_subtree_nodes_chunked(ugp_mat *mat, uint64_t n, const uint32_t *nodes_bfs, uint32_t *kept_bfs, uint32_t *kept_parent, uint64_t *ent_off,
+                              uint64_t cap, uint64_t *n_kept, uint64_t *n_entries, ugp_subtree_info *info, uint64_t chunk_items);
+int ugp_subtree_entries(ugp_mat *mat, int32_t *pos /* [cap] */, uint32_t *first_entry /* [cap] */, uint8_t *nuc /* [cap] */, uint64_t cap,
+                        uint64_t *n_out);
+int ugp_subtree_owner(ugp_mat *mat, uint64_t n, const uint32_t *nodes_bfs, uint32_t *owner /* [n] */);
+/* Bench hook: milliseconds of device time of the passes alone, no copies, for the n named nodes: *nodes_ms the marks, the scans and
+ * the kept list, *merge_ms the gather, the sort, the merge and the compaction; each the mean of `reps` runs after one warm-up run. */
+int ugp_subtree_time(ugp_mat *mat, uint64_t n, const uint32_t *nodes_bfs, uint32_t reps, double *nodes_ms, double *merge_ms);
 /* matUtils summary --haplotype (matUtils/summary.cpp: count_haplotypes :182-218, write_haplotype_table :244-264): the distinct
  * HAPLOTYPES of the leaves with the number of leaves that carry each.  The reference walks the nodes in depth-first order with a
  * std::map<int,int8_t> per node: a node starts from its parent's map (the root from an empty one) and applies its entries in stored

@@ -125,6 +125,12 @@ SYMBOLS = {
     "ugp_mask_mutations": (C.c_int, [P, C.c_uint64, P, P, P, P, P, P, P, P, P]),
     "ugp_mask_mutations_chunked": (C.c_int, [P, C.c_uint64, P, P, P, P, P, P, P, P, P, C.c_uint32]),
     "ugp_mask_time": (C.c_int, [P, C.c_uint64, P, C.c_uint64, P, P, P, P, P, P, C.c_uint32, P, P]),
+    "ugp_subtree_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc)]),
+    "ugp_subtree_nodes": (C.c_int, [P, C.c_uint64, P, P, P, P, C.c_uint64, P, P, P]),
+    "ugp_subtree_nodes_chunked": (C.c_int, [P, C.c_uint64, P, P, P, P, C.c_uint64, P, P, P, C.c_uint64]),
+    "ugp_subtree_entries": (C.c_int, [P, P, P, P, C.c_uint64, P]),
+    "ugp_subtree_owner": (C.c_int, [P, C.c_uint64, P, P]),
+    "ugp_subtree_time": (C.c_int, [P, C.c_uint64, P, C.c_uint32, P, P]),
     "ugp_haplotypes_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc)]),
     "ugp_haplotype_groups": (C.c_int, [P, P, C.c_uint64, P, P]),
     "ugp_haplotype_groups_hashed": (C.c_int, [P, P, C.c_uint64, P, P, C.c_uint32]),

@@ -30,6 +30,8 @@
 // body: the selections are bitmaps over leaf ranks from ugp_select.hip, -e asks ugp_uncertainty; --host runs the reference's walks.
 // mask_main (mask.cpp:68-159), as the subcommand `mask`: -s (restrictSamples) and -m (restrictMutationsLocally) ask ugp_mask.hip which
 // entries to mask or remove and apply the answer to the host tree; -r, -c and the writer run on the host; --host walks as the reference.
+// get_subtree (mutation_annotated_tree.cpp:1577-1685), as the subcommand `subtree`: select's body, with the induced subtree of the
+// selection from ugp_subtree.hip (kept nodes, subtree parents, merged entries, chain owners) instead of the pairwise walk; --host runs it.
 #include <hip/hip_runtime_api.h>
 #include <sys/stat.h>
 #include <zlib.h>
@@ -69,7 +71,8 @@ void usage(FILE *f) {
             "      --device             HIP device ordinal [0]\n"
             "  (-d / --dropout-mutations is not supported)\n"
             "       matutils-amd annotate --help | matutils-amd extract --help | matutils-amd summarize --help | matutils-amd translate --help\n"
-            "       matutils-amd relatives --help | matutils-amd select --help | matutils-amd mask --help | matutils-amd haplotypes --help\n");
+            "       matutils-amd relatives --help | matutils-amd select --help | matutils-amd mask --help | matutils-amd haplotypes --help\n"
+            "       matutils-amd subtree --help\n");
 }
 
 [[noreturn]] void lib_fail(const char *what) {
@@ -1282,10 +1285,11 @@ struct SelectDevice {
     uh::TreeArrays A;   // kept: -e attaches the uncertainty tables later
     std::vector<uint32_t> leaf_bfs, rank_of;   // rank_of by BFS index, UINT32_MAX for an internal node
     bool unc_attached = false;
-    SelectDevice(uh::Tree &t, int dev) : T(t), device(dev) {}
+    unsigned keep;      // what A keeps beside the arrays (subtree: the entries)
+    SelectDevice(uh::Tree &t, int dev, unsigned keep_ = 0) : T(t), device(dev), keep(keep_) {}
     void up() {
         if (h) return;
-        A = uh::TreeArrays(T);
+        A = uh::TreeArrays(T, keep);
         const uint64_t N = A.bfs.size();
         // the handle takes the bare topology, the select tables the mutations as they are stored (masked, repeated positions)
         const ugp_tree_desc desc = A.desc();
@@ -1605,15 +1609,96 @@ bool select_prune(uh::Tree &T, const SelectOpts &O, SelectDevice &D, std::vector
     return true;
 }
 
-// extract_main, extract.cpp:149-640, 867-888 for the options of extract_usage; `sel`: the subcommand `select`, which adds the selectors
-int extract_or_select(int argc, char **argv, bool sel) {
+// ---- subtree: select, with the induced subtree from ugp_subtree.hip instead of get_subtree ---------------------------------------
+
+void subtree_usage(FILE *f) {
+    fprintf(f,
+            "Usage: matutils-amd subtree -i tree.pb [-s samples.txt] [-k sample:k] [-I node] [-c clade[,clade]] [-m mutation[,mutation]] [-H regex]\n"
+            "       [-a n] [-b n] [-P n] [-e n] [-U] [-Y y] [-p] [-u used.txt] [-t tree.nh] [-o out.pb] [-v out.vcf] [-n] [-d dir] [-T n]\n"
+            "       [--device k] [--reference-ties] [--host-genotypes] [--host]\n"
+            "  every option of matutils-amd select (see select --help), with the same output; the subtree of the selection (its samples,\n"
+            "  the most recent common ancestor of every pair, the mutations merged along the collapsed paths) is built on the device from\n"
+            "  the depth-first ranges instead of pair by pair on the host.\n"
+            "      --host               run every selector and get_subtree as the reference's walk on the host (slow)\n");
+}
+
+// get_subtree (mat.cpp) from the three calls of ugp_subtree.hip: the kept nodes in depth-first order below their subtree parents,
+// their merged entries (every field but the allele from the entry that opened the state) and the annotations of their chains.
+bool device_subtree(uh::Tree &T, SelectDevice &D, const std::vector<std::string> &samples, uh::Tree &dst, std::string &err) {
+    D.up();
+    std::vector<uint32_t> nodes;
+    for (const std::string &s : samples) {
+        const uh::Node *n = T.get_node(s);
+        if (!n) { err = "get_subtree: sample " + s + " is not in the tree"; return false; }
+        nodes.push_back(n->flat_index);
+    }
+    const ugp_tree_desc desc = D.A.desc();
+    if (ugp_subtree_attach(D.h, &desc) != UGP_OK) lib_fail("ugp_subtree_attach");
+    const size_t room = std::min(2 * nodes.size(), D.A.bfs.size());   // n names keep fewer than 2n nodes
+    std::vector<uint32_t> kept(room), kpar(room);
+    std::vector<uint64_t> off(room + 1);
+    uint64_t nk = 0, ne = 0;
+    ugp_subtree_info info;
+    if (ugp_subtree_nodes(D.h, nodes.size(), nodes.data(), kept.data(), kpar.data(), off.data(), room, &nk, &ne, &info) != UGP_OK)
+        lib_fail("ugp_subtree_nodes");
+    if (nk > room) { err = "get_subtree: more kept nodes than twice the selection"; return false; }
+    off[nk] = ne;
+    std::vector<int32_t> pos(std::max<uint64_t>(ne, 1));
+    std::vector<uint32_t> first(std::max<uint64_t>(ne, 1));
+    std::vector<uint8_t> nuc(std::max<uint64_t>(ne, 1));
+    uint64_t got = 0;
+    if (ugp_subtree_entries(D.h, pos.data(), first.data(), nuc.data(), ne, &got) != UGP_OK) lib_fail("ugp_subtree_entries");
+    if (info.n_disagree)
+        fprintf(stderr, "WARNING: %llu consecutive mutations at one position disagree and are skipped (first below node %s)\n",
+                (unsigned long long)info.n_disagree, D.A.bfs[info.first_disagree]->id.c_str());
+    const size_t n_ann = T.num_annotations();
+    std::vector<uh::Node *> made(nk);
+    for (uint64_t k = 0; k < nk; k++) {
+        const uh::Node *src = D.A.bfs[kept[k]];
+        uh::Node *nn = dst.create_node(src->id, kpar[k] == UINT32_MAX ? nullptr : made[kpar[k]], -1.0f);
+        if (!nn) { err = "get_subtree: duplicate node " + src->id; return false; }
+        nn->clade_annotations.assign(n_ann, "");
+        nn->mutations.reserve(off[k + 1] - off[k]);
+        for (uint64_t e = off[k]; e < off[k + 1]; e++) {
+            uh::Mutation m = *D.A.ent[first[e]];
+            m.mut_nuc = (int8_t)nuc[e];
+            nn->mutations.push_back(m);
+        }
+        made[k] = nn;
+    }
+    // annotations: a kept node takes, per column, the deepest one of its chain; the subtree's root only its own (:1640-1644)
+    std::vector<const uh::Node *> ann;
+    for (const uh::Node *n : T.dfs())
+        for (const std::string &a : n->clade_annotations) if (!a.empty()) { ann.push_back(n); break; }
+    if (!ann.empty()) {
+        std::vector<uint32_t> at(ann.size()), owner(ann.size());
+        for (size_t i = 0; i < ann.size(); i++) at[i] = ann[i]->flat_index;
+        if (ugp_subtree_owner(D.h, at.size(), at.data(), owner.data()) != UGP_OK) lib_fail("ugp_subtree_owner");
+        for (size_t i = 0; i < ann.size(); i++) {   // depth-first: top-down within a chain
+            if (owner[i] == UINT32_MAX || (owner[i] == 0 && at[i] != kept[0])) continue;
+            uh::Node *nn = made[owner[i]];
+            for (size_t k = 0; k < n_ann && k < ann[i]->clade_annotations.size(); k++)
+                if (!ann[i]->clade_annotations[k].empty()) nn->clade_annotations[k] = ann[i]->clade_annotations[k];
+        }
+    }
+    dst.curr_internal_node = T.curr_internal_node;
+    dst.chroms = T.chroms;
+    return true;
+}
+
+enum { kExtract = 0, kSelect = 1, kSubtree = 2 };
+
+// extract_main, extract.cpp:149-640, 867-888 for the options of extract_usage; kSelect: the subcommand `select`, which adds the
+// selectors; kSubtree: `subtree`, which is select with the induced subtree built on the device
+int extract_or_select(int argc, char **argv, int mode) {
+    const bool sel = mode != kExtract;
     std::string in_mat, fsamples, nearest_k, fused, ftree, fmat, fvcf, dir = "./";
     int max_parsimony = -1, max_branch = -1, max_path = -1, device = 0;
     size_t select_nearest = 0;
     bool reference_ties = false, no_genotypes = false, host_genotypes = false;
     SelectOpts S;
     S.on = sel;
-    void (*const show_usage)(FILE *) = sel ? select_usage : extract_usage;
+    void (*const show_usage)(FILE *) = mode == kSubtree ? subtree_usage : sel ? select_usage : extract_usage;
     static const char *const unsupported[] = {
         "-K", "--nearest-k-batch", "-j", "--write-json", "-c", "--clade", "-m", "--mutation", "-H", "--match",
         "-V", "--closest-relatives", "-q", "--break-ties", "--within-distance", "--distance-threshold", "-z", "--set-size", "-W", "--add-random",
@@ -1731,7 +1816,7 @@ int extract_or_select(int argc, char **argv, bool sel) {
             samples = inter;
         }
     }
-    SelectDevice seldev(T, device);
+    SelectDevice seldev(T, device, mode == kSubtree ? (unsigned)uh::TreeArrays::kEntries : 0u);
     if (sel && !select_before_filters(T, S, seldev, samples)) return 1;
     if (max_parsimony >= 0) { samples = get_parsimony_samples(T, samples, max_parsimony); if (samples.empty()) { fputs(none, stderr); return 1; } }
     if (max_branch >= 0) { samples = get_short_steppers(T, samples, max_branch); if (samples.empty()) { fputs(none, stderr); return 1; } }
@@ -1755,7 +1840,10 @@ int extract_or_select(int argc, char **argv, bool sel) {
         samples = leaf_ids(T);
     } else {
         fprintf(stderr, "Extracting subtree of %zu samples.\n", samples.size());
-        if (!uh::get_subtree(T, samples, sub, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+        const auto t0 = std::chrono::steady_clock::now();
+        const bool ok = mode == kSubtree && !S.host ? device_subtree(T, seldev, samples, sub, err) : uh::get_subtree(T, samples, sub, err);
+        if (!ok) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+        if (mode == kSubtree) step_time("subtree", S.host, t0);
         out = &sub;
     }
     if (!fused.empty()) {
@@ -1782,8 +1870,9 @@ int extract_or_select(int argc, char **argv, bool sel) {
     return 0;
 }
 
-int extract(int argc, char **argv) { return extract_or_select(argc, argv, false); }
-int select_samples(int argc, char **argv) { return extract_or_select(argc, argv, true); }
+int extract(int argc, char **argv) { return extract_or_select(argc, argv, kExtract); }
+int select_samples(int argc, char **argv) { return extract_or_select(argc, argv, kSelect); }
+int subtree(int argc, char **argv) { return extract_or_select(argc, argv, kSubtree); }
 
 // ---- summary (summary.cpp) ----------------------------------------------------------------------------------------
 
@@ -3300,8 +3389,9 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "translate")) return translate(argc - 2, argv + 2);
     if (!strcmp(argv[1], "relatives")) return relatives(argc - 2, argv + 2);
     if (!strcmp(argv[1], "select")) return select_samples(argc - 2, argv + 2);
+    if (!strcmp(argv[1], "subtree")) return subtree(argc - 2, argv + 2);
     if (!strcmp(argv[1], "mask")) return mask(argc - 2, argv + 2);
     if (!strcmp(argv[1], "haplotypes")) return haplotypes(argc - 2, argv + 2);
-    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate, extract, summarize, haplotypes, translate, relatives, select, mask)\n", argv[1]);
+    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate, extract, subtree, summarize, haplotypes, translate, relatives, select, mask)\n", argv[1]);
     return 1;
 }

@@ -33,6 +33,7 @@
 #include "ugp_relatives.hpp"
 #include "ugp_haplotypes.hpp"
 #include "ugp_mask.hpp"
+#include "ugp_subtree.hpp"
 #include "ugp_select.hpp"
 #include "ugp_genotypes.hpp"
 #include "ugp_summary.hpp"
@@ -312,6 +313,7 @@ struct ugp_mat {
     ugp::TrState *tr = nullptr;      // matUtils summary --translate tables (ugp_translate_attach), or none
     ugp::SelState *sel = nullptr;    // matUtils extract selector tables (ugp_select_attach), or none
     ugp::MskState *msk = nullptr;    // matUtils mask tables (ugp_mask_attach), or none
+    ugp::SubState *sub = nullptr;    // induced-subtree tables (ugp_subtree_attach), or none
     ugp::HpState *hp = nullptr;      // matUtils summary --haplotype tables (ugp_haplotypes_attach), or none
     ugp::DfsTables *dfs = nullptr;   // the depth-first tables uncertainty and annotate share (their first attach), or none
     hipEvent_t kb_done = nullptr;    // behind the latest k_best8 launch of this handle ...
@@ -1441,6 +1443,7 @@ void ugp_mat_destroy(ugp_mat *m) {
     ugp::tr_free(m->tr);
     ugp::sel_free(m->sel);
     ugp::msk_free(m->msk);
+    ugp::sub_free(m->sub);
     ugp::hp_free(m->hp);
     ugp::dfs_tables_free(m->dfs);
     delete m;
@@ -2059,6 +2062,40 @@ int ugp_mask_time(ugp_mat *m, uint64_t n, const uint32_t *leaves_bfs, uint64_t n
                   double *restricted_ms, double *mutations_ms) {
     if (!m) return fail(UGP_ERR_INVALID, "null argument");
     return ugp::msk_time(m->msk, n, leaves_bfs, n_lines, pos, par, nuc, node_bfs, excl_off, excl_bfs, reps, restricted_ms, mutations_ms);
+}
+
+// ---- the subtree induced by a selection, in closed form (ugp_subtree.hip) ------------------------------------------------
+
+int ugp_subtree_attach(ugp_mat *m, const ugp_tree_desc *tree) {
+    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
+    if (int rc = check_handle_tree(m, tree)) return rc;
+    return ugp::sub_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->sub);
+}
+
+int ugp_subtree_nodes_chunked(ugp_mat *m, uint64_t n, const uint32_t *nodes_bfs, uint32_t *kept_bfs, uint32_t *kept_parent, uint64_t *ent_off,
+                              uint64_t cap, uint64_t *n_kept, uint64_t *n_entries, ugp_subtree_info *info, uint64_t chunk_items) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sub_nodes(m->sub, n, nodes_bfs, kept_bfs, kept_parent, ent_off, cap, n_kept, n_entries, info, chunk_items);
+}
+
+int ugp_subtree_nodes(ugp_mat *m, uint64_t n, const uint32_t *nodes_bfs, uint32_t *kept_bfs, uint32_t *kept_parent, uint64_t *ent_off,
+                      uint64_t cap, uint64_t *n_kept, uint64_t *n_entries, ugp_subtree_info *info) {
+    return ugp_subtree_nodes_chunked(m, n, nodes_bfs, kept_bfs, kept_parent, ent_off, cap, n_kept, n_entries, info, 0);
+}
+
+int ugp_subtree_entries(ugp_mat *m, int32_t *pos, uint32_t *first_entry, uint8_t *nuc, uint64_t cap, uint64_t *n_out) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sub_entries(m->sub, pos, first_entry, nuc, cap, n_out);
+}
+
+int ugp_subtree_owner(ugp_mat *m, uint64_t n, const uint32_t *nodes_bfs, uint32_t *owner) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sub_owner(m->sub, n, nodes_bfs, owner);
+}
+
+int ugp_subtree_time(ugp_mat *m, uint64_t n, const uint32_t *nodes_bfs, uint32_t reps, double *nodes_ms, double *merge_ms) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sub_time(m->sub, n, nodes_bfs, reps, nodes_ms, merge_ms);
 }
 
 // ---- matUtils extract -v: genotypes of a selection (ugp_genotypes.hip) -------------------------------------------------

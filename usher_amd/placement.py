@@ -772,6 +772,71 @@ class Placer:
                                        _ptr(flat) if len(flat) else None, int(reps), C.byref(a), C.byref(b)))
         return float(a.value), float(b.value)
 
+    # ---- the subtree induced by a selection, in closed form (ugp_subtree_*) ----------------------------------------------------------
+    SUB_INFO = np.dtype([("n_selected", np.uint64), ("n_gathered", np.uint64), ("n_disagree", np.uint64), ("longest_chain", np.uint64),
+                         ("first_disagree", np.uint32), ("pad", np.uint32)])
+
+    def subtree_attach(self, arrays: Optional[Dict] = None):
+        """ugp_subtree_attach with the placer's own tree, or with other mutation arrays on the same topology (masked entries, two
+        entries at one position on a node).  The depth-first tables are shared as genotypes_attach describes."""
+        t = self._t if arrays is None else _TreeArrays(arrays)
+        self._ck(self._L.ugp_subtree_attach(self._h, C.byref(t.desc)))
+
+    def subtree_nodes(self, nodes, chunk_items: int = 0, cap: Optional[int] = None):
+        """get_subtree (mutation_annotated_tree.cpp:1577-1685) for the named nodes (BFS indices, leaf or internal): a dict with
+        kept (BFS indices in depth-first order), parent (index into kept, UINT32_MAX for the root), ent_off (CSR offsets, one more
+        than kept), pos / first_entry / nuc (the merged entries: position, the index in the mutation CSR of the entry that opened
+        the state, the final allele) and info (a SUB_INFO scalar).  chunk_items (test hook): items per launch window; cap (test
+        hook): room for that many kept nodes and merged entries only (ent_off then has as many values as kept)."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
+        info = np.zeros(1, self.SUB_INFO)
+        nk, ne = C.c_uint64(0), C.c_uint64(0)
+
+        def call(kept, par, off, room):
+            self._ck(self._L.ugp_subtree_nodes_chunked(self._h, len(nodes), _ptr(nodes) if len(nodes) else None, _ptr(kept) if room else None,
+                                                       _ptr(par) if room else None, _ptr(off) if room else None, int(room), C.byref(nk),
+                                                       C.byref(ne), _ptr(info), int(chunk_items)))
+
+        if cap is None:   # the two-call convention: the counts, then the lists
+            call(None, None, None, 0)
+            room = int(nk.value)
+        else:
+            room = int(cap)
+        kept, par = np.full(room, 0xA5A5A5A5, np.uint32), np.full(room, 0xA5A5A5A5, np.uint32)
+        off = np.full(room + 1, 0xA5A5A5A5A5A5A5A5, np.uint64)
+        call(kept, par, off, room)
+        w = min(room, int(nk.value))
+        n_ent = int(ne.value)
+        eroom = n_ent if cap is None else min(int(cap), n_ent)
+        pos, first, nuc = np.zeros(eroom, np.int32), np.zeros(eroom, np.uint32), np.zeros(eroom, np.uint8)
+        n_out = C.c_uint64(0)
+        self._ck(self._L.ugp_subtree_entries(self._h, _ptr(pos) if eroom else None, _ptr(first) if eroom else None,
+                                             _ptr(nuc) if eroom else None, eroom, C.byref(n_out)))
+        if int(n_out.value) != n_ent:
+            raise UgpError(-1, "ugp_subtree_entries and ugp_subtree_nodes disagree on the number of merged entries")
+        if w == int(nk.value):
+            off[w] = n_ent
+            off = off[:w + 1]
+        else:
+            off = off[:w]
+        return {"kept": kept[:w], "parent": par[:w], "ent_off": off, "pos": pos, "first_entry": first, "nuc": nuc, "info": info[0].copy(),
+                "n_kept": int(nk.value), "n_entries": n_ent}
+
+    def subtree_owner(self, nodes) -> np.ndarray:
+        """Per node (BFS indices, any node) the index in the kept list of the last subtree_nodes call of the kept node whose chain
+        holds it, or UINT32_MAX when no selected node lies at or below it."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
+        owner = np.full(len(nodes), 0xA5A5A5A5, np.uint32)
+        self._ck(self._L.ugp_subtree_owner(self._h, len(nodes), _ptr(nodes) if len(nodes) else None, _ptr(owner) if len(nodes) else None))
+        return owner
+
+    def subtree_time(self, nodes, reps: int = 5):
+        """Bench hook: (nodes_ms, merge_ms), milliseconds of device time of the passes alone for the named nodes."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
+        a, b = C.c_double(0), C.c_double(0)
+        self._ck(self._L.ugp_subtree_time(self._h, len(nodes), _ptr(nodes) if len(nodes) else None, int(reps), C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
+
     # ---- matUtils summary --haplotype (ugp_haplotypes_attach / ugp_haplotype_groups / _sets) --------------------------------------
     HP_GROUP = np.dtype([("leaf", np.uint32), ("count", np.uint32), ("size", np.uint32), ("pad", np.uint32)])
     HP_INFO = np.dtype([("n_leaves", np.uint64), ("n_groups", np.uint64), ("n_collisions", np.uint64), ("n_duplicate", np.uint64),
