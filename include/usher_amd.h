@@ -556,6 +556,46 @@ int ugp_subtree_owner(ugp_mat *mat, uint64_t n, const uint32_t *nodes_bfs, uint3
 /* Bench hook: milliseconds of device time of the passes alone, no copies, for the n named nodes: *nodes_ms the marks, the scans and
  * the kept list, *merge_ms the gather, the sort, the merge and the compaction; each the mean of `reps` runs after one warm-up run. */
 int ugp_subtree_time(ugp_mat *mat, uint64_t n, const uint32_t *nodes_bfs, uint32_t reps, double *nodes_ms, double *merge_ms);
+/* Many induced subtrees of the attached tree in one call (matUtils/convert.cpp: get_minimum_subtrees :665-798 builds one per
+ * neighbourhood).  Selection b is nodes_bfs[sel_off[b] .. sel_off[b + 1]); its result is exactly what ugp_subtree_nodes and
+ * ugp_subtree_entries return for that selection alone, by the definitions above.  The device work and workspace of a selection
+ * follow its WINDOW -- the depth-first range of its lowest common ancestor, the entries on those nodes and the entries on the
+ * ancestor's root path -- not the tree: selections are laid end to end in GROUPS of at most group_positions window positions
+ * (0: the default, half the tree's nodes and half its entries, so that a group needs no more memory than the single call's
+ * tables; a selection whose window alone is larger runs as a group of its own), and the passes run once per group.
+ * ugp_subtree_batch: n_sel = 0, an empty selection, a node out of range or descending sel_off is UGP_ERR_INVALID before anything is
+ *   written.  kept_off[b] / entry_off[b] ([n_sel + 1]) = the first kept node / merged entry of selection b in the batch's lists;
+ *   info[b] (info may be NULL): the single call's counts for selection b, its kept nodes and merged entries, and its lowest common
+ *   ancestor (BFS), which is its first kept node.
+ * ugp_subtree_batch_nodes: the kept nodes of the last batch, selection after selection, each slice in depth-first order.
+ *   kept_parent[k] is an index WITHIN the slice of k's selection (UINT32_MAX: the slice's root, whose chain starts at the tree's
+ *   root); ent_off[k] indexes the batch's entry list (the last entry of k is in front of ent_off[k + 1], or of the entry count for
+ *   the last kept node).  ugp_subtree_batch_entries: the merged entries of the last batch.  Both follow the single call's cap
+ *   convention: [0 .. min(cap, *n_out)) is written, *n_out is the true count; either before any batch is UGP_ERR_INVALID.
+ * The batch keeps its own result: ugp_subtree_entries and ugp_subtree_owner go on answering for the last ugp_subtree_nodes call, and
+ * a single call leaves the last batch's lists as they are.  The _chunked twin (test hook) sets the group budget and the items
+ * per launch window of the gather and the merge (0: default). */
+typedef struct ugp_subtree_batch_info {
+    uint64_t n_selected;         /* distinct selected nodes                         */
+    uint64_t n_kept;             /* kept nodes                                      */
+    uint64_t n_entries;          /* merged entries                                  */
+    uint64_t n_gathered;         /* tree entries on the chains                      */
+    uint64_t n_disagree;         /* entries add_mutation refuses                    */
+    uint64_t longest_chain;      /* nodes of the longest chain                      */
+    uint32_t first_disagree;     /* BFS index, UINT32_MAX: none                     */
+    uint32_t lca;                /* BFS index of the lowest common ancestor         */
+} ugp_subtree_batch_info;
+int ugp_subtree_batch(ugp_mat *mat, uint64_t n_sel, const uint64_t *sel_off /* [n_sel + 1] */, const uint32_t *nodes_bfs,
+                      uint64_t *kept_off /* [n_sel + 1] */, uint64_t *entry_off /* [n_sel + 1] */, ugp_subtree_batch_info *info /* [n_sel] or NULL */);
+int ugp_subtree_batch_chunked(ugp_mat *mat, uint64_t n_sel, const uint64_t *sel_off, const uint32_t *nodes_bfs, uint64_t *kept_off,
+                              uint64_t *entry_off, ugp_subtree_batch_info *info, uint64_t group_positions, uint64_t chunk_items);
+int ugp_subtree_batch_nodes(ugp_mat *mat, uint32_t *kept_bfs /* [cap] */, uint32_t *kept_parent /* [cap] */, uint64_t *ent_off /* [cap] */,
+                            uint64_t cap, uint64_t *n_out);
+int ugp_subtree_batch_entries(ugp_mat *mat, int32_t *pos /* [cap] */, uint32_t *first_entry /* [cap] */, uint8_t *nuc /* [cap] */, uint64_t cap,
+                              uint64_t *n_out);
+/* Bench hook: as ugp_subtree_time, for the passes of every group of the batch (default budget), summed over the groups. */
+int ugp_subtree_batch_time(ugp_mat *mat, uint64_t n_sel, const uint64_t *sel_off, const uint32_t *nodes_bfs, uint32_t reps, double *nodes_ms,
+                           double *merge_ms);
 /* matUtils summary --haplotype (matUtils/summary.cpp: count_haplotypes :182-218, write_haplotype_table :244-264): the distinct
  * HAPLOTYPES of the leaves with the number of leaves that carry each.  The reference walks the nodes in depth-first order with a
  * std::map<int,int8_t> per node: a node starts from its parent's map (the root from an empty one) and applies its entries in stored

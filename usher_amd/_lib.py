@@ -131,6 +131,11 @@ SYMBOLS = {
     "ugp_subtree_entries": (C.c_int, [P, P, P, P, C.c_uint64, P]),
     "ugp_subtree_owner": (C.c_int, [P, C.c_uint64, P, P]),
     "ugp_subtree_time": (C.c_int, [P, C.c_uint64, P, C.c_uint32, P, P]),
+    "ugp_subtree_batch": (C.c_int, [P, C.c_uint64, P, P, P, P, P]),
+    "ugp_subtree_batch_chunked": (C.c_int, [P, C.c_uint64, P, P, P, P, P, C.c_uint64, C.c_uint64]),
+    "ugp_subtree_batch_nodes": (C.c_int, [P, P, P, P, C.c_uint64, P]),
+    "ugp_subtree_batch_entries": (C.c_int, [P, P, P, P, C.c_uint64, P]),
+    "ugp_subtree_batch_time": (C.c_int, [P, C.c_uint64, P, P, C.c_uint32, P, P]),
     "ugp_haplotypes_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc)]),
     "ugp_haplotype_groups": (C.c_int, [P, P, C.c_uint64, P, P]),
     "ugp_haplotype_groups_hashed": (C.c_int, [P, P, C.c_uint64, P, P, C.c_uint32]),

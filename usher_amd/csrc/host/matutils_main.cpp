@@ -32,6 +32,9 @@
 // entries to mask or remove and apply the answer to the host tree; -r, -c and the writer run on the host; --host walks as the reference.
 // get_subtree (mutation_annotated_tree.cpp:1577-1685), as the subcommand `subtree`: select's body, with the induced subtree of the
 // selection from ugp_subtree.hip (kept nodes, subtree parents, merged entries, chain owners) instead of the pairwise walk; --host runs it.
+// extract -N (get_minimum_subtrees, convert.cpp:665-798), as the subcommand `subtrees`: select's body, then the greedy cover of the
+// samples by nearest-N neighbourhoods in rounds of batched searches (ugp_nearest_k) and every neighbourhood's induced subtree from one
+// ugp_subtree_batch call per round, written as <name>-subtree-<i>.nw and subtree-assignments.tsv; --host runs get_nearby and get_subtree.
 #include <hip/hip_runtime_api.h>
 #include <sys/stat.h>
 #include <zlib.h>
@@ -72,7 +75,7 @@ void usage(FILE *f) {
             "  (-d / --dropout-mutations is not supported)\n"
             "       matutils-amd annotate --help | matutils-amd extract --help | matutils-amd summarize --help | matutils-amd translate --help\n"
             "       matutils-amd relatives --help | matutils-amd select --help | matutils-amd mask --help | matutils-amd haplotypes --help\n"
-            "       matutils-amd subtree --help\n");
+            "       matutils-amd subtree --help | matutils-amd subtrees --help\n");
 }
 
 [[noreturn]] void lib_fail(const char *what) {
@@ -988,14 +991,24 @@ struct NearestSearch {
     bool reference_ties;
     std::vector<uh::Node *> bfs;
     Mat h;
+    ugp_mat *use = nullptr;   // h, or the handle share() was given
     NearestSearch(uh::Tree &t, int dev, bool ties) : T(t), device(dev), reference_ties(ties) {}
     void up() {
-        if (h) return;
+        if (use) return;
         uh::TreeArrays A(T);
         const ugp_tree_desc desc = A.desc();
         h.create(desc, device);
         if (ugp_nearest_attach(h, &desc) != UGP_OK) lib_fail("ugp_nearest_attach");
         bfs = std::move(A.bfs);   // the library has its copy of the arrays: only the nodes are kept
+        use = h;
+    }
+    // subtrees: search on the handle another owner has made of this tree and its arrays, instead of on a second copy of the tree
+    void share(ugp_mat *other, const uh::TreeArrays &A) {
+        if (use) return;
+        const ugp_tree_desc desc = A.desc();
+        if (ugp_nearest_attach(other, &desc) != UGP_OK) lib_fail("ugp_nearest_attach");
+        bfs = A.bfs;
+        use = other;
     }
     // The literal sort of one query between the device's anc and last_anc: Tree::get_leaves' order into std::sort.
     std::vector<std::string> literal(uh::Node *anc, uh::Node *last, size_t k) const {
@@ -1028,7 +1041,7 @@ struct NearestSearch {
         for (size_t i0 = 0; i0 < n; i0 += per) {
             const size_t m = std::min(per, n - i0);
             on.resize(m * k); od.resize(m * k);
-            if (ugp_nearest_k(h, m, qn.data() + i0, qk.data() + i0, (uint32_t)k, on.data(), od.data(), info.data() + i0) != UGP_OK) lib_fail("ugp_nearest_k");
+            if (ugp_nearest_k(use, m, qn.data() + i0, qk.data() + i0, (uint32_t)k, on.data(), od.data(), info.data() + i0) != UGP_OK) lib_fail("ugp_nearest_k");
             for (size_t i = 0; i < m; i++) {
                 const ugp_nearest_info &f = info[i0 + i];
                 if (f.anc == UINT32_MAX) continue;
@@ -1686,7 +1699,211 @@ bool device_subtree(uh::Tree &T, SelectDevice &D, const std::vector<std::string>
     return true;
 }
 
-enum { kExtract = 0, kSelect = 1, kSubtree = 2 };
+// ---- subtrees: extract -N, one induced subtree around each of many samples (get_minimum_subtrees, convert.cpp:665-798) -----------
+
+void subtrees_usage(FILE *f) {
+    fprintf(f,
+            "Usage: matutils-amd subtrees -i tree.pb -N n -t name [-s samples.txt] [-k sample:k] [-I node] [-c clade[,clade]] [-m mutation[,mutation]]\n"
+            "       [-H regex] [-a n] [-b n] [-P n] [-e n] [-U] [-Y y] [-p] [-u used.txt] [-d dir] [-T n] [--device k] [--reference-ties] [--host]\n"
+            "  every selector of matutils-amd select (see select --help); with none, every leaf is a sample.  Then, as matUtils extract -N:\n"
+            "  -N, --minimum-subtrees-size  cover the samples by subtrees of the n nearest leaves of a sample [REQUIRED]: the samples are\n"
+            "                           walked in order, a sample already in an earlier subtree is skipped, and a sample with no ancestor of\n"
+            "                           more than n leaves gets none\n"
+            "  -t, --write-tree         write subtree i as <dir>/<name>-subtree-<i>.nw [REQUIRED], and <dir>/subtree-assignments.tsv with\n"
+            "                           the file of every sample\n"
+            "  -u, --used-samples       write a text file of the selected sample ids\n"
+            "      --reference-ties     order equal distances as the reference's std::sort does (host, slow)\n"
+            "      --host               run the selectors, get_nearby and get_subtree as the reference's walks on the host (slow)\n"
+            "  The neighbourhoods are searched in rounds of batched device calls and every round's subtrees are built by one batched call.\n"
+            "  -o, -v and -n are refused: the reference exits after the -N files, before it would write them.  -j is not supported.\n");
+}
+
+void step_ms(const char *what, bool host, double ms) {   // step_time for a step that runs in pieces
+    fprintf(stderr, "Selection step %s (%s): %.3f msec\n", what, host ? "host" : "device", ms);
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// get_nearby (select.cpp:206-276) on the host, statement by statement; nleaves: get_num_leaves of every node, counted once.
+std::vector<std::string> host_nearby(const NearestSearch &near, const std::unordered_map<const uh::Node *, size_t> &nleaves, uh::Node *node,
+                                     size_t k) {
+    uh::Node *last = node;
+    for (uh::Node *anc = node; anc; anc = anc->parent) {
+        if (nleaves.at(anc) <= k) { last = anc; continue; }
+        return near.literal(anc, last, k);   // the leaves of last_anc, then the nearest others up to k: never fewer than k
+    }
+    return {};
+}
+
+// The subtrees of one round's neighbourhoods from one ugp_subtree_batch call, each built as device_subtree builds its one (no owner
+// call: a newick file carries no annotations), and written as the reference streams them (convert.cpp:724-731: no newline).
+struct SubtreesWriter {
+    uh::Tree &T;
+    SelectDevice &D;
+    const std::string newick_n;
+    bool host, attached = false;
+    double build_ms = 0, write_ms = 0;
+    size_t written = 0;
+    SubtreesWriter(uh::Tree &t, SelectDevice &d, const std::string &n, bool h) : T(t), D(d), newick_n(n), host(h) {}
+    bool write(const uh::Tree &sub, std::string &err) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const std::string path = newick_n + "-subtree-" + std::to_string(written++) + ".nw";
+        std::ofstream f(path, std::ios::binary);
+        f << uh::newick(sub, sub.root, true, true);
+        f.close();
+        write_ms += ms_since(t0);
+        if (!f) { err = "could not write " + path; return false; }
+        return true;
+    }
+    bool run(const std::vector<std::vector<std::string>> &sets, std::string &err) {
+        if (sets.empty()) return true;
+        auto t0 = std::chrono::steady_clock::now();
+        if (host) {
+            for (const auto &set : sets) {
+                t0 = std::chrono::steady_clock::now();
+                uh::Tree sub;
+                if (!uh::get_subtree(T, set, sub, err)) return false;
+                build_ms += ms_since(t0);
+                if (!write(sub, err)) return false;
+            }
+            return true;
+        }
+        D.up();
+        if (!attached) {
+            const ugp_tree_desc desc = D.A.desc();
+            if (ugp_subtree_attach(D.h, &desc) != UGP_OK) lib_fail("ugp_subtree_attach");
+            attached = true;
+        }
+        const size_t n = sets.size();
+        std::vector<uint64_t> sel_off(n + 1, 0), koff(n + 1), eoff(n + 1);
+        std::vector<uint32_t> nodes;
+        for (size_t b = 0; b < n; b++) {
+            for (const std::string &s : sets[b]) {
+                const uh::Node *nd = T.get_node(s);
+                if (!nd) { err = "get_subtree: sample " + s + " is not in the tree"; return false; }
+                nodes.push_back(nd->flat_index);
+            }
+            sel_off[b + 1] = nodes.size();
+        }
+        std::vector<ugp_subtree_batch_info> info(n);
+        if (ugp_subtree_batch(D.h, n, sel_off.data(), nodes.data(), koff.data(), eoff.data(), info.data()) != UGP_OK) lib_fail("ugp_subtree_batch");
+        const uint64_t nk = koff[n], ne = eoff[n];
+        std::vector<uint32_t> kept(nk), kpar(nk), first(std::max<uint64_t>(ne, 1));
+        std::vector<uint64_t> off(nk + 1);
+        std::vector<int32_t> pos(std::max<uint64_t>(ne, 1));
+        std::vector<uint8_t> nuc(std::max<uint64_t>(ne, 1));
+        uint64_t got = 0;
+        if (ugp_subtree_batch_nodes(D.h, kept.data(), kpar.data(), off.data(), nk, &got) != UGP_OK) lib_fail("ugp_subtree_batch_nodes");
+        if (ugp_subtree_batch_entries(D.h, pos.data(), first.data(), nuc.data(), ne, &got) != UGP_OK) lib_fail("ugp_subtree_batch_entries");
+        off[nk] = ne;
+        build_ms += ms_since(t0);
+        std::vector<uh::Node *> made;
+        for (size_t b = 0; b < n; b++) {
+            t0 = std::chrono::steady_clock::now();
+            if (info[b].n_disagree)
+                fprintf(stderr, "WARNING: %llu consecutive mutations at one position disagree and are skipped (first below node %s)\n",
+                        (unsigned long long)info[b].n_disagree, D.A.bfs[info[b].first_disagree]->id.c_str());
+            uh::Tree sub;
+            const uint64_t k0 = koff[b], k1 = koff[b + 1];
+            made.assign(k1 - k0, nullptr);
+            for (uint64_t k = k0; k < k1; k++) {
+                const uh::Node *src = D.A.bfs[kept[k]];
+                uh::Node *nn = sub.create_node(src->id, kpar[k] == UINT32_MAX ? nullptr : made[kpar[k]], -1.0f);
+                if (!nn) { err = "get_subtree: duplicate node " + src->id; return false; }
+                nn->mutations.reserve(off[k + 1] - off[k]);
+                for (uint64_t e = off[k]; e < off[k + 1]; e++) {
+                    uh::Mutation m = *D.A.ent[first[e]];
+                    m.mut_nuc = (int8_t)nuc[e];
+                    nn->mutations.push_back(m);
+                }
+                made[k - k0] = nn;
+            }
+            build_ms += ms_since(t0);
+            if (!write(sub, err)) return false;
+        }
+        return true;
+    }
+};
+
+// The round size of the cover: the searches of one round fill round * n slots of a node and a distance (8 bytes): 2^22 slots, 32 MiB.
+size_t subtrees_round(size_t n) { return std::max<size_t>(1, (size_t(1) << 22) / n); }
+
+// get_minimum_subtrees (convert.cpp:665-798) for -t: the cover loop :681-711 in rounds -- the next `round` samples not yet seen are
+// searched as one batch, and their answers are applied in order, dropping those that an earlier one of the round made seen (the
+// sequential loop would not have searched them) -- then the files :713-797.
+int minimum_subtrees(uh::Tree &T, const std::vector<std::string> &samples, size_t size, const std::string &prefix, const std::string &ftree,
+                     NearestSearch &near, SelectDevice &D, bool host, size_t round) {
+    fprintf(stderr, "Finding minimum covering sample subtrees.\n");
+    const auto t_all = std::chrono::steady_clock::now();
+    const std::string newick_n = prefix + ftree;
+    std::unordered_map<std::string, long> seen;   // samples_we_have_seen: the first subtree that holds a sample, or -1
+    std::unordered_map<const uh::Node *, size_t> nleaves;
+    if (host) {
+        const std::vector<uh::Node *> dfs = T.dfs();
+        for (size_t i = dfs.size(); i-- > 0;) {
+            size_t &c = nleaves[dfs[i]];
+            if (dfs[i]->is_leaf()) c = 1;
+            const size_t mine = c;
+            if (dfs[i]->parent) nleaves[dfs[i]->parent] += mine;
+        }
+    }
+    if (!round) round = subtrees_round(size);
+    SubtreesWriter W(T, D, newick_n, host);
+    std::string err;
+    double cover_ms = 0;
+    size_t n_sets = 0, rounds = 0;
+    for (size_t i = 0; i < samples.size();) {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<size_t> idx;
+        std::vector<uh::Node *> qs;
+        size_t j = i;
+        for (; j < samples.size() && idx.size() < round; j++) {
+            if (seen.count(samples[j])) continue;
+            idx.push_back(j);
+            qs.push_back(must_get(T, samples[j]));
+        }
+        std::vector<std::vector<std::string>> found;
+        if (!host) {
+            D.up();
+            near.share(D.h, D.A);   // one handle for the searches and the subtrees
+            found = near.run(qs, size);
+        }
+        std::vector<std::vector<std::string>> sets;
+        for (size_t q = 0; q < idx.size(); q++) {
+            const std::string &s = samples[idx[q]];
+            if (seen.count(s)) continue;
+            std::vector<std::string> keep = host ? host_nearby(near, nleaves, qs[q], size) : std::move(found[q]);
+            if (keep.empty()) { seen.emplace(s, -1); continue; }
+            for (const std::string &l : keep) seen.emplace(l, (long)(n_sets + sets.size()));   // insert: the first subtree owns a sample
+            sets.push_back(std::move(keep));
+        }
+        cover_ms += ms_since(t0);
+        if (!W.run(sets, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+        n_sets += sets.size();
+        rounds++;
+        i = j;
+    }
+    step_ms("cover", host, cover_ms);
+    step_ms("subtrees", host, W.build_ms);
+    fprintf(stderr, "%zu subtrees of %zu samples in %zu rounds; newick files: %.3f msec\n", n_sets, samples.size(), rounds, W.write_ms);
+    const std::string tsv = prefix + "subtree-assignments.tsv";
+    std::ofstream tracker(tsv, std::ios::binary);
+    tracker << "samples\tnewick_file\n";   // no metadata can be loaded here: no further columns
+    for (const std::string &s : samples) {
+        const auto it = seen.find(s);
+        const long v = it == seen.end() ? 0 : it->second;   // the reference's operator[] makes a 0 for a sample no subtree holds
+        if (v == -1) continue;
+        tracker << s << "\t" << newick_n << "-subtree-" << v << ".nw\n";
+    }
+    tracker.close();
+    if (!tracker) { fprintf(stderr, "ERROR: could not write %s\n", tsv.c_str()); return 1; }
+    fprintf(stderr, "Minimum subtree files written in %.0f msec; exiting\n", ms_since(t_all));
+    return 0;
+}
+
+enum { kExtract = 0, kSelect = 1, kSubtree = 2, kSubtrees = 3 };
 
 // extract_main, extract.cpp:149-640, 867-888 for the options of extract_usage; kSelect: the subcommand `select`, which adds the
 // selectors; kSubtree: `subtree`, which is select with the induced subtree built on the device
@@ -1698,7 +1915,9 @@ int extract_or_select(int argc, char **argv, int mode) {
     bool reference_ties = false, no_genotypes = false, host_genotypes = false;
     SelectOpts S;
     S.on = sel;
-    void (*const show_usage)(FILE *) = mode == kSubtree ? subtree_usage : sel ? select_usage : extract_usage;
+    const bool many = mode == kSubtrees;
+    long min_subtrees = 0, round_size = 0;
+    void (*const show_usage)(FILE *) = many ? subtrees_usage : mode == kSubtree ? subtree_usage : sel ? select_usage : extract_usage;
     static const char *const unsupported[] = {
         "-K", "--nearest-k-batch", "-j", "--write-json", "-c", "--clade", "-m", "--mutation", "-H", "--match",
         "-V", "--closest-relatives", "-q", "--break-ties", "--within-distance", "--distance-threshold", "-z", "--set-size", "-W", "--add-random",
@@ -1728,6 +1947,13 @@ int extract_or_select(int argc, char **argv, int mode) {
         long v = 0;
         bool ok = true;
         if (a == "-i" || a == "--input-mat") ok = val(in_mat);
+        else if (many && (a == "-N" || a == "--minimum-subtrees-size")) ok = ival(min_subtrees);
+        else if (many && a == "--round-size") ok = ival(round_size);   // (undocumented: the samples searched per round of the cover)
+        else if (many && (a == "-o" || a == "--write-mat" || a == "-v" || a == "--write-vcf" || a == "-n" || a == "--no-genotypes")) {
+            fprintf(stderr, "ERROR: %s is not written by matutils-amd subtrees: the reference exits after the -N files, before it would write it "
+                            "(extract.cpp:723-730)\n", a.c_str());
+            return 1;
+        }
         else if (a == "-s" || a == "--samples") ok = val(fsamples);
         else if (a == "-k" || a == "--nearest-k") ok = val(nearest_k);
         else if (a == "-Y" || a == "--select-nearest") { ok = ival(v); if (ok && v < 0) { fprintf(stderr, "ERROR: bad value %ld for %s\n", v, a.c_str()); return 1; } select_nearest = (size_t)v; }
@@ -1766,6 +1992,16 @@ int extract_or_select(int argc, char **argv, int mode) {
         if (!ok) return 1;
     }
     if (in_mat.empty()) { fprintf(stderr, "ERROR: the option '--input-mat' is required but missing\n"); show_usage(stderr); return 1; }
+    if (many && min_subtrees <= 0) {
+        fprintf(stderr, "ERROR: matutils-amd subtrees needs -N/--minimum-subtrees-size with a size above 0\n");
+        show_usage(stderr);
+        return 1;
+    }
+    if (many && ftree.empty()) {   // convert.cpp:668-671 (-j is not supported here)
+        fprintf(stderr, "ERROR: Either JSON (-j) or Newick (-t) output must be requested alongside -N.");
+        return 1;
+    }
+    if (many && round_size < 0) { fprintf(stderr, "ERROR: bad value %ld for --round-size\n", round_size); return 1; }
     struct stat sb;
     if (stat(dir.c_str(), &sb) != 0) {
         fprintf(stderr, "Creating output directory.\n\n");
@@ -1816,7 +2052,7 @@ int extract_or_select(int argc, char **argv, int mode) {
             samples = inter;
         }
     }
-    SelectDevice seldev(T, device, mode == kSubtree ? (unsigned)uh::TreeArrays::kEntries : 0u);
+    SelectDevice seldev(T, device, mode == kSubtree || many ? (unsigned)uh::TreeArrays::kEntries : 0u);
     if (sel && !select_before_filters(T, S, seldev, samples)) return 1;
     if (max_parsimony >= 0) { samples = get_parsimony_samples(T, samples, max_parsimony); if (samples.empty()) { fputs(none, stderr); return 1; } }
     if (max_branch >= 0) { samples = get_short_steppers(T, samples, max_branch); if (samples.empty()) { fputs(none, stderr); return 1; } }
@@ -1832,6 +2068,19 @@ int extract_or_select(int argc, char **argv, int mode) {
         for (const uh::Node *n : T.dfs()) if (set.count(n->id)) samples.push_back(n->id);
     }
     if (sel && !select_prune(T, S, seldev, samples)) return 1;
+    if (many) {   // :591-598 (every leaf), -u, then :723-730; the subtree of the whole selection is built there and never used
+        if (samples.empty()) {
+            fprintf(stderr, "No sample selection arguments passed; using full input tree for further output.\n");
+            samples = leaf_ids(T);
+        }
+        if (!fused.empty()) {
+            fprintf(stderr, "Dumping selected samples to file...\n");
+            std::ofstream f(prefix + fused, std::ios::binary);
+            for (const std::string &s : samples) f << s << "\n";
+            if (!f) { fprintf(stderr, "ERROR: could not write %s\n", (prefix + fused).c_str()); return 1; }
+        }
+        return minimum_subtrees(T, samples, (size_t)min_subtrees, prefix, ftree, near, seldev, S.host, (size_t)round_size);
+    }
     // :590-606: nothing selected = the whole tree
     uh::Tree sub;
     uh::Tree *out = &T;
@@ -1873,6 +2122,7 @@ int extract_or_select(int argc, char **argv, int mode) {
 int extract(int argc, char **argv) { return extract_or_select(argc, argv, kExtract); }
 int select_samples(int argc, char **argv) { return extract_or_select(argc, argv, kSelect); }
 int subtree(int argc, char **argv) { return extract_or_select(argc, argv, kSubtree); }
+int subtrees(int argc, char **argv) { return extract_or_select(argc, argv, kSubtrees); }
 
 // ---- summary (summary.cpp) ----------------------------------------------------------------------------------------
 
@@ -3390,8 +3640,9 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "relatives")) return relatives(argc - 2, argv + 2);
     if (!strcmp(argv[1], "select")) return select_samples(argc - 2, argv + 2);
     if (!strcmp(argv[1], "subtree")) return subtree(argc - 2, argv + 2);
+    if (!strcmp(argv[1], "subtrees")) return subtrees(argc - 2, argv + 2);
     if (!strcmp(argv[1], "mask")) return mask(argc - 2, argv + 2);
     if (!strcmp(argv[1], "haplotypes")) return haplotypes(argc - 2, argv + 2);
-    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate, extract, subtree, summarize, haplotypes, translate, relatives, select, mask)\n", argv[1]);
+    fprintf(stderr, "ERROR: unsupported matUtils subcommand '%s' (matutils-amd runs: uncertainty, annotate, extract, subtree, subtrees, summarize, haplotypes, translate, relatives, select, mask)\n", argv[1]);
     return 1;
 }

@@ -2098,6 +2098,35 @@ int ugp_subtree_time(ugp_mat *m, uint64_t n, const uint32_t *nodes_bfs, uint32_t
     return ugp::sub_time(m->sub, n, nodes_bfs, reps, nodes_ms, merge_ms);
 }
 
+// ---- many induced subtrees in one call (ugp_subtree_batch.hip) ----------------------------------------------------------
+
+int ugp_subtree_batch_chunked(ugp_mat *m, uint64_t n_sel, const uint64_t *sel_off, const uint32_t *nodes_bfs, uint64_t *kept_off,
+                              uint64_t *entry_off, ugp_subtree_batch_info *info, uint64_t group_positions, uint64_t chunk_items) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sub_batch(m->sub, n_sel, sel_off, nodes_bfs, kept_off, entry_off, info, group_positions, chunk_items);
+}
+
+int ugp_subtree_batch(ugp_mat *m, uint64_t n_sel, const uint64_t *sel_off, const uint32_t *nodes_bfs, uint64_t *kept_off, uint64_t *entry_off,
+                      ugp_subtree_batch_info *info) {
+    return ugp_subtree_batch_chunked(m, n_sel, sel_off, nodes_bfs, kept_off, entry_off, info, 0, 0);
+}
+
+int ugp_subtree_batch_nodes(ugp_mat *m, uint32_t *kept_bfs, uint32_t *kept_parent, uint64_t *ent_off, uint64_t cap, uint64_t *n_out) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sub_batch_nodes(m->sub, kept_bfs, kept_parent, ent_off, cap, n_out);
+}
+
+int ugp_subtree_batch_entries(ugp_mat *m, int32_t *pos, uint32_t *first_entry, uint8_t *nuc, uint64_t cap, uint64_t *n_out) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sub_batch_entries(m->sub, pos, first_entry, nuc, cap, n_out);
+}
+
+int ugp_subtree_batch_time(ugp_mat *m, uint64_t n_sel, const uint64_t *sel_off, const uint32_t *nodes_bfs, uint32_t reps, double *nodes_ms,
+                           double *merge_ms) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    return ugp::sub_batch_time(m->sub, n_sel, sel_off, nodes_bfs, reps, nodes_ms, merge_ms);
+}
+
 // ---- matUtils extract -v: genotypes of a selection (ugp_genotypes.hip) -------------------------------------------------
 
 int ugp_genotypes_attach(ugp_mat *m, const ugp_tree_desc *tree) {

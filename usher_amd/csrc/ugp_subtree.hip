@@ -25,6 +25,7 @@
 
 #include "ugp_sort.hpp"
 #include "ugp_subtree.hpp"
+#include "ugp_subtree_state.hpp"
 
 namespace ugp {
 namespace {
@@ -139,22 +140,6 @@ __global__ void __launch_bounds__(kBlock) k_sub_owner(DfsView t, uint32_t nn, co
 }
 
 }  // namespace
-
-struct SubState {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    const DfsTables *T = nullptr;                 // the handle's
-    const std::vector<uint32_t> *dfs2bfs = nullptr;
-    DBuf<uint8_t> mpn;                            // per depth-first entry: stored parent allele << 4 | allele
-    DBuf<uint32_t> at, seg, sb, kb, kdfs, kpar, eb, vin, vout, sv, sfirst, ofirst, eoff, qat, qown;
-    DBuf<uint8_t> sel, kept, eflag, surv, snuc, onuc;
-    DBuf<u64> kin, kout, ctr;
-    DBuf<int32_t> opos;
-    DBuf<unsigned char> tmp;
-    bool have = false;                            // the buffers hold a selection's answer
-    uint32_t nk = 0, G = 0, E = 0;                // kept nodes, gathered entries, merged entries
-    ~SubState() { if (stream) (void)hipStreamDestroy(stream); }
-};
 
 void sub_free(SubState *s) {
     if (!s) return;

@@ -24,5 +24,12 @@ int sub_nodes(SubState *s, uint64_t n, const uint32_t *nodes_bfs, uint32_t *kept
 int sub_entries(SubState *s, int32_t *pos, uint32_t *first_entry, uint8_t *nuc, uint64_t cap, uint64_t *n_out);
 int sub_owner(SubState *s, uint64_t n, const uint32_t *nodes_bfs, uint32_t *owner);
 int sub_time(SubState *s, uint64_t n, const uint32_t *nodes_bfs, uint32_t reps, double *nodes_ms, double *merge_ms);
+// ugp_subtree_batch.hip: as ugp_subtree_batch_chunked / _nodes / _entries / _time document them; 0 is either default.
+int sub_batch(SubState *s, uint64_t n_sel, const uint64_t *sel_off, const uint32_t *nodes_bfs, uint64_t *kept_off, uint64_t *entry_off,
+              ugp_subtree_batch_info *info, uint64_t group_positions, uint64_t chunk_items);
+int sub_batch_nodes(SubState *s, uint32_t *kept_bfs, uint32_t *kept_parent, uint64_t *ent_off, uint64_t cap, uint64_t *n_out);
+int sub_batch_entries(SubState *s, int32_t *pos, uint32_t *first_entry, uint8_t *nuc, uint64_t cap, uint64_t *n_out);
+int sub_batch_time(SubState *s, uint64_t n_sel, const uint64_t *sel_off, const uint32_t *nodes_bfs, uint32_t reps, double *nodes_ms,
+                   double *merge_ms);
 
 }  // namespace ugp

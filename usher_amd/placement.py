@@ -837,6 +837,57 @@ class Placer:
         self._ck(self._L.ugp_subtree_time(self._h, len(nodes), _ptr(nodes) if len(nodes) else None, int(reps), C.byref(a), C.byref(b)))
         return float(a.value), float(b.value)
 
+    # ---- many induced subtrees in one call (ugp_subtree_batch*) -------------------------------------------------------------------------
+    SUB_BATCH_INFO = np.dtype([("n_selected", np.uint64), ("n_kept", np.uint64), ("n_entries", np.uint64), ("n_gathered", np.uint64),
+                               ("n_disagree", np.uint64), ("longest_chain", np.uint64), ("first_disagree", np.uint32), ("lca", np.uint32)])
+
+    @staticmethod
+    def _selections(selections):
+        sels = [np.ascontiguousarray(s, dtype=np.uint32).ravel() for s in selections]
+        off = np.zeros(len(sels) + 1, np.uint64)
+        off[1:] = np.cumsum([len(s) for s in sels], dtype=np.uint64)
+        flat = np.concatenate(sels) if sels else np.zeros(0, np.uint32)
+        return off, np.ascontiguousarray(flat, dtype=np.uint32)
+
+    def subtree_batch(self, selections, group_positions: int = 0, chunk_items: int = 0):
+        """get_subtree for every selection (lists of BFS indices) in one call: per selection the dict subtree_nodes returns, its kept
+        nodes, parents and offsets sliced out of the batch's lists and rebased to the slice, and info a SUB_BATCH_INFO scalar.
+        group_positions / chunk_items (test hooks): window positions per group, items per launch window; 0: the defaults."""
+        off, flat = self._selections(selections)
+        ns = len(off) - 1
+        koff, eoff = np.zeros(ns + 1, np.uint64), np.zeros(ns + 1, np.uint64)
+        info = np.zeros(max(ns, 1), self.SUB_BATCH_INFO)
+        self._ck(self._L.ugp_subtree_batch_chunked(self._h, ns, _ptr(off), _ptr(flat) if len(flat) else None, _ptr(koff), _ptr(eoff), _ptr(info),
+                                                   int(group_positions), int(chunk_items)))
+        nk, ne = int(koff[ns]), int(eoff[ns])
+        kept, par, ent = np.zeros(nk, np.uint32), np.zeros(nk, np.uint32), np.zeros(nk + 1, np.uint64)
+        n_out = C.c_uint64(0)
+        self._ck(self._L.ugp_subtree_batch_nodes(self._h, _ptr(kept) if nk else None, _ptr(par) if nk else None, _ptr(ent) if nk else None, nk,
+                                                 C.byref(n_out)))
+        if int(n_out.value) != nk:
+            raise UgpError(-1, "ugp_subtree_batch_nodes and ugp_subtree_batch disagree on the number of kept nodes")
+        ent[nk] = ne
+        pos, first, nuc = np.zeros(ne, np.int32), np.zeros(ne, np.uint32), np.zeros(ne, np.uint8)
+        self._ck(self._L.ugp_subtree_batch_entries(self._h, _ptr(pos) if ne else None, _ptr(first) if ne else None, _ptr(nuc) if ne else None, ne,
+                                                   C.byref(n_out)))
+        if int(n_out.value) != ne:
+            raise UgpError(-1, "ugp_subtree_batch_entries and ugp_subtree_batch disagree on the number of merged entries")
+        out = []
+        for b in range(ns):
+            k0, k1, e0, e1 = int(koff[b]), int(koff[b + 1]), int(eoff[b]), int(eoff[b + 1])
+            out.append({"kept": kept[k0:k1].copy(), "parent": par[k0:k1].copy(), "ent_off": ent[k0:k1 + 1] - np.uint64(e0),
+                        "pos": pos[e0:e1].copy(), "first_entry": first[e0:e1].copy(), "nuc": nuc[e0:e1].copy(), "info": info[b].copy(),
+                        "n_kept": k1 - k0, "n_entries": e1 - e0})
+        return out
+
+    def subtree_batch_time(self, selections, reps: int = 5):
+        """Bench hook: (nodes_ms, merge_ms), milliseconds of device time of the passes alone for the batch, summed over its groups."""
+        off, flat = self._selections(selections)
+        a, b = C.c_double(0), C.c_double(0)
+        self._ck(self._L.ugp_subtree_batch_time(self._h, len(off) - 1, _ptr(off), _ptr(flat) if len(flat) else None, int(reps), C.byref(a),
+                                                C.byref(b)))
+        return float(a.value), float(b.value)
+
     # ---- matUtils summary --haplotype (ugp_haplotypes_attach / ugp_haplotype_groups / _sets) --------------------------------------
     HP_GROUP = np.dtype([("leaf", np.uint32), ("count", np.uint32), ("size", np.uint32), ("pad", np.uint32)])
     HP_INFO = np.dtype([("n_leaves", np.uint64), ("n_groups", np.uint64), ("n_collisions", np.uint64), ("n_duplicate", np.uint64),
