@@ -220,13 +220,16 @@ int ugp_place_batch_prepared(ugp_mat *mat, const ugp_queries *q, const ugp_ex *e
  *   nsize[i]     = get_neighborhood_size (:41-130) over the WHOLE tie set when num_best > 1, else 0 -- never depends on cap.
  * Every pair is scored (dense; exact for the literal row order, which ugp_place_batch_ex cannot take).  The tables come from
  * ugp_uncertainty_attach, once per handle: `tree` must be the tree the handle was created from (same parent array; the arrays
- * are copied and may be freed).  A tree with two non-masked mutations at one position on one branch is UGP_ERR_UNSUPPORTED. */
+ * are copied and may be freed).  A tree with two non-masked mutations at one position on one branch is UGP_ERR_UNSUPPORTED.
+ * The handle's depth-first tables are shared as ugp_genotypes_attach describes: when another attach has built them, `tree` must
+ * carry the mutation arrays of that attach (UGP_ERR_INVALID otherwise, nothing changed).  A later attach replaces the tables. */
 int ugp_uncertainty_attach(ugp_mat *mat, const ugp_tree_desc *tree);
 int ugp_uncertainty(ugp_mat *mat, const uint32_t *nodes /* BFS */, uint64_t n, uint32_t cap, uint32_t *epps, uint32_t *nsize,
                     uint32_t *tie_dfs /* [n * cap] */, uint32_t *tie_count);
 /* matUtils annotate (annotate.cpp:301-419, 466-481, 611-638).  ugp_annotate_attach makes the depth-first tables of `tree` once per
- * handle (the handle's tree: same parent array; arrays are copied).  Clades are CSR lists of exemplar nodes (BFS indices);
- * an exemplar listed twice counts twice, as in the reference.
+ * handle (the handle's tree: same parent array; arrays are copied); they are shared as ugp_genotypes_attach describes: when
+ * another attach has built them, `tree` must carry the mutation arrays of that attach (UGP_ERR_INVALID otherwise, nothing
+ * changed).  Clades are CSR lists of exemplar nodes (BFS indices); an exemplar listed twice counts twice, as in the reference.
  * ugp_clade_alleles: for each clade, every mutation entry (its index in tree->mut_off's CSR) that the reference's walk
  *   rsearch(exemplar, true) adds (:355-390) -- the first non-masked entry of a position wins (later ones on the same node and
  *   older ones above are skipped), masked entries always count, entries with ref == mut count nothing -- and how many of the
@@ -250,6 +253,8 @@ int ugp_annotate_search(ugp_mat *mat, const ugp_queries *q, uint32_t cap, int32_
                         uint32_t *tie_count /* [n_queries] */);
 /* matUtils extract's "k nearest samples" (get_nearby, matUtils/select.cpp:206-276) for a batch of queries.  ugp_nearest_attach makes
  * the depth-first tables of `tree` (the handle's tree: same parent array; arrays are copied) and a leaf prefix table, once per handle.
+ * The depth-first tables are shared as ugp_genotypes_attach describes: when another attach has built them, `tree` must carry the
+ * mutation arrays of that attach (UGP_ERR_INVALID otherwise, nothing changed).
  * ugp_nearest_k: query i is a node (BFS index; any node, not only a leaf) and its own k[i] > 0.  As the reference: climbing from the
  * node itself, last_anc is the last ancestor with <= k leaves (the node to begin with) and anc the first with more; the result is
  * the leaves of last_anc in depth-first order, then the leaves under anc that are not strict descendants of last_anc (is_ancestor
@@ -279,8 +284,9 @@ int ugp_nearest_k_chunked(ugp_mat *mat, uint64_t n_queries, const uint32_t *node
 /* matUtils extract -v (make_vcf / r_add_genotypes, matUtils/convert.cpp:53-292): the VCF site table and genotype codes of a selection
  * of nodes.  ugp_genotypes_attach shares the depth-first tables of `tree` (the handle's tree; arrays are copied; mut_par is needed,
  * and mut_nuc / mut_par of non-masked mutations must lie in 1 .. 15, UGP_ERR_UNSUPPORTED otherwise), once per handle.
- * The handle's depth-first tables are shared with the uncertainty, annotate and nearest attaches and are built by the first of them: when
- * they exist, `tree` must carry the mutation arrays they were built from (compared entry by entry; UGP_ERR_INVALID otherwise, nothing
+ * The handle's depth-first tables are shared by every dense attach (uncertainty, annotate, nearest, relatives, select, mask, subtree,
+ * genotypes, summary, translate, haplotypes) and are built by the first of them: when they exist, EVERY one of these attaches checks
+ * that `tree` carries the mutation arrays they were built from (compared entry by entry; UGP_ERR_INVALID otherwise, nothing
  * changed) -- a handle takes one set of mutation arrays for its whole life.
  * ugp_genotype_select: the selection is a set of nodes (BFS indices; any node; one given twice counts once; NULL or n = 0: all
  * leaves).  Columns are the selected nodes in depth-first order.  Masked mutations (mut_pos < 0) are skipped everywhere.  At a

@@ -65,3 +65,16 @@ def tie_tree():
     arrays = from_spec((0, [(2, leaves(200) + [(0, leaves(20))] + leaves(280))] + leaves(30, 3)))
     s = int(np.flatnonzero(arrays["parent"] == 1)[200])
     return arrays, int(np.flatnonzero(arrays["parent"] == s)[7])
+
+
+SORT_LDS = 4096   # pairs the sort of one query's candidates takes in LDS; more go through a global scratch
+
+
+def sort_tree(L=8300, spare=4):
+    """A root with a polytomy P of L leaves and `spare` more leaves.  Leaf i of P has (L - i) % 64 + 1 entries, so in depth-first
+    order the keys fall and wrap: the compaction hands the sort an unsorted list with long runs of ties, and a sort that passed its
+    input through would fail.  About 32.5 * L entries.  Returns (arrays, the first leaf of P, P): from that leaf every k < L has
+    last_anc = the leaf itself, one leaf held, and need = k - 1 candidates to order -- the leaf among them (is_ancestor starts at the
+    parent)."""
+    arrays = from_spec((0, [(2, [(L - i) % 64 + 1 for i in range(L)])] + leaves(spare, 3)))
+    return arrays, spare + 2, 1   # breadth-first: root 0, P 1, the spare leaves, P's children from spare + 2

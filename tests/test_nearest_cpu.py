@@ -105,3 +105,22 @@ def _extract(*args):
 def test_extract_argument_errors(args, msg, tmp_path):
     r = _extract(*(args + ["-d", str(tmp_path)]))
     assert r.returncode != 0 and msg in r.stderr, (r.returncode, r.stderr[-500:])
+
+
+@pytest.mark.parametrize("L", [70, 131])
+def test_sort_tree_is_what_the_size_edges_need(L):
+    """The generator of the sort's size edges at a size the per-leaf walk takes: every need from 1 to L - 2, the numpy restatement
+    against the literal one, and the shape the device test relies on."""
+    arrays, q, P = NC.sort_tree(L)
+    T, F = R.Tree(arrays), R.Fast(arrays)
+    assert int(T.nleaves[P]) == L and int(T.par[q]) == P and not T.kids[q]
+    keys = [int(T.nmut[c]) for c in T.kids[P]]
+    assert keys == [(L - i) % 64 + 1 for i in range(L)] and keys != sorted(keys) and len(set(keys)) == min(L, 64)   # unsorted, with ties
+    for need in range(1, L - 1):
+        want = F.query(q, need + 1)
+        assert want == R.literal(T, q, need + 1), need
+        assert (want["anc"], want["last_anc"], want["count"]) == (P, q, need + 1) and want["nodes"][0] == q
+        assert want["dist"][1:] == sorted(keys)[:need]                      # the need smallest keys, the leaf's own among them
+        if keys[0] < want["cut_dist"]:                                      # a candidate of its own search: listed twice
+            assert want["nodes"].count(q) == 2
+    assert F.query(q, L)["anc"] == 0                                        # one more climbs past P

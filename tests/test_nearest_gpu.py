@@ -95,6 +95,31 @@ def test_segment_edges():
     assert infos[-4]["count"] == len(in_c2) and infos[-1]["count"] > max(ks)
 
 
+SORT_NEEDS = (1, 2, 3, 4, 5, NC.SORT_LDS - 1, NC.SORT_LDS, NC.SORT_LDS + 1, 2 * NC.SORT_LDS - 1, 2 * NC.SORT_LDS, 2 * NC.SORT_LDS + 1)
+
+
+def test_sort_size_edges():
+    """The sort of one query's candidates at the edges of its two paths: 4096 pairs in LDS and the same network over a global
+    scratch for more, padded to a power of two (a pad of one slot at 4095 and 8191, none at 4096 and 8192, the next power at 4097
+    and 8193).  The keys come unsorted and with ties (NC.sort_tree).  A second call puts the LDS queries between the global ones, so
+    that scratch ranges of different padded length lie side by side in one chunk."""
+    arrays, q, P = NC.sort_tree()
+    F = R.Fast(arrays)
+    want = {need: F.query(q, need + 1) for need in SORT_NEEDS}
+    assert all(w["anc"] == P and w["last_anc"] == q and w["count"] == need + 1 for need, w in want.items())
+    mixed = (8193, 3, 4097, 1, 4096, 8192, 2, 4095, 8191, 5, 4)
+    assert sorted(mixed) == sorted(SORT_NEEDS)
+    pl = Placer(arrays)
+    for needs in (SORT_NEEDS, mixed):
+        ks = np.array(needs, np.uint32) + 1
+        for chunk in (1, 3, 0):
+            got = pl.nearest_k(np.full(len(needs), q), ks, chunk_queries=chunk)
+            assert got[0].shape == (len(needs), max(SORT_NEEDS) + 1)
+            for i, need in enumerate(needs):
+                R.check(got, want[need], i)
+    pl.close()
+
+
 def test_digit_edges():
     arrays, q, n_p = NC.digit_tree()
     infos = _run(arrays, np.full(n_p + 3, q), np.arange(1, n_p + 4), literal_every=1)

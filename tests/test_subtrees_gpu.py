@@ -2,7 +2,6 @@
 --reference-ties, with a neighbourhood size per fixture at which Placer.nearest_k says that every sample's nearest set is unique (the
 n_at_cut rule of ugp_nearest_k), so that no query needs leaving out; on a random tree with --reference-ties on both sides; and with
 the cover's round size forced small, so that one run crosses several rounds."""
-import ctypes as C
 import os
 import types
 
@@ -16,7 +15,6 @@ from tests import synth
 from tests import test_subtree_cpu as CPU
 from tests import test_subtrees_cpu as TC
 from usher_amd import Placer
-from usher_amd.placement import _TreeArrays
 
 pytestmark = pytest.mark.gpu
 
@@ -38,9 +36,7 @@ def both(tmp_path, tag, pb, opts, device=(), host=("--host",)):
 
 def every_set_is_unique(arrays, nodes, n):
     pl = Placer(SMC.topology(arrays))   # the handle takes the bare topology, the nearest tables the entries as they are stored
-    full = _TreeArrays(arrays)
-    pl._ck(pl._L.ugp_nearest_attach(pl._h, C.byref(full.desc)))
-    pl._near_ready = True
+    pl.nearest_attach(arrays)
     out, dist, info = pl.nearest_k(np.asarray(nodes, np.uint32), n)
     pl.close()
     nleaves = NR.Tree(arrays).nleaves

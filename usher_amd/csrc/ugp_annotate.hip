@@ -211,6 +211,9 @@ int ann_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, 
     if (!out) return set_error(UGP_ERR_INVALID, "null argument");
     const int rc = dfs_tables(tree, dfs2bfs, bfs2dfs, device, 31, tables);
     if (rc) return rc;
+    try {
+        if (int same = dfs_tables_same_arrays(**tables, tree, dfs2bfs, "ugp_annotate_attach")) return same;
+    } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }
     AnnState *S = new (std::nothrow) AnnState();
     if (!S) return set_error(UGP_ERR_NOMEM, "out of host memory");
     S->device = device;

@@ -18,8 +18,9 @@ int dfs_tables_same_arrays(const DfsTables &T, const ugp_tree_desc *tree, const 
     const uint64_t M = tree->mut_off[tree->n_nodes];
     if (T.m != M || T.n != tree->n_nodes) return set_error(UGP_ERR_INVALID, other);
     if (hipSetDevice(T.device) != hipSuccess) return set_error(UGP_ERR_HIP, "hipSetDevice failed");
-    std::vector<uint32_t> morig(M), mbits(M);
+    std::vector<uint32_t> morig(M), mbits(M), moff((size_t)T.n + 1);
     std::vector<int32_t> mpos(M);
+    UGP_HIP_TRY(hipMemcpy(moff.data(), T.moff.p, moff.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (M) {
         UGP_HIP_TRY(hipMemcpy(morig.data(), T.morig.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost));
         UGP_HIP_TRY(hipMemcpy(mbits.data(), T.mbits.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -29,6 +30,7 @@ int dfs_tables_same_arrays(const DfsTables &T, const ugp_tree_desc *tree, const 
     bool same = true;
     for (uint64_t i = 0; i < T.n && same; i++) {
         const uint32_t b = dfs2bfs[i];
+        same = moff[i] == e;   // the same entries on other nodes are other arrays: an entry moved to the next node keeps the flat order
         for (uint64_t k = tree->mut_off[b]; k < tree->mut_off[b + 1] && same; k++, e++)
             same = e < M && morig[e] == k && mpos[e] == tree->mut_pos[k] &&
                    (mbits[e] & 0xffffu) == ((uint32_t)tree->mut_nuc[k] | (uint32_t)tree->mut_ref[k] << 8);

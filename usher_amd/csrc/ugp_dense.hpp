@@ -129,7 +129,8 @@ int dfs_tables(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, 
                int entry_bits, DfsTables **tables);
 void dfs_tables_free(DfsTables *t);
 // The handle's tables may be older than the attach that reads the caller's arrays THROUGH them (morig, pent): UGP_OK when `t` was
-// built from exactly the mutation arrays of `tree` (compared entry by entry), else UGP_ERR_INVALID naming the call `who`.
+// built from exactly the mutation arrays of `tree` (compared entry by entry, and each node's first entry with its offset: the same
+// entries on other nodes are other arrays), else UGP_ERR_INVALID naming the call `who`.  Every dense attach calls it.
 int dfs_tables_same_arrays(const DfsTables &t, const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const char *who);
 
 // The leaf-rank ranges select and mask read: leaf r is the r-th leaf in depth-first order, lbefore[i] ([n + 1]) the leaves in front of

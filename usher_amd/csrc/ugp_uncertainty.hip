@@ -261,6 +261,9 @@ int unc_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, 
     if (!out) return set_error(UGP_ERR_INVALID, "null argument");
     const int rc = dfs_tables(tree, dfs2bfs, bfs2dfs, device, 32, tables);
     if (rc) return rc;
+    try {
+        if (int same = dfs_tables_same_arrays(**tables, tree, dfs2bfs, "ugp_uncertainty_attach")) return same;
+    } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }
     if (!(*tables)->literal_ok) return set_error(UGP_ERR_UNSUPPORTED, "two mutations at one position on one branch");
     UncState *S = new (std::nothrow) UncState();
     if (!S) return set_error(UGP_ERR_NOMEM, "out of host memory");

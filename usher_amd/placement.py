@@ -266,13 +266,20 @@ class Placer:
         self._ck(self._L.ugp_place_batch_prepared(self._h, C.byref(batch.desc), ex, None if sk is None else _ptr(sk), _ptr(out), C.c_void_p(d_scores) if d_scores else None))
         return out
 
+    def uncertainty_attach(self, arrays: Optional[Dict] = None):
+        """ugp_uncertainty_attach with the placer's own tree, or with other mutation arrays on the same topology (masked entries,
+        ambiguous alleles: trees the placement tables refuse).  The depth-first tables are shared as genotypes_attach describes."""
+        t = self._t if arrays is None else _TreeArrays(arrays)
+        self._ck(self._L.ugp_uncertainty_attach(self._h, C.byref(t.desc)))
+        self._unc_ready = True
+
     def uncertainty(self, nodes, cap: int = 64):
         """matUtils uncertainty (ugp_uncertainty) for tree nodes given by BFS index: (epps, neighborhood_size, ties, tie_count),
         ties[i] = the first min(cap, tie_count[i]) tied nodes as depth-first positions, ascending.  The tables are made on
-        the first call (ugp_uncertainty_attach) from the arrays this Placer was built from."""
+        the first call (uncertainty_attach) from the arrays this Placer was built from; on a handle whose depth-first tables
+        another attach built from other arrays, call uncertainty_attach with those arrays first."""
         if not getattr(self, "_unc_ready", False):
-            self._ck(self._L.ugp_uncertainty_attach(self._h, C.byref(self._t.desc)))
-            self._unc_ready = True
+            self.uncertainty_attach()
         nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
         n = len(nodes)
         epps = np.zeros(n, np.uint32); nsize = np.zeros(n, np.uint32); cnt = np.zeros(n, np.uint32)
@@ -281,10 +288,18 @@ class Placer:
         return epps, nsize, [ties[i, :min(int(cnt[i]), cap)].copy() for i in range(n)], cnt
 
     # ---- matUtils annotate (ugp_annotate_attach / ugp_clade_alleles / ugp_clade_descendants / ugp_annotate_search) ------
+    def annotate_attach(self, arrays: Optional[Dict] = None):
+        """ugp_annotate_attach with the placer's own tree, or with other mutation arrays on the same topology (masked entries,
+        ambiguous alleles, a position twice on one node: trees the placement tables refuse).  The depth-first tables are shared as
+        genotypes_attach describes."""
+        t = self._t if arrays is None else _TreeArrays(arrays)
+        self._ck(self._L.ugp_annotate_attach(self._h, C.byref(t.desc)))
+        self._ann_attached = True
+
     def _ann_ready(self):
+        """The annotate tables, made on the first call (annotate_attach) from the arrays this Placer was built from."""
         if not getattr(self, "_ann_attached", False):
-            self._ck(self._L.ugp_annotate_attach(self._h, C.byref(self._t.desc)))
-            self._ann_attached = True
+            self.annotate_attach()
 
     @staticmethod
     def _clades_csr(clades):
@@ -339,15 +354,23 @@ class Placer:
     NEAREST_INFO = np.dtype([("count", np.uint32), ("anc", np.uint32), ("last_anc", np.uint32), ("cut_dist", np.uint32),
                              ("n_at_cut", np.uint32)])
 
+    def nearest_attach(self, arrays: Optional[Dict] = None):
+        """ugp_nearest_attach with the placer's own tree, or with other mutation arrays on the same topology (masked entries, a
+        position twice on one node: trees the placement tables refuse).  The depth-first tables are shared as genotypes_attach
+        describes."""
+        t = self._t if arrays is None else _TreeArrays(arrays)
+        self._ck(self._L.ugp_nearest_attach(self._h, C.byref(t.desc)))
+        self._near_ready = True
+
     def nearest_k(self, nodes, k, out_stride: Optional[int] = None, chunk_queries: int = 0):
         """matUtils extract's k nearest samples (ugp_nearest_k, select.cpp:206-276) for tree nodes given by BFS index; k is a
         scalar or one value per query.  Returns (out_nodes, out_dist, info): row i holds min(info[i].count, out_stride) leaves
         (BFS indices) and their distances to info[i].anc -- the leaves of last_anc in depth-first order, then the nearest others,
         ties in depth-first order; info is a NEAREST_INFO array.  out_stride defaults to the largest k; chunk_queries (test hook)
-        sets the queries per workspace chunk.  The tables are made on the first call (ugp_nearest_attach)."""
+        sets the queries per workspace chunk.  The tables are made on the first call (nearest_attach) from the arrays this Placer
+        was built from."""
         if not getattr(self, "_near_ready", False):
-            self._ck(self._L.ugp_nearest_attach(self._h, C.byref(self._t.desc)))
-            self._near_ready = True
+            self.nearest_attach()
         nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
         n = len(nodes)
         ks = np.ascontiguousarray(np.broadcast_to(np.asarray(k, dtype=np.uint32), (n,)))
