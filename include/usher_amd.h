@@ -477,6 +477,50 @@ int ugp_select_mrca(ugp_mat *mat, const uint64_t *words, uint32_t *node /* BFS *
 /* Bench hook: milliseconds of device time of the mutation kernel alone over these queries (the bitmap and the counts stay on the
  * device); mean of `reps` runs after one warm-up run. */
 int ugp_select_time(ugp_mat *mat, uint64_t n_mut, const int32_t *pos, const uint8_t *nuc, uint32_t reps, double *ms);
+/* node_excess_mutations and node_imputed_mutations of mapper2_body (usher_mapper.cpp:167-504 with compute_vecs, as pass 2 of
+ * usher_common.cpp:426-449 runs it on the placement node) for (sample, node) pairs: with ugp_place_batch the whole of
+ * usher_common.cpp:342-449.  ugp_vectors_attach shares the depth-first tables of `tree` (the handle's tree; arrays are copied,
+ * mut_par included: it is what the entries of part 1 report; tables built from other mutation arrays: UGP_ERR_INVALID, nothing
+ * changed; an allele above 15: UGP_ERR_UNSUPPORTED).  A second attach replaces the first.  A call before the attach is
+ * UGP_ERR_INVALID.
+ * Pair i is (sample[i] -- an index into q; NULL: i --, node[i] -- BFS).  Every entry is (pos, ref, par, nuc) = (position, ref_nuc,
+ * par_nuc, mut_nuc).  The excess list of a pair is, in this order,
+ *   1. the node's own entries that the branch loop (:190-264) keeps, in stored order, par as stored: info.n_branch of them;
+ *   2. one entry per non-missing row of the sample that the ancestral state g(p) does not explain (:292-388), in row order:
+ *      par = g(p), the allele of the nearest node on the root path with a non-masked entry at p (the node's own entry only when
+ *      part 1 kept it; the root's own for the root; none: the row's ref), nuc = the row's ref when the row holds it, else its
+ *      lowest set bit, and nuc != par (for rows that pass the row checks -- a one-hot ref, a non-zero mask -- a row that g(p) does
+ *      not explain always has nuc != par: nuc is a bit of the row or its ref, and g(p) shares no bit with the row);
+ *   3. one entry (g(p) -> ref) per position with an ancestral state other than its reference and no row in the sample (:393-445),
+ *      in ascending position.  For the root, its masked entries with nuc != ref give one each as well: they come first, in stored
+ *      order (the reference's unstable sort leaves their mutual order open).
+ * The imputed list holds one entry per ambiguous row (more than one bit), in row order (:322-335, :341-351, :375-377).
+ * info: n_excess, n_imputed, n_branch; set_difference = the entries of parts 2 and 3 (the reference's figure for an eligible node,
+ * one less than it for any other); has_unique = the branch loop's; eligible = the predicate of :454-455.  A pair whose node stores
+ * one non-masked position twice has refused = 1, every other field 0 and both lists empty: the reference's answer depends on an
+ * unstable sort there, and the caller runs such a pair on the host.
+ * Rows are checked as ugp_place_batch checks them (same errors).  A sample index >= q->n_queries or a node >= n_nodes is
+ * UGP_ERR_INVALID before anything is written.  ex_off / im_off [n_pairs + 1] are always complete, excess[0 .. min(ex_cap,
+ * *n_excess)) is written and *n_excess is the true total; the same for imputed.  Pairs come in any order and may repeat.  The
+ * _chunked twin (test hook) sets the pairs per launch window (0: default). */
+typedef struct ugp_vec_entry { int32_t pos; uint8_t ref, par, nuc, pad; } ugp_vec_entry;
+typedef struct ugp_vec_info {
+    uint32_t n_excess, n_imputed;
+    uint32_t n_branch;        /* leading excess entries that come from the node's own branch (loop 1) */
+    int32_t  set_difference;  /* excess entries of loops 2 and 3: the score before the "+1" of an ineligible node */
+    uint8_t  has_unique, eligible, refused, pad;
+} ugp_vec_info;
+int ugp_vectors_attach(ugp_mat *mat, const ugp_tree_desc *tree);
+int ugp_vectors(ugp_mat *mat, const ugp_queries *q, uint64_t n_pairs, const uint32_t *sample, const uint32_t *node, ugp_vec_info *info,
+                uint64_t *ex_off, ugp_vec_entry *excess, uint64_t ex_cap, uint64_t *n_excess,
+                uint64_t *im_off, ugp_vec_entry *imputed, uint64_t im_cap, uint64_t *n_imputed);
+int ugp_vectors_chunked(ugp_mat *mat, const ugp_queries *q, uint64_t n_pairs, const uint32_t *sample, const uint32_t *node, ugp_vec_info *info,
+                        uint64_t *ex_off, ugp_vec_entry *excess, uint64_t ex_cap, uint64_t *n_excess,
+                        uint64_t *im_off, ugp_vec_entry *imputed, uint64_t im_cap, uint64_t *n_imputed, uint32_t chunk_pairs);
+/* Bench hook: milliseconds of device time of the kernels alone over these pairs -- count_ms the counting pass with its prefix sums,
+ * fill_ms the pass that writes the lists and orders part 3 (they stay on the device) -- mean of `reps` runs after one warm-up run. */
+int ugp_vectors_time(ugp_mat *mat, const ugp_queries *q, uint64_t n_pairs, const uint32_t *sample, const uint32_t *node, uint32_t reps,
+                     double *count_ms, double *fill_ms);
 /* matUtils mask (matUtils/mask.cpp: restrictSamples :802-905, restrictMutationsLocally :703-800), both in closed form over the
  * depth-first ranges.  A mutation's KEY is (position, parent allele as stored, allele); entries are those of the mutation CSR.
  * ugp_mask_attach shares the depth-first tables of `tree` (the handle's tree; arrays are copied; tables built from other mutation

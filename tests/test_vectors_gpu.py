@@ -1,0 +1,234 @@
+"""Placer.vectors (ugp_vectors) against the literal mapper2_body of the oracle (OracleTree.node_vecs), exactly, on every case of
+tests/vectors_cases.py: info, both offset arrays and both lists, on a handle that holds the tree's mutations and on a topology-only
+one, through every window size, with pairs shuffled and repeated, under caps, and the errors; then vectors beside the other
+families that share a handle's depth-first tables (tests/shared_tables_cases.py)."""
+import numpy as np
+import pytest
+
+from oracle import capi
+from tests import shared_tables_cases as S
+from tests import summary_cases as SMC
+from tests import synth
+from tests import vectors_cases as VC
+from tests import vectors_ref as VR
+from usher_amd import Placer, QueryBatch, UgpError
+
+pytestmark = pytest.mark.gpu
+CASES = VC.cases()
+WANT = {}   # case name -> {(sample, node): the oracle's answer}, computed once
+
+
+def want(case):
+    if case["name"] not in WANT:
+        ot = capi.OracleTree(case["arrays"])
+        WANT[case["name"]] = {(s, j): VR.oracle_answer(ot, case["samples"][s], j) for s, j in sorted(set(case["pairs"])) if j not in case["refused"]}
+    return WANT[case["name"]]
+
+
+def bare(case):
+    pl = Placer(SMC.topology(case["arrays"]))
+    pl.vectors_attach(case["arrays"])
+    return pl
+
+
+def check(case, pl, pairs, **kw):
+    """One call over `pairs`; every pair against the oracle, the offsets against the counts."""
+    q = QueryBatch(case["samples"])
+    got = pl.vectors(q, [j for _, j in pairs], [s for s, _ in pairs], **kw)
+    info, ex_off, ex, im_off, im = got
+    assert int(ex_off[0]) == 0 and int(im_off[0]) == 0 and int(ex_off[-1]) == len(ex) and int(im_off[-1]) == len(im)
+    assert pl._vec_totals == (len(ex), len(im))
+    ans = VR.device_answers(info, ex_off, ex, im_off, im)
+    w = want(case)
+    for (s, j), a in zip(pairs, ans):
+        assert a["refused"] == (1 if j in case["refused"] else 0), (case["name"], s, j)
+        if a["refused"]:
+            assert a["excess"] == [] and a["imputed"] == [] and a["n_branch"] == 0 and a["set_difference"] == 0
+        else:
+            assert VR.agrees(a, w[(s, j)]), (case["name"], s, j, a, w[(s, j)])
+            assert a["excess"][:a["n_branch"]] == w[(s, j)]["excess"][:a["n_branch"]]
+    return got
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: c["name"])
+def test_every_pair_on_a_topology_only_handle(case):
+    pl = bare(case)
+    check(case, pl, case["pairs"])
+    pl.close()
+
+
+def test_every_pair_on_a_handle_with_the_trees_own_mutations():
+    """The placement tables refuse masked entries and a position twice on a node: the cases they take run on such a handle too."""
+    ran = []
+    for case in CASES:
+        try:
+            pl = Placer(case["arrays"])
+        except UgpError as e:
+            assert e.code == -2, case["name"]
+            continue
+        pl.vectors_attach()
+        check(case, pl, case["pairs"])
+        pl.close()
+        ran.append(case["name"])
+    assert {"ambiguous", "rewrite", "caterpillar", "caterpillar_flip", "rows", "polytomy"} <= set(ran), ran
+
+
+@pytest.mark.parametrize("name", ["loop1", "rows", "twice"])
+def test_windows_shuffles_and_repeats(name):
+    case = next(c for c in CASES if c["name"] == name)
+    pl = bare(case)
+    pairs = list(case["pairs"])
+    n = len(pairs)
+    whole = check(case, pl, pairs)
+    for chunk in (1, 2, 3, n - 1, n, n + 1, 0):
+        got = check(case, pl, pairs, chunk_pairs=chunk)
+        assert all(np.array_equal(a, b) for a, b in zip(got, whole)), chunk
+    rng = np.random.default_rng(7)
+    mixed = [pairs[i] for i in rng.permutation(n)]
+    mixed.insert(n // 2, mixed[0])
+    check(case, pl, mixed, chunk_pairs=5)
+    pl.close()
+
+
+def test_no_pairs_and_caps():
+    case = next(c for c in CASES if c["name"] == "ambiguous")
+    pl = bare(case)
+    q = QueryBatch(case["samples"])
+    info, ex_off, ex, im_off, im = pl.vectors(q, [])
+    assert len(info) == 0 and ex_off.tolist() == [0] and im_off.tolist() == [0] and len(ex) == 0 and len(im) == 0
+    pairs = case["pairs"]
+    nodes, smp = [j for _, j in pairs], [s for s, _ in pairs]
+    whole = pl.vectors(q, nodes, smp)
+    tot = pl._vec_totals
+    assert tot[0] > 2 and tot[1] > 2
+    for chunk in (0, 7):
+        for cap_ex, cap_im in ((0, 0), (tot[0] - 1, tot[1] - 1), (tot[0], tot[1]), (0, tot[1]), (tot[0], 0)):
+            info, ex_off, ex, im_off, im = pl.vectors(q, nodes, smp, chunk_pairs=chunk, ex_cap=cap_ex, im_cap=cap_im)
+            assert pl._vec_totals == tot                                                       # the totals are true
+            assert np.array_equal(info, whole[0]) and np.array_equal(ex_off, whole[1]) and np.array_equal(im_off, whole[3])   # complete
+            assert len(ex) == cap_ex and np.array_equal(ex, whole[2][:cap_ex])                   # the prefix is exact
+            assert len(im) == cap_im and np.array_equal(im, whole[4][:cap_im])
+    pl.close()
+
+
+def _raw(pl, q, nodes, samples, info, ex_off, ex, im_off, im):
+    import ctypes as C
+    from usher_amd.placement import _ptr
+    n_ex, n_im = C.c_uint64(77), C.c_uint64(77)
+    rc = pl._L.ugp_vectors(pl._h, C.byref(q.desc), len(nodes), _ptr(samples), _ptr(nodes), _ptr(info), _ptr(ex_off), _ptr(ex), len(ex), C.byref(n_ex),
+                           _ptr(im_off), _ptr(im), len(im), C.byref(n_im))
+    return rc, n_ex.value, n_im.value
+
+
+def test_errors_write_nothing():
+    case = next(c for c in CASES if c["name"] == "loop1")
+    q = QueryBatch(case["samples"])
+    n = int(case["arrays"]["n"])
+    pl = Placer(SMC.topology(case["arrays"]))
+    with pytest.raises(UgpError) as e:   # before the attach
+        pl.vectors(q, [0])
+    assert e.value.code == -1 and "ugp_vectors_attach" in str(e.value)
+    with pytest.raises(UgpError) as e:
+        pl.vectors_time(q, [0])
+    assert e.value.code == -1 and "ugp_vectors_attach" in str(e.value)
+    pl.vectors_attach(case["arrays"])
+    for nodes, samples in (([1, n], [0, 0]), ([1, 0xFFFFFFFF], [0, 0]), ([1, 2], [0, len(case["samples"])]), ([1, 2], [0xFFFFFFFF, 0])):
+        nodes, samples = np.asarray(nodes, np.uint32), np.asarray(samples, np.uint32)
+        info = np.full(2, 0x5A, np.uint8).repeat(Placer.VEC_INFO.itemsize).view(Placer.VEC_INFO)
+        ex_off, im_off = np.full(3, 99, np.uint64), np.full(3, 99, np.uint64)
+        ex, im = np.full(64, 0x5A, np.uint8).view(Placer.VEC_ENTRY), np.full(64, 0x5A, np.uint8).view(Placer.VEC_ENTRY)
+        rc, n_ex, n_im = _raw(pl, q, nodes, samples, info, ex_off, ex, im_off, im)
+        assert rc == -1 and b"out of range" in pl._L.ugp_last_error()
+        assert (n_ex, n_im) == (77, 77) and ex_off.tolist() == [99] * 3 and im_off.tolist() == [99] * 3
+        assert (info.view(np.uint8) == 0x5A).all() and (ex.view(np.uint8) == 0x5A).all() and (im.view(np.uint8) == 0x5A).all()
+    # without a sample list pair i is sample i: more pairs than samples is out of range too
+    with pytest.raises(UgpError) as e:
+        pl.vectors(q, [0] * (len(case["samples"]) + 1))
+    assert e.value.code == -1
+    # unsorted rows: the error of ugp_place_batch
+    bad = dict(case["samples"][0])
+    bad = {k: (v[::-1].copy() if k != "name" else v) for k, v in bad.items()}
+    qb = QueryBatch([bad])
+    with pytest.raises(UgpError) as e1:
+        pl.place(qb)
+    with pytest.raises(UgpError) as e2:
+        pl.vectors(qb, [1])
+    assert e1.value.code == e2.value.code == -2 and str(e1.value) == str(e2.value) and "not sorted" in str(e2.value)
+    check(case, pl, case["pairs"][:7])   # and the handle still answers
+    pl.close()
+
+
+# ---- beside the families that share the depth-first tables ----------------------------------------------------------------------------
+
+def shared_questions(t):
+    if t.name == "plain":
+        arrays, queries = synth.make_case(2, n_leaves=250, n_queries=4, n_sites=60, genome_len=500)
+        assert np.array_equal(arrays["mut_pos"], t.X["mut_pos"]) and np.array_equal(arrays["mut_off"], t.X["mut_off"])
+    else:
+        ref = lambda p: S.ONEHOT[p % 4]
+        rows = lambda k: [(p, (None, 15 ^ ref(p), [a for a in S.ONEHOT if a != ref(p)][k % 3], ref(p) | 8)[(p // 2 + k) % 4]) for p in range(3 + 2 * k, 93, 6)]
+        queries = [{"name": "b%d" % k, "pos": np.asarray([p for p, _ in rows(k)], np.int32), "ref": np.asarray([ref(p) for p, _ in rows(k)], np.int8),
+                    "nuc": np.asarray([15 if a is None else a for _, a in rows(k)], np.int8),
+                    "is_missing": np.asarray([a is None for _, a in rows(k)], np.int8)} for k in range(3)]
+    pairs = [(s, j) for s in range(len(queries)) for j in t.nodes + [0]]
+    ot = capi.OracleTree(t.X)
+    return queries, pairs, [VR.oracle_answer(ot, queries[s], j) for s, j in pairs]
+
+
+_SHARED = {}
+
+
+def vectors_answer(t, pl, why):
+    if t.name not in _SHARED:
+        _SHARED[t.name] = shared_questions(t)
+    queries, pairs, wanted = _SHARED[t.name]
+    ans = VR.device_answers(*pl.vectors(QueryBatch(queries), [j for _, j in pairs], [s for s, _ in pairs]))
+    for a, w, pr in zip(ans, wanted, pairs):
+        assert not a["refused"] and VR.agrees(a, w), (t.name, pr, why)
+
+
+@pytest.mark.parametrize("tree", ("plain", "bare"))
+@pytest.mark.parametrize("other", ("uncertainty", "select", "haplotypes"))
+def test_beside_the_families_that_share_the_tables(tree, other):
+    t = S.trees()[tree]
+    B = next(f for f in S.families(t) if f.name == other)
+    pl = t.handle()            # vectors first: it builds the depth-first tables and the owners' nodes
+    pl.vectors_attach(t.X)
+    vectors_answer(t, pl, "alone")
+    B.attach(pl, t.X)
+    assert B.ask(pl) == B.wanted(), ("after vectors", other)
+    vectors_answer(t, pl, ("after", other))
+    pl.close()
+    pl = t.handle()            # vectors second
+    B.attach(pl, t.X)
+    assert B.ask(pl) == B.wanted()
+    pl.vectors_attach(t.X)
+    vectors_answer(t, pl, ("attached after", other))
+    assert B.ask(pl) == B.wanted(), ("before vectors", other)
+    pl.close()
+
+
+def _refused(pl, y):
+    with pytest.raises(UgpError) as e:
+        pl.vectors_attach(y)
+    assert e.value.code == -1 and "other mutation arrays" in str(e.value) and "ugp_vectors_attach" in str(e.value)
+
+
+@pytest.mark.parametrize("tree", ("plain", "bare"))
+def test_other_arrays_are_refused(tree):
+    t = S.trees()[tree]
+    B = next(f for f in S.families(t) if f.name == "select")
+    pl = t.handle()
+    B.attach(pl, t.X)
+    for y in S.YS:             # as a first attach of vectors: the handle has no vector tables afterwards
+        _refused(pl, t.Y[y])
+        with pytest.raises(UgpError) as e:
+            pl.vectors(QueryBatch([]), [])
+        assert "ugp_vectors_attach" in str(e.value)
+    assert B.ask(pl) == B.wanted()
+    pl.vectors_attach(t.X)
+    for y in S.YS:             # as a second attach, which would replace the state
+        _refused(pl, t.Y[y])
+    vectors_answer(t, pl, "after the refused attaches")
+    assert B.ask(pl) == B.wanted()
+    pl.close()

@@ -120,6 +120,10 @@ SYMBOLS = {
     "ugp_select_subtrees_chunked": (C.c_int, [P, C.c_uint64, P, P, P, C.c_uint32]),
     "ugp_select_mrca": (C.c_int, [P, P, P, P]),
     "ugp_select_time": (C.c_int, [P, C.c_uint64, P, P, C.c_uint32, P]),
+    "ugp_vectors_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc)]),
+    "ugp_vectors": (C.c_int, [P, C.POINTER(ugp_queries), C.c_uint64, P, P, P, P, P, C.c_uint64, P, P, P, C.c_uint64, P]),
+    "ugp_vectors_chunked": (C.c_int, [P, C.POINTER(ugp_queries), C.c_uint64, P, P, P, P, P, C.c_uint64, P, P, P, C.c_uint64, P, C.c_uint32]),
+    "ugp_vectors_time": (C.c_int, [P, C.POINTER(ugp_queries), C.c_uint64, P, P, C.c_uint32, P, P]),
     "ugp_mask_attach": (C.c_int, [P, C.POINTER(ugp_tree_desc)]),
     "ugp_mask_restricted": (C.c_int, [P, C.c_uint64, P, P, P, C.c_uint64, P, P]),
     "ugp_mask_mutations": (C.c_int, [P, C.c_uint64, P, P, P, P, P, P, P, P, P]),

@@ -3,6 +3,7 @@
 // loading (usher.cpp:132-173) and the call into the driver (usher.cpp:175-178).
 #include <algorithm>
 #include <chrono>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -43,6 +44,8 @@ static const char *kHelp =
     "  -T [ --threads ] arg                      Number of host threads (the node x sample search runs on the GPU)\n"
     "  --device arg (=0)                         HIP device ordinal\n"
     "  --devices arg                             HIP devices to shard the samples across, e.g. 0-7 or 0,2,3 (the tree is replicated)\n"
+    "  --device-vectors                          With -n or -p: excess and imputed mutations of the placement nodes from the device, one call per batch\n"
+    "  --host-vectors                            With -n or -p: excess and imputed mutations of the placement nodes on the host (the default)\n"
     "  --version                                 Print version number\n"
     "  -h [ --help ]                             Print help messages\n";
 
@@ -56,7 +59,7 @@ static int parse(int argc, char **argv, Options &o) {
         {'e', "max-uncertainty-per-sample", 1}, {'E', "max-parsimony-per-sample", 1}, {'u', "write-uncondensed-final-tree", 0},
         {'k', "write-subtrees-size", 1}, {'K', "write-single-subtree", 1}, {'p', "write-parsimony-scores-per-node", 0},
         {'M', "multiple-placements", 1}, {'l', "retain-input-branch-lengths", 0}, {'n', "no-add", 0}, {'D', "detailed-clades", 0},
-        {'T', "threads", 1}, {0, "device", 1}, {0, "devices", 1}, {0, "version", 0}, {'h', "help", 0}};
+        {'T', "threads", 1}, {0, "device", 1}, {0, "devices", 1}, {0, "device-vectors", 0}, {0, "host-vectors", 0}, {0, "version", 0}, {'h', "help", 0}};
     bool version = false, help = false, bad = false;
     auto apply = [&](const Spec &sp, const char *val) {
         const std::string l = sp.l;
@@ -73,7 +76,8 @@ static int parse(int argc, char **argv, Options &o) {
         else if (l == "write-parsimony-scores-per-node") o.print_scores = true; else if (l == "multiple-placements") o.max_trees = (uint32_t)num(val);
         else if (l == "retain-input-branch-lengths") o.retain_branch_len = true; else if (l == "no-add") o.no_add = true;
         else if (l == "detailed-clades") o.detailed_clades = true; else if (l == "threads") o.threads = (uint32_t)num(val);
-        else if (l == "device") o.device = (int)num(val); else if (l == "devices") o.devices = val; else if (l == "version") version = true; else if (l == "help") help = true;
+        else if (l == "device") o.device = (int)num(val); else if (l == "devices") o.devices = val;
+        else if (l == "device-vectors") o.device_vectors = true; else if (l == "host-vectors") o.device_vectors = false; else if (l == "version") version = true; else if (l == "help") help = true;
     };
     for (int i = 1; i < argc && !bad; i++) {
         const std::string a = argv[i];
@@ -180,9 +184,19 @@ int usher_main(int argc, char **argv, const Backend &be) {
 }  // namespace uh
 
 // C entry for tests: the same front end with a caller-supplied placement backend.
+// The C entries.  uh_usher_main_sized takes the size of the caller's Backend: the members the caller's structure has are copied,
+// the ones added to uh::Backend since stay null -- members are only ever appended.  uh_usher_main is the entry of callers whose
+// structure ends with `prepare` (the layout before `vectors` was added); a caller that sets `vectors` uses the sized entry with
+// sizeof(uh::Backend), or uh::usher_main directly.
+extern "C" int uh_usher_main_sized(int argc, char **argv, const uh::Backend *be, size_t be_size) {
+    if (!be || be_size < offsetof(uh::Backend, scores)) { fprintf(stderr, "ERROR: no placement backend\n"); return 1; }
+    uh::Backend own;
+    memcpy(static_cast<void *>(&own), static_cast<const void *>(be), std::min(be_size, sizeof(uh::Backend)));
+    if (!own.place) { fprintf(stderr, "ERROR: no placement backend\n"); return 1; }
+    return uh::usher_main(argc, argv, own);
+}
 extern "C" int uh_usher_main(int argc, char **argv, const uh::Backend *be) {
-    if (!be || !be->place) { fprintf(stderr, "ERROR: no placement backend\n"); return 1; }
-    return uh::usher_main(argc, argv, *be);
+    return uh_usher_main_sized(argc, argv, be, offsetof(uh::Backend, vectors));
 }
 
 // Bench / test utilities (no GPU): write the synthetic workload as the files the front end reads, and time the two loaders.

@@ -237,6 +237,60 @@ void node_vecs(const Node *node, const std::vector<Mutation> &sample, NodeVecs &
 }
 
 // ---------------------------------------------------------------------------
+// The same vectors from the backend (Backend::vectors, ugp_vectors) for the (sample, node) pairs of one static-tree batch, in one
+// call: the pairs are added sample by sample, a sample's in ascending node order.
+// ---------------------------------------------------------------------------
+namespace {
+struct DevVecs {
+    bool on = false;                     // the last run() answered
+    std::vector<uint32_t> smp, node;
+    std::vector<size_t> first;           // per sample of the batch its first pair, [samples + 1]
+    std::vector<ugp_vec_info> info;
+    std::vector<uint64_t> ex_off, im_off;
+    std::vector<ugp_vec_entry> ex, im;
+    size_t calls = 0, pairs = 0;         // over every run() of this object, for the profile
+    mutable size_t taken = 0;            // pairs get() answered
+    double secs = 0;
+    void begin(size_t n_samples) { on = false; smp.clear(); node.clear(); first.assign(n_samples + 1, 0); }
+    void add(size_t s, uint32_t j) { smp.push_back((uint32_t)s); node.push_back(j); first[s + 1]++; }
+    int run(const Backend &be, const ugp_tree_desc *t, uint64_t version, const ugp_queries *q) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (size_t i = 1; i < first.size(); i++) first[i] += first[i - 1];
+        const size_t n = smp.size();
+        info.resize(n); ex_off.assign(n + 1, 0); im_off.assign(n + 1, 0);
+        uint64_t nx = 8 * n + 1024, ni = 2 * n + 1024;
+        for (int round = 0; round < 2; round++) {   // the call reports the true totals: room for them, and once more
+            ex.resize(nx); im.resize(ni);
+            uint64_t tx = 0, ti = 0;
+            if (int rc = be.vectors(be.ctx, t, version, q, n, smp.data(), node.data(), info.data(), ex_off.data(), ex.data(), nx, &tx, im_off.data(),
+                                    im.data(), ni, &ti)) return rc;
+            if (tx <= nx && ti <= ni) break;
+            nx = std::max(nx, tx); ni = std::max(ni, ti);
+        }
+        on = true;
+        calls++; pairs += n;
+        secs += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return 0;
+    }
+    // Pair p as node_vecs would have filled `out`; false: the pair was refused, or `host` says so (the caller runs node_vecs).
+    bool get(size_t p, bool host, NodeVecs &out) const {
+        if (!on || host || p >= info.size() || info[p].refused) return false;
+        auto mut = [](const ugp_vec_entry &e) {
+            Mutation m;
+            m.position = e.pos; m.ref_nuc = (int8_t)e.ref; m.par_nuc = (int8_t)e.par; m.mut_nuc = (int8_t)e.nuc;
+            return m;
+        };
+        out.excess.clear(); out.imputed.clear();
+        for (uint64_t k = ex_off[p]; k < ex_off[p + 1]; k++) out.excess.push_back(mut(ex[k]));
+        for (uint64_t k = im_off[p]; k < im_off[p + 1]; k++) out.imputed.push_back(mut(im[k]));
+        out.set_difference = info[p].set_difference;
+        out.has_unique = info[p].has_unique != 0;
+        out.eligible = info[p].eligible != 0;
+        taken++;
+        return true;
+    }
+};
+}  // namespace
 
 // ---------------------------------------------------------------------------
 // The search of usher_common.cpp:389-449 for ONE sample on the host, with the literal routine above at every node.
@@ -976,6 +1030,12 @@ int run_usher(const Options &opt, Tree &T, std::vector<MissingSample> &missing, 
             batch_res.resize(missing.size());
             if (!host_all && be.place(be.ctx, &flat.desc, tree_version, &allq.desc, batch_res.data()) != 0) return be_fail("placement");
         }
+        // The vectors of the placement nodes on a static tree: from the backend, one call per batch (--device-vectors), else node_vecs.
+        // Masked entries of the root are kept as the literal routine reads them off the tree: such root pairs stay on the host.
+        const bool use_dev_vecs = static_tree && opt.device_vectors && be.vectors && !host_all;
+        bool root_masked = false;
+        for (const Mutation &m : T.root->mutations) root_masked = root_masked || m.masked();
+        DevVecs slab_vecs, win_vecs;
         // -p: the samples x nodes score matrix is produced in slabs of at most ~1 GiB
         size_t slab_base = 0, slab_len = 0;
         std::vector<int32_t> host_scores;
@@ -995,6 +1055,15 @@ int run_usher(const Options &opt, Tree &T, std::vector<MissingSample> &missing, 
                 part.finish();
                 batch_scores.resize(slab_len * n);
                 if (be.scores(be.ctx, &flat.desc, tree_version, &part.desc, batch_scores.data()) != 0) return nullptr;
+                slab_vecs.begin(slab_len);
+                if (use_dev_vecs) {   // every optimal (sample, node) of the slab in one call
+                    for (size_t k = 0; k < slab_len; k++) {
+                        if (odd[s + k]) continue;
+                        const int32_t *row = batch_scores.data() + k * n, best = batch_res[s + k].best_set_difference;
+                        for (size_t j = 0; j < n; j++) if (row[j] == best) slab_vecs.add(k, (uint32_t)j);
+                    }
+                    if (slab_vecs.run(be, &flat.desc, tree_version, &part.desc) != 0) return nullptr;
+                }
             }
             return batch_scores.data() + (s - slab_base) * n;
         };
@@ -1165,6 +1234,15 @@ int run_usher(const Options &opt, Tree &T, std::vector<MissingSample> &missing, 
             dev.t_batch += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0;
             return true;
         };
+        if (use_dev_vecs && !opt.print_scores) {   // -n: every sample's winner in one call
+            const double tv0 = now_s();
+            win_vecs.begin(missing.size());
+            for (size_t i = 0; i < missing.size(); i++)
+                if (!odd[i] && batch_res[i].num_best <= opt.max_uncertainty && (uint32_t)batch_res[i].best_set_difference <= opt.max_parsimony)
+                    win_vecs.add(i, batch_res[i].best_j);
+            if (win_vecs.run(be, &flat.desc, tree_version, &allq.desc) != 0) return be_fail("vectors of the placement nodes");
+            prof.vecs += now_s() - tv0;
+        }
         FILE *stats = fopen((outdir + "/placement_stats.tsv").c_str(), "w");
         if (!stats) { fprintf(stderr, "ERROR: cannot write to %s\n", outdir.c_str()); return 1; }
         FILE *scores_file = nullptr;
@@ -1437,12 +1515,13 @@ int run_usher(const Options &opt, Tree &T, std::vector<MissingSample> &missing, 
             if (opt.print_scores) {                                             // :557-578
                 const int32_t *sc = scores_row(s);
                 if (!sc) { fclose(stats); return be_fail("per-node scoring"); }
+                size_t pair = (slab_vecs.on && !odd[s]) ? slab_vecs.first[s - slab_base] : 0;   // the sample's optimal nodes, ascending
                 for (size_t k = 0; k < total_nodes && scores_file; k++) {
                     const bool optimal = sc[k] == best;
                     fprintf(scores_file, "%s\t%s\t%d\t\t%c\t", ms.name.c_str(), flat.bfs[k]->id.c_str(), sc[k], optimal ? 'y' : 'n');
                     if (optimal) {
                         if (sc[k] == 0) fprintf(scores_file, "*");
-                        node_vecs(flat.bfs[k], ms.mutations, vec);
+                        if (!slab_vecs.get(pair++, odd[s] || (k == 0 && root_masked), vec)) node_vecs(flat.bfs[k], ms.mutations, vec);
                         for (int i = 0; i < sc[k] && (size_t)i < vec.excess.size(); i++)   // first `score` entries of the excess vector (:565-572)
                             fprintf(scores_file, "%s%s", vec.excess[i].str().c_str(), i + 1 < sc[k] ? "," : "");
                     } else fprintf(scores_file, "N/A");
@@ -1480,7 +1559,9 @@ int run_usher(const Options &opt, Tree &T, std::vector<MissingSample> &missing, 
                     }
                 }
                 const double tv0 = now_s();
-                node_vecs(best_node, ms.mutations, vec);                        // pass 2 for the winner, :426-449
+                if (!(win_vecs.on && !patched && win_vecs.first[s] < win_vecs.first[s + 1] &&           // pass 2 for the winner, :426-449
+                      win_vecs.get(win_vecs.first[s], best_node->is_root() && root_masked, vec)))
+                    node_vecs(best_node, ms.mutations, vec);
                 prof.vecs += now_s() - tv0;
                 if (!opt.no_add) {
                     const size_t t0 = touched.size();
@@ -1544,7 +1625,10 @@ int run_usher(const Options &opt, Tree &T, std::vector<MissingSample> &missing, 
         prof.loop = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t_loop0;
         if (getenv("USHER_AMD_PROFILE"))
             fprintf(stderr, "[usher-amd profile] per-sample loop %.3f s in all: vectors of the winning node (pass 2) %.3f s, tree edits %.3f s, bookkeeping of the edits %.3f s\n",
-                    prof.loop, prof.vecs, prof.insert, prof.book);
+                    prof.loop, prof.vecs + slab_vecs.secs, prof.insert, prof.book);   // (-p: its calls run inside scores_row)
+        if (getenv("USHER_AMD_PROFILE") && use_dev_vecs)
+            fprintf(stderr, "[usher-amd profile] vectors from the device: %zu calls, %zu pairs in %.3f s, %zu of them used (the others: refused, masked root entries, or answered again on the host)\n",
+                    slab_vecs.calls + win_vecs.calls, slab_vecs.pairs + win_vecs.pairs, slab_vecs.secs + win_vecs.secs, slab_vecs.taken + win_vecs.taken);
         if (getenv("USHER_AMD_PROFILE") && dev.flat_done)
             fprintf(stderr, "[usher-amd profile] add mode on the device: %zu batches %.3f s, %zu record uploads %.3f s, result fetches %.3f s, %zu records; "
                             "asked again: flattened tree %zu, records %zu, all records on the host %zu\n", dev.n_batches, dev.t_batch, dev.n_flush, dev.t_flush,

@@ -25,6 +25,7 @@ struct Options {   // the 22 flags of src/usher.cpp:47-86
     uint32_t threads = 0;
     int device = 0;   // extension: HIP device ordinal (--device)
     std::string devices;   // extension: device list to shard the samples across (--devices 0-7); parsed by the backend
+    bool device_vectors = false;   // extension: -n / -p take the placement nodes' vectors from Backend::vectors (--device-vectors / --host-vectors)
 };
 
 // The search block of usher_common.cpp:342-449 for a batch of samples on a
@@ -53,6 +54,13 @@ struct Backend {
     // read, so that flattening and upload are over when the samples arrive.
     void (*warm)(void *ctx) = nullptr;
     int (*prepare)(void *ctx, const ugp_tree_desc *, uint64_t tree_version) = nullptr;
+    // Optional: ugp_vectors on the tree of `place` -- mapper2_body's excess / imputed vectors of (sample, node) pairs in one call.
+    // Null (the oracle backend), or a refused pair: the driver runs node_vecs below.  Members are only ever appended to this
+    // structure: the C entry uh_usher_main takes the members up to `prepare` (this one stays null), uh_usher_main_sized the
+    // caller's sizeof (cli.cpp).
+    int (*vectors)(void *ctx, const ugp_tree_desc *, uint64_t tree_version, const ugp_queries *, uint64_t n_pairs, const uint32_t *sample,
+                   const uint32_t *node, ugp_vec_info *info, uint64_t *ex_off, ugp_vec_entry *excess, uint64_t ex_cap, uint64_t *n_excess,
+                   uint64_t *im_off, ugp_vec_entry *imputed, uint64_t im_cap, uint64_t *n_imputed) = nullptr;
 };
 
 // The tree as loaded, turned into the backend's arrays (and handed to Backend::prepare) on a thread of its own; run_usher takes it

@@ -27,6 +27,7 @@ struct GpuCtx {
     ugp_fitch *fitch = nullptr;
     bool fitch_pool = false;   // ugp_fitch_sankoff has run: its pooled device buffers are handed back before the first tree goes to the device
     uint64_t version = 0;
+    uint64_t vec_version = 0;   // the tree version the first handle's vector tables were attached for (0: none)
     std::string err;
     std::thread warm_th;   // Backend::warm: the device runtime comes up while the inputs are read
 };
@@ -45,6 +46,7 @@ int ensure(GpuCtx *c, const ugp_tree_desc *t, uint64_t version) {
     int rc = ugp_mat_create_multi(t, c->devices.data(), (int)c->devices.size(), c->mats.data());
     if (rc != UGP_OK) { c->err = ugp_last_error(); c->mats.clear(); return rc; }
     c->version = version;
+    c->vec_version = 0;
     return UGP_OK;
 }
 
@@ -108,6 +110,21 @@ int gpu_ties(void *ctx, const ugp_tree_desc *t, uint64_t v, const ugp_queries *q
     return sharded(c, q, [&](size_t d, const ugp_queries &part, uint64_t lo) {
         return ugp_tied_nodes(c->mats[d], &part, cap, tj + lo * cap, th + lo * cap, tc + lo);
     });
+}
+// The vectors of (sample, node) pairs, on the first device: the tables are attached once per tree.
+int gpu_vectors(void *ctx, const ugp_tree_desc *t, uint64_t v, const ugp_queries *q, uint64_t n_pairs, const uint32_t *sample, const uint32_t *node,
+                ugp_vec_info *info, uint64_t *ex_off, ugp_vec_entry *excess, uint64_t ex_cap, uint64_t *n_excess, uint64_t *im_off,
+                ugp_vec_entry *imputed, uint64_t im_cap, uint64_t *n_imputed) {
+    GpuCtx *c = (GpuCtx *)ctx;
+    if (int rc = ensure(c, t, v)) return rc;
+    int rc = UGP_OK;
+    if (c->vec_version != v) {
+        rc = ugp_vectors_attach(c->mats[0], t);
+        if (rc == UGP_OK) c->vec_version = v;
+    }
+    if (rc == UGP_OK) rc = ugp_vectors(c->mats[0], q, n_pairs, sample, node, info, ex_off, excess, ex_cap, n_excess, im_off, imputed, im_cap, n_imputed);
+    if (rc != UGP_OK) c->err = ugp_last_error();
+    return rc;
 }
 // Add mode: the edits go to every replica (each keeps excluding the rewritten nodes from its searches); the records are scored on
 // the first device.
@@ -193,7 +210,7 @@ int main(int argc, char **argv) {
         if (ctx.devices.empty()) { fprintf(stderr, "ERROR: cannot parse the device list '%s' (expected e.g. 0-7 or 0,2,3)\n", val.c_str()); return 1; }
     }
     uh::Backend be;
-    be.ctx = &ctx; be.place = gpu_place; be.scores = gpu_scores; be.ties = gpu_ties; be.last_error = gpu_err;
+    be.ctx = &ctx; be.place = gpu_place; be.scores = gpu_scores; be.ties = gpu_ties; be.last_error = gpu_err; be.vectors = gpu_vectors;
     be.fitch = gpu_fitch; be.fitch_get = gpu_fitch_get;
     be.update = gpu_update; be.touched_open = gpu_touched_open; be.touched_score = gpu_touched_score; be.touched_rescore = gpu_touched_rescore;
     be.touched_fetch = gpu_touched_fetch;

@@ -35,6 +35,7 @@
 #include "ugp_mask.hpp"
 #include "ugp_subtree.hpp"
 #include "ugp_select.hpp"
+#include "ugp_vectors.hpp"
 #include "ugp_genotypes.hpp"
 #include "ugp_summary.hpp"
 #include "ugp_translate.hpp"
@@ -312,6 +313,7 @@ struct ugp_mat {
     ugp::SmState *sm = nullptr;      // matUtils summary tables (ugp_summary_attach), or none
     ugp::TrState *tr = nullptr;      // matUtils summary --translate tables (ugp_translate_attach), or none
     ugp::SelState *sel = nullptr;    // matUtils extract selector tables (ugp_select_attach), or none
+    ugp::VecState *vec = nullptr;    // excess / imputed vector tables (ugp_vectors_attach), or none
     ugp::MskState *msk = nullptr;    // matUtils mask tables (ugp_mask_attach), or none
     ugp::SubState *sub = nullptr;    // induced-subtree tables (ugp_subtree_attach), or none
     ugp::HpState *hp = nullptr;      // matUtils summary --haplotype tables (ugp_haplotypes_attach), or none
@@ -1442,6 +1444,7 @@ void ugp_mat_destroy(ugp_mat *m) {
     ugp::sm_free(m->sm);
     ugp::tr_free(m->tr);
     ugp::sel_free(m->sel);
+    ugp::vec_free(m->vec);
     ugp::msk_free(m->msk);
     ugp::sub_free(m->sub);
     ugp::hp_free(m->hp);
@@ -2029,6 +2032,60 @@ int ugp_select_mrca(ugp_mat *m, const uint64_t *words, uint32_t *node, uint64_t 
 int ugp_select_time(ugp_mat *m, uint64_t n_mut, const int32_t *pos, const uint8_t *nuc, uint32_t reps, double *ms) {
     if (!m) return fail(UGP_ERR_INVALID, "null argument");
     return ugp::sel_time(m->sel, n_mut, pos, nuc, reps, ms);
+}
+
+// ---- the excess and imputed mutations of (sample, node) pairs (ugp_vectors.hip) -------------------------------------------
+
+int ugp_vectors_attach(ugp_mat *m, const ugp_tree_desc *tree) {
+    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
+    if (int rc = check_handle_tree(m, tree)) return rc;
+    return ugp::vec_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->vec);
+}
+
+// The pairs are checked, then the rows go to the device through the checks of ugp_place_batch (qset_fill), then the passes run.
+static int vectors_call(ugp_mat *m, const char *who, const ugp_queries *q, uint64_t n_pairs, const uint32_t *sample, const uint32_t *node,
+                        ugp_vec_info *info, uint64_t *ex_off, ugp_vec_entry *excess, uint64_t ex_cap, uint64_t *n_excess, uint64_t *im_off,
+                        ugp_vec_entry *imputed, uint64_t im_cap, uint64_t *n_imputed, uint32_t chunk_pairs, double *kernel_ms) {
+    if (!m) return fail(UGP_ERR_INVALID, "null argument");
+    if (int rc = ugp::vec_check(m->vec, who, q, n_pairs, sample, node)) return rc;
+    ugp_qset qs;
+    int rc = qset_fill(m, q, &qs);
+    if (!rc) rc = ugp::vec_run(m->vec, q, qs.d_pos.p, qs.d_ref.p, qs.d_nuc.p, qs.d_missing.p, n_pairs, sample, node, info, ex_off, excess, ex_cap,
+                               n_excess, im_off, imputed, im_cap, n_imputed, chunk_pairs, kernel_ms);
+    (void)hipSetDevice(m->device);   // qs frees its buffers there
+    return rc;
+}
+
+int ugp_vectors_chunked(ugp_mat *m, const ugp_queries *q, uint64_t n_pairs, const uint32_t *sample, const uint32_t *node, ugp_vec_info *info,
+                        uint64_t *ex_off, ugp_vec_entry *excess, uint64_t ex_cap, uint64_t *n_excess, uint64_t *im_off, ugp_vec_entry *imputed,
+                        uint64_t im_cap, uint64_t *n_imputed, uint32_t chunk_pairs) {
+    return vectors_call(m, "ugp_vectors", q, n_pairs, sample, node, info, ex_off, excess, ex_cap, n_excess, im_off, imputed, im_cap, n_imputed,
+                        chunk_pairs, nullptr);
+}
+
+int ugp_vectors(ugp_mat *m, const ugp_queries *q, uint64_t n_pairs, const uint32_t *sample, const uint32_t *node, ugp_vec_info *info,
+                uint64_t *ex_off, ugp_vec_entry *excess, uint64_t ex_cap, uint64_t *n_excess, uint64_t *im_off, ugp_vec_entry *imputed,
+                uint64_t im_cap, uint64_t *n_imputed) {
+    return ugp_vectors_chunked(m, q, n_pairs, sample, node, info, ex_off, excess, ex_cap, n_excess, im_off, imputed, im_cap, n_imputed, 0);
+}
+
+int ugp_vectors_time(ugp_mat *m, const ugp_queries *q, uint64_t n_pairs, const uint32_t *sample, const uint32_t *node, uint32_t reps,
+                     double *count_ms, double *fill_ms) {
+    if (!m || !reps || !count_ms || !fill_ms) return fail(UGP_ERR_INVALID, "null argument");
+    if (int rc = ugp::vec_check(m->vec, "ugp_vectors_time", q, n_pairs, sample, node)) return rc;
+    ugp_qset qs;
+    int rc = qset_fill(m, q, &qs);
+    double ms[2], sum[2] = {0, 0};
+    for (uint32_t r = 0; r <= reps && !rc; r++) {   // the first run warms up
+        rc = ugp::vec_run(m->vec, q, qs.d_pos.p, qs.d_ref.p, qs.d_nuc.p, qs.d_missing.p, n_pairs, sample, node, nullptr, nullptr, nullptr, 0, nullptr,
+                          nullptr, nullptr, 0, nullptr, 0, ms);
+        if (r) { sum[0] += ms[0]; sum[1] += ms[1]; }
+    }
+    (void)hipSetDevice(m->device);
+    if (rc) return rc;
+    *count_ms = sum[0] / reps;
+    *fill_ms = sum[1] / reps;
+    return UGP_OK;
 }
 
 // ---- matUtils mask: restricted samples and masked mutations in closed form (ugp_mask.hip) ---------------------------------

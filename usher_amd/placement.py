@@ -795,6 +795,59 @@ class Placer:
                                        _ptr(flat) if len(flat) else None, int(reps), C.byref(a), C.byref(b)))
         return float(a.value), float(b.value)
 
+    # ---- the excess and imputed mutations of (sample, node) pairs (ugp_vectors_*) ---------------------------------------------------
+    VEC_ENTRY = np.dtype([("pos", np.int32), ("ref", np.uint8), ("par", np.uint8), ("nuc", np.uint8), ("pad", np.uint8)])
+    VEC_INFO = np.dtype([("n_excess", np.uint32), ("n_imputed", np.uint32), ("n_branch", np.uint32), ("set_difference", np.int32),
+                         ("has_unique", np.uint8), ("eligible", np.uint8), ("refused", np.uint8), ("pad", np.uint8)])
+
+    def vectors_attach(self, arrays: Optional[Dict] = None):
+        """ugp_vectors_attach with the placer's own tree, or with other mutation arrays on the same topology: the stored parent
+        alleles of the vectors calls.  The depth-first tables are shared as genotypes_attach describes."""
+        t = self._t if arrays is None else _TreeArrays(arrays)
+        self._ck(self._L.ugp_vectors_attach(self._h, C.byref(t.desc)))
+
+    def _vec_pairs(self, queries, nodes, samples):
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
+        samples = None if samples is None else np.ascontiguousarray(samples, dtype=np.uint32)
+        if samples is not None and len(samples) != len(nodes):
+            raise UgpError(-1, "one sample per node")
+        return nodes, samples
+
+    def vectors(self, queries: QueryBatch, nodes, samples=None, chunk_pairs: int = 0, ex_cap: Optional[int] = None, im_cap: Optional[int] = None):
+        """node_excess_mutations and node_imputed_mutations of mapper2_body (ugp_vectors) for the pairs (samples[i] -- an index into
+        `queries`; None: i --, nodes[i] -- BFS).  Returns (info, ex_off, excess, im_off, imputed): info a VEC_INFO array; the excess
+        entries of pair i are excess[ex_off[i]:ex_off[i + 1]] (VEC_ENTRY: pos, ref, par, nuc), the imputed ones likewise.  The tables
+        are those of vectors_attach, which is not called here.  chunk_pairs (test hook): pairs per launch window; ex_cap / im_cap
+        (test hooks): room for that many entries only, the true totals are then in _vec_totals."""
+        nodes, samples = self._vec_pairs(queries, nodes, samples)
+        n = len(nodes)
+        info = np.zeros(n, self.VEC_INFO)
+        ex_off, im_off = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+        n_ex, n_im = C.c_uint64(0), C.c_uint64(0)
+        room_ex = int(ex_cap) if ex_cap is not None else max(8 * n, 1024)
+        room_im = int(im_cap) if im_cap is not None else max(2 * n, 1024)
+        while True:   # grow and retry: the call reports the true totals
+            ex, im = np.zeros(room_ex, self.VEC_ENTRY), np.zeros(room_im, self.VEC_ENTRY)
+            self._ck(self._L.ugp_vectors_chunked(self._h, C.byref(queries.desc), n, None if samples is None or not n else _ptr(samples),
+                                                 _ptr(nodes) if n else None, _ptr(info) if n else None, _ptr(ex_off), _ptr(ex) if room_ex else None,
+                                                 room_ex, C.byref(n_ex), _ptr(im_off), _ptr(im) if room_im else None, room_im, C.byref(n_im),
+                                                 int(chunk_pairs)))
+            self._vec_totals = (int(n_ex.value), int(n_im.value))
+            if (ex_cap is not None or self._vec_totals[0] <= room_ex) and (im_cap is not None or self._vec_totals[1] <= room_im):
+                return info, ex_off, ex[:min(room_ex, self._vec_totals[0])], im_off, im[:min(room_im, self._vec_totals[1])]
+            if ex_cap is None:
+                room_ex = max(room_ex, self._vec_totals[0])
+            if im_cap is None:
+                room_im = max(room_im, self._vec_totals[1])
+
+    def vectors_time(self, queries: QueryBatch, nodes, samples=None, reps: int = 5):
+        """Bench hook: (count_ms, fill_ms), the device time of the two passes alone over these pairs, no copy to the host."""
+        nodes, samples = self._vec_pairs(queries, nodes, samples)
+        a, b = C.c_double(0), C.c_double(0)
+        self._ck(self._L.ugp_vectors_time(self._h, C.byref(queries.desc), len(nodes), None if samples is None else _ptr(samples), _ptr(nodes),
+                                          int(reps), C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
+
     # ---- the subtree induced by a selection, in closed form (ugp_subtree_*) ----------------------------------------------------------
     SUB_INFO = np.dtype([("n_selected", np.uint64), ("n_gathered", np.uint64), ("n_disagree", np.uint64), ("longest_chain", np.uint64),
                          ("first_disagree", np.uint32), ("pad", np.uint32)])
