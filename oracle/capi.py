@@ -48,6 +48,8 @@ def lib():
         L.orc_cf_scores.argtypes = [P, C.c_int64, P, P, P, P, P]
         L.orc_node_vecs.restype = C.c_int
         L.orc_node_vecs.argtypes = [P, C.c_int64, P, P, P, P, C.c_int64, C.c_int64] + [P] * 12
+        L.orc_node_vecs_split.restype = C.c_int
+        L.orc_node_vecs_split.argtypes = [P, C.c_int64, P, P, P, P, C.c_int64, C.c_int64] + [P] * 14
         L.orc_fitch_site.restype = C.c_int
         L.orc_fitch_site.argtypes = [C.c_int64, P, C.c_int8, C.c_int64, P, P, P, P, P]
         L.orc_add_mutations.restype = C.c_int
@@ -150,6 +152,14 @@ class OracleTree:
         return {"best": int(best[0]), "num_best": int(nb[0]), "best_j": int(bj[0])}
 
     def node_vecs(self, sample: dict, j: int, cap: int = 65536):
+        return self._node_vecs(sample, j, cap, False)
+
+    def node_vecs_split(self, sample: dict, j: int, cap: int = 65536):
+        """node_vecs, and from the same run n_branch (the size of the excess list when the branch loop ends) and eligible (the
+        predicate of usher_mapper.cpp:454-455); set_difference stays the reference's figure, with its +1 when not eligible."""
+        return self._node_vecs(sample, j, cap, True)
+
+    def _node_vecs(self, sample: dict, j: int, cap: int, split: bool):
         pos = np.ascontiguousarray(sample["pos"], dtype=np.int32)
         ref = np.ascontiguousarray(sample["ref"], dtype=np.int8)
         nuc = np.ascontiguousarray(sample["nuc"], dtype=np.int8)
@@ -160,16 +170,21 @@ class OracleTree:
         nim = np.zeros(1, np.int64)
         sd = np.zeros(1, np.int32)
         hu = np.zeros(1, np.int8)
-        rc = lib().orc_node_vecs(self.h, len(pos), _p(pos), _p(ref), _p(nuc), _p(mis), j, cap,
-                                 *[_p(a) for a in ex], _p(nex), *[_p(a) for a in im], _p(nim), _p(sd), _p(hu))
+        nbr = np.zeros(1, np.int32)
+        el = np.zeros(1, np.int8)
+        args = [self.h, len(pos), _p(pos), _p(ref), _p(nuc), _p(mis), j, cap, *[_p(a) for a in ex], _p(nex), *[_p(a) for a in im], _p(nim), _p(sd), _p(hu)]
+        rc = lib().orc_node_vecs_split(*args, _p(nbr), _p(el)) if split else lib().orc_node_vecs(*args)
         assert rc == 0
 
         def pack(arrs, n):
             n = min(int(n), cap)
             return [(int(arrs[0][i]), int(arrs[1][i]), int(arrs[2][i]), int(arrs[3][i])) for i in range(n)]
 
-        return {"excess": pack(ex, nex[0]), "imputed": pack(im, nim[0]), "set_difference": int(sd[0]),
-                "has_unique": bool(hu[0])}
+        out = {"excess": pack(ex, nex[0]), "imputed": pack(im, nim[0]), "set_difference": int(sd[0]),
+               "has_unique": bool(hu[0])}
+        if split:
+            out["n_branch"], out["eligible"] = int(nbr[0]), int(el[0])
+        return out
 
 
 class ClosedFormC:

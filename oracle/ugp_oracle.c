@@ -169,7 +169,8 @@ static void orc_mapper2(const orc_tree *t, int64_t j, const orc_mut *sm, int64_t
                         orc_shared *sh, int compute_parsimony_scores, int compute_vecs,
                         int *set_difference_out, mvec *excess, mvec *imputed,
                         mvec *anc /* scratch: ancestral_mutations */,
-                        int *has_unique_out /* may be NULL */) {
+                        int *has_unique_out /* may be NULL */,
+                        int *split_out /* may be NULL: [0] the excess list's size behind the branch loop, [1] the predicate of :454-455 */) {
     int set_difference = 0;                                   /* :172 */
     int best_set_difference = sh->best_set_difference;        /* :176 */
     anc->n = 0;                                               /* :178-179 (anc_positions == positions of anc) */
@@ -226,6 +227,8 @@ static void orc_mapper2(const orc_tree *t, int64_t j, const orc_mut *sm, int64_t
     } else {
         for (int64_t a = 0; a < n_nm; a++) mv_push(anc, nm[a]);   /* :266-269 */
     }
+
+    if (split_out) split_out[0] = (compute_vecs && excess) ? (int)excess->n : 0;   /* :270, the branch loop is over */
 
     /* :275-286 ancestor walk, most recent mutation per position wins */
     {
@@ -329,10 +332,12 @@ static void orc_mapper2(const orc_tree *t, int64_t j, const orc_mut *sm, int64_t
     if (has_unique_out) *has_unique_out = has_unique;
 
     int leaf = is_leaf(t, j);
-    if (is_root(t, j) ||
+    const int eligible = is_root(t, j) ||
         ((has_unique && !leaf && (num_common_mut > 0) && (node_num_mut != num_common_mut)) ||
          (leaf && (num_common_mut > 0)) ||
-         (!has_unique && !leaf && (node_num_mut == num_common_mut)))) {          /* :454-455 */
+         (!has_unique && !leaf && (node_num_mut == num_common_mut)));            /* :454-455 */
+    if (split_out) split_out[1] = eligible;
+    if (eligible) {
         if (set_difference > sh->best_set_difference) return;                   /* :457-461 */
         const int64_t jj = sh->jidx >= 0 ? sh->jidx : j;                        /* input.j */
         int64_t num_leaves = t->num_leaves[j];                                  /* :464 */
@@ -412,7 +417,7 @@ int orc_place_sample(const orc_tree *t, int64_t n_ent, const int32_t *pos, const
     for (int64_t k = 0; k < t->n; k++) {                                      /* :389-414 */
         int sd = 0;
         ex.n = 0; im.n = 0;
-        orc_mapper2(t, k, sm, n_ent, &sh, compute_scores, compute_scores, &sd, &ex, &im, &anc, NULL);
+        orc_mapper2(t, k, sm, n_ent, &sh, compute_scores, compute_scores, &sd, &ex, &im, &anc, NULL, NULL);
         if (compute_scores) scores[k] = sd;
     }
     if (!compute_scores) {                                                    /* :416-449 */
@@ -424,7 +429,7 @@ int orc_place_sample(const orc_tree *t, int64_t n_ent, const int32_t *pos, const
         sh.best_j_vec_n = 0;
         for (int64_t l = 0; l < ntmp; l++) {
             ex.n = 0; im.n = 0;
-            orc_mapper2(t, tmp[l], sm, n_ent, &sh, 0, 1, NULL, &ex, &im, &anc, NULL);
+            orc_mapper2(t, tmp[l], sm, n_ent, &sh, 0, 1, NULL, &ex, &im, &anc, NULL, NULL);
         }
         free(tmp);
     }
@@ -459,13 +464,13 @@ int orc_node_has_unique_prefix(const orc_tree *t, int64_t n_ent, const int32_t *
     sh.best_j = 0; sh.num_best = 1;
     bjv_push(&sh, 0);
     mvec anc = {0, 0, 0}, ex = {0, 0, 0}, im = {0, 0, 0};
-    for (int64_t j = 0; j < t->n; j++) orc_mapper2(t, j, sm, n_ent, &sh, 0, 0, NULL, &ex, &im, &anc, NULL);
+    for (int64_t j = 0; j < t->n; j++) orc_mapper2(t, j, sm, n_ent, &sh, 0, 0, NULL, &ex, &im, &anc, NULL, NULL);
     sh.best_set_difference += 1;
     int64_t ntmp = sh.best_j_vec_n;
     int64_t *tmp = (int64_t *)malloc(sizeof(int64_t) * (ntmp > 0 ? ntmp : 1));
     memcpy(tmp, sh.best_j_vec, sizeof(int64_t) * ntmp);
     sh.num_best = 0; sh.best_j_vec_n = 0;
-    for (int64_t l = 0; l < ntmp; l++) { ex.n = 0; im.n = 0; orc_mapper2(t, tmp[l], sm, n_ent, &sh, 0, 1, NULL, &ex, &im, &anc, NULL); }
+    for (int64_t l = 0; l < ntmp; l++) { ex.n = 0; im.n = 0; orc_mapper2(t, tmp[l], sm, n_ent, &sh, 0, 1, NULL, &ex, &im, &anc, NULL, NULL); }
     for (int64_t j = 0; j < k && j < t->n; j++) out[j] = sh.node_has_unique[j];
     free(tmp); free(sh.node_has_unique); free(sh.best_j_vec); free(anc.v); free(ex.v); free(im.v); free(sm);
     return 0;
@@ -503,7 +508,7 @@ int orc_place_sample_list(const orc_tree *t, int64_t n_ent, const int32_t *pos, 
         ex.n = 0; im.n = 0;
         sh.jidx = jidx ? jidx[k] : k;
         sh.distance = distance ? distance[k] : 0;
-        orc_mapper2(t, nodes[k], sm, n_ent, &sh, compute_scores, 1, &sd, &ex, &im, &anc, NULL);
+        orc_mapper2(t, nodes[k], sm, n_ent, &sh, compute_scores, 1, &sd, &ex, &im, &anc, NULL, NULL);
         if (compute_scores && scores) scores[k] = sd;
     }
     *out_best = sh.best_set_difference;
@@ -529,11 +534,11 @@ int orc_place_sample_list(const orc_tree *t, int64_t n_ent, const int32_t *pos, 
  * caller-allocated with capacity cap; counts are returned through n_excess /
  * n_imputed (the true counts, even when > cap).
  */
-int orc_node_vecs(const orc_tree *t, int64_t n_ent, const int32_t *pos, const int8_t *ref,
-                  const int8_t *nuc, const int8_t *is_missing, int64_t j, int64_t cap,
-                  int32_t *ex_pos, int8_t *ex_ref, int8_t *ex_par, int8_t *ex_mut, int64_t *n_excess,
-                  int32_t *im_pos, int8_t *im_ref, int8_t *im_par, int8_t *im_mut, int64_t *n_imputed,
-                  int32_t *set_difference, int8_t *has_unique) {
+static int node_vecs_impl(const orc_tree *t, int64_t n_ent, const int32_t *pos, const int8_t *ref,
+                          const int8_t *nuc, const int8_t *is_missing, int64_t j, int64_t cap,
+                          int32_t *ex_pos, int8_t *ex_ref, int8_t *ex_par, int8_t *ex_mut, int64_t *n_excess,
+                          int32_t *im_pos, int8_t *im_ref, int8_t *im_par, int8_t *im_mut, int64_t *n_imputed,
+                          int32_t *set_difference, int8_t *has_unique, int *split) {
     orc_mut *sm = make_sample(n_ent, pos, ref, nuc, is_missing);
     orc_shared sh; memset(&sh, 0, sizeof(sh));
     sh.jidx = -1;
@@ -541,7 +546,7 @@ int orc_node_vecs(const orc_tree *t, int64_t n_ent, const int32_t *pos, const in
     sh.best_set_difference = 0x3fffffff;
     mvec anc = {0, 0, 0}, ex = {0, 0, 0}, im = {0, 0, 0};
     int sd = 0, hu = 0;
-    orc_mapper2(t, j, sm, n_ent, &sh, 1, 1, &sd, &ex, &im, &anc, &hu);
+    orc_mapper2(t, j, sm, n_ent, &sh, 1, 1, &sd, &ex, &im, &anc, &hu, split);
     for (int64_t i = 0; i < ex.n && i < cap; i++) {
         ex_pos[i] = ex.v[i].position; ex_ref[i] = ex.v[i].ref_nuc; ex_par[i] = ex.v[i].par_nuc; ex_mut[i] = ex.v[i].mut_nuc;
     }
@@ -553,6 +558,32 @@ int orc_node_vecs(const orc_tree *t, int64_t n_ent, const int32_t *pos, const in
     free(sh.node_has_unique); free(sh.best_j_vec);
     free(anc.v); free(ex.v); free(im.v); free(sm);
     return 0;
+}
+
+int orc_node_vecs(const orc_tree *t, int64_t n_ent, const int32_t *pos, const int8_t *ref,
+                  const int8_t *nuc, const int8_t *is_missing, int64_t j, int64_t cap,
+                  int32_t *ex_pos, int8_t *ex_ref, int8_t *ex_par, int8_t *ex_mut, int64_t *n_excess,
+                  int32_t *im_pos, int8_t *im_ref, int8_t *im_par, int8_t *im_mut, int64_t *n_imputed,
+                  int32_t *set_difference, int8_t *has_unique) {
+    return node_vecs_impl(t, n_ent, pos, ref, nuc, is_missing, j, cap, ex_pos, ex_ref, ex_par, ex_mut, n_excess,
+                          im_pos, im_ref, im_par, im_mut, n_imputed, set_difference, has_unique, NULL);
+}
+
+/*
+ * orc_node_vecs, and two values of the same run of mapper2_body that its score folds together: *n_branch = the size of the excess
+ * list when the branch loop (:190-270) ends, *eligible = the predicate of :454-455 (set_difference is the reference's figure, one
+ * more than the entries of the two later loops when *eligible is 0).
+ */
+int orc_node_vecs_split(const orc_tree *t, int64_t n_ent, const int32_t *pos, const int8_t *ref,
+                        const int8_t *nuc, const int8_t *is_missing, int64_t j, int64_t cap,
+                        int32_t *ex_pos, int8_t *ex_ref, int8_t *ex_par, int8_t *ex_mut, int64_t *n_excess,
+                        int32_t *im_pos, int8_t *im_ref, int8_t *im_par, int8_t *im_mut, int64_t *n_imputed,
+                        int32_t *set_difference, int8_t *has_unique, int32_t *n_branch, int8_t *eligible) {
+    int split[2] = {0, 0};
+    const int rc = node_vecs_impl(t, n_ent, pos, ref, nuc, is_missing, j, cap, ex_pos, ex_ref, ex_par, ex_mut, n_excess,
+                                  im_pos, im_ref, im_par, im_mut, n_imputed, set_difference, has_unique, split);
+    *n_branch = split[0]; *eligible = (int8_t)split[1];
+    return rc;
 }
 
 /* ------------------------------------------------- threaded CPU baseline */
@@ -601,7 +632,7 @@ static void orc_run_ranges(orc_pool *pl, orc_job *jb) {
             jb->sh.best_node_num_leaves = -1; jb->sh.best_j = -1;   /* no winner of its own at this score yet */
         }
         for (int64_t k = lo; k < hi; k++)
-            orc_mapper2(jb->t, k, jb->sm, jb->n_sm, &jb->sh, 0, 0, NULL, NULL, NULL, &anc, NULL);
+            orc_mapper2(jb->t, k, jb->sm, jb->n_sm, &jb->sh, 0, 0, NULL, NULL, NULL, &anc, NULL, NULL);
         g = __atomic_load_n(&pl->shared_best, __ATOMIC_RELAXED);
         while (jb->sh.best_set_difference < g &&
                !__atomic_compare_exchange_n(&pl->shared_best, &g, jb->sh.best_set_difference, 0, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}

@@ -1,7 +1,10 @@
-"""Placer.vectors (ugp_vectors) against the literal mapper2_body of the oracle (OracleTree.node_vecs), exactly, on every case of
-tests/vectors_cases.py: info, both offset arrays and both lists, on a handle that holds the tree's mutations and on a topology-only
-one, through every window size, with pairs shuffled and repeated, under caps, and the errors; then vectors beside the other
-families that share a handle's depth-first tables (tests/shared_tables_cases.py)."""
+"""Placer.vectors (ugp_vectors) against the literal mapper2_body of the oracle (OracleTree.node_vecs_split: the lists, and n_branch,
+eligible and the score each on its own), exactly, on every case of tests/vectors_cases.py: info, both offset arrays and both lists,
+on a handle that holds the tree's mutations and on a topology-only one, through every window size, with pairs shuffled and repeated,
+under caps, and the errors; nodes of more than 64 entries, root paths whose nodes hold 0 to 70 entries side by side, windows of one
+and two tiles of the prefix sums and a pair more or less, and seeded random trees (the picks of vectors_cases.py, whose edges
+tests/test_vectors_cpu.py proves); then vectors beside the other families that share a handle's depth-first tables
+(tests/shared_tables_cases.py)."""
 import numpy as np
 import pytest
 
@@ -21,7 +24,8 @@ WANT = {}   # case name -> {(sample, node): the oracle's answer}, computed once
 def want(case):
     if case["name"] not in WANT:
         ot = capi.OracleTree(case["arrays"])
-        WANT[case["name"]] = {(s, j): VR.oracle_answer(ot, case["samples"][s], j) for s, j in sorted(set(case["pairs"])) if j not in case["refused"]}
+        WANT[case["name"]] = {(s, j): VR.oracle_answer_split(ot, case["samples"][s], j) for s, j in sorted(set(case["pairs"]))
+                              if j not in case["refused"]}
     return WANT[case["name"]]
 
 
@@ -47,6 +51,7 @@ def check(case, pl, pairs, **kw):
         else:
             assert VR.agrees(a, w[(s, j)]), (case["name"], s, j, a, w[(s, j)])
             assert a["excess"][:a["n_branch"]] == w[(s, j)]["excess"][:a["n_branch"]]
+            assert VR.agrees_split(a, w[(s, j)]), (case["name"], s, j, a, w[(s, j)])
     return got
 
 
@@ -158,6 +163,124 @@ def test_errors_write_nothing():
     pl.close()
 
 
+# ---- the steps of 64, the tiles of the prefix sums, random trees --------------------------------------------------------------------
+
+def generated(make, *args):
+    """A case of a generator of vectors_cases.py, built once."""
+    key = (make.__name__,) + args
+    if key not in _GENERATED:
+        _GENERATED[key] = make(*args)
+        assert not _GENERATED[key]["refused"]
+    return _GENERATED[key]
+
+
+_GENERATED = {}
+
+
+@pytest.mark.parametrize("pick", VC.WIDE_PICKS, ids=lambda p: "-".join(map(str, p)))
+def test_wide_nodes(pick):
+    """A node of 63 .. 200 own entries in ascending, descending and shuffled stored order, with a masked entry on and around the
+    seam of two steps of 64, as an internal node, as a leaf and as the root: all pairs in one call, and a pair a window."""
+    case = generated(VC.wide, *pick)
+    pl = bare(case)
+    whole = check(case, pl, case["pairs"])
+    single = check(case, pl, case["pairs"], chunk_pairs=1)
+    assert all(np.array_equal(a, b) for a, b in zip(single, whole))
+    pl.close()
+    masked = (np.asarray(case["arrays"]["mut_pos"]) < 0).any()
+    try:
+        pl = Placer(case["arrays"])
+    except UgpError as e:   # the placement tables may refuse a masked entry, nothing else here
+        assert e.code == -2 and masked, case["name"]
+        return
+    pl.vectors_attach()
+    got = check(case, pl, case["pairs"])
+    assert all(np.array_equal(a, b) for a, b in zip(got, whole))
+    pl.close()
+
+
+@pytest.mark.parametrize("pick", VC.RAGGED_PICKS, ids=lambda p: "%d-%s" % (p[0], "".join(map(str, p[1]))))
+def test_ragged_paths(pick):
+    """Root paths whose nodes hold 0, 1, 2, 3, 7 and 70 entries side by side in one step of 64 lanes, of 2 .. 202 nodes."""
+    case = generated(VC.ragged_path, *pick)
+    pl = bare(case)
+    check(case, pl, case["pairs"])
+    pl.close()
+
+
+def expected_arrays(case, pairs):
+    """What Placer.vectors must return for `pairs`, as arrays, from the oracle's answers to the distinct pairs."""
+    w = want(case)
+    one = {}
+    for pr in set(pairs):
+        o = w[pr]
+        info = np.zeros(1, Placer.VEC_INFO)
+        info[0] = (len(o["excess"]), len(o["imputed"]), o["n_branch"], o["set_difference"] - (0 if o["eligible"] else 1), o["has_unique"],
+                   o["eligible"], 0, 0)
+        ent = lambda l: np.asarray([(p, r, a, n, 0) for p, r, a, n in l], Placer.VEC_ENTRY).reshape(-1)
+        one[pr] = (info, ent(o["excess"]), ent(o["imputed"]))
+    info, ex, im = (np.concatenate([one[pr][k] for pr in pairs]) for k in range(3))
+    off = lambda c: np.concatenate([[0], np.cumsum(c, dtype=np.uint64)]).astype(np.uint64)
+    return info, off(info["n_excess"]), ex, off(info["n_imputed"]), im
+
+
+@pytest.mark.parametrize("both", [False, True], ids=["empty_empty_part3", "both_lists"])
+def test_window_seams(both):
+    """One tile of k_vec_scan less a pair, one tile, one more, two tiles, two and a pair, in one window: at the seam of the first two
+    tiles two pairs without any entry and one with entries of part 3, or three pairs with both lists.  Every returned array against
+    the oracle's; the largest count once more in windows of a tile less and more a pair; caps that cut inside the pair on the seam."""
+    case = next(c for c in CASES if c["name"] == VC.SEAM_CASE)
+    pl = bare(case)
+    q = QueryBatch(case["samples"])
+    w = want(case)
+    for n in VC.SEAM_COUNTS:
+        pairs = VC.seam_pairs(n, both)
+        nodes, smp = [j for _, j in pairs], [s for s, _ in pairs]
+        exp = expected_arrays(case, pairs)
+        got = pl.vectors(q, nodes, smp)
+        for name, a, b in zip(("info", "ex_off", "excess", "im_off", "imputed"), got, exp):
+            assert np.array_equal(a, b), (n, name, np.flatnonzero(a != b)[:4] if len(a) == len(b) else (len(a), len(b)))
+        assert pl._vec_totals == (len(exp[2]), len(exp[4]))
+        lo = max(0, VC.SEAM_TILE - 3)
+        for pr, a in zip(pairs[lo:lo + 6], VR.device_answers(got[0][lo:lo + 6], got[1][lo:lo + 7], got[2], got[3][lo:lo + 7], got[4])):
+            assert VR.agrees_split(a, w[pr]), (n, pr)
+        if n == VC.SEAM_COUNTS[-1]:
+            for chunk in (VC.SEAM_TILE - 1, VC.SEAM_TILE + 1):
+                again = pl.vectors(q, nodes, smp, chunk_pairs=chunk)
+                assert all(np.array_equal(a, b) for a, b in zip(again, got)), chunk
+        if both and n == VC.SEAM_TILE + 1:   # the caps end one entry into the lists of the pair at the head of the second tile
+            cap_ex, cap_im = int(exp[1][VC.SEAM_TILE]) + 1, int(exp[3][VC.SEAM_TILE]) + 1
+            assert cap_ex < int(exp[1][VC.SEAM_TILE + 1]) and cap_im < int(exp[3][VC.SEAM_TILE + 1])
+            cut = pl.vectors(q, nodes, smp, ex_cap=cap_ex, im_cap=cap_im)
+            assert pl._vec_totals == (len(exp[2]), len(exp[4]))
+            assert np.array_equal(cut[0], exp[0]) and np.array_equal(cut[1], exp[1]) and np.array_equal(cut[3], exp[3])
+            assert len(cut[2]) == cap_ex and np.array_equal(cut[2], exp[2][:cap_ex])
+            assert len(cut[4]) == cap_im and np.array_equal(cut[4], exp[4][:cap_im])
+    pl.close()
+
+
+def test_random_trees_on_the_device():
+    """Every node for every sample of a dozen seeded random trees of up to 150 nodes and 80 entries a node, one call a tree."""
+    pairs = part3 = branch = 0
+    for pick in VC.RANDOM_PICKS:
+        case = generated(VC.random_case, *pick)
+        pl = bare(case)
+        info = check(case, pl, case["pairs"])[0]
+        pl.close()
+        pairs += len(info)
+        branch += int((info["n_branch"] > 0).sum())
+        part3 += int((info["n_excess"] > info["n_branch"] + np.asarray([_part2(case, s, j) for s, j in case["pairs"]])).sum())
+    assert pairs >= 4000 and part3 >= 2000 and branch >= 500, (pairs, part3, branch)
+
+
+def _part2(case, s, j):
+    """The entries of part 2 in the oracle's answer: those behind the branch's at the position of a non-missing row of the sample
+    (part 3 has entries only where the sample has no row)."""
+    smp, o = case["samples"][s], want(case)[(s, j)]
+    rows = {int(p) for p, m in zip(smp["pos"], smp["is_missing"]) if not m}
+    return sum(1 for p, _, _, _ in o["excess"][o["n_branch"]:] if p in rows)
+
+
 # ---- beside the families that share the depth-first tables ----------------------------------------------------------------------------
 
 def shared_questions(t):
@@ -172,7 +295,7 @@ def shared_questions(t):
                     "is_missing": np.asarray([a is None for _, a in rows(k)], np.int8)} for k in range(3)]
     pairs = [(s, j) for s in range(len(queries)) for j in t.nodes + [0]]
     ot = capi.OracleTree(t.X)
-    return queries, pairs, [VR.oracle_answer(ot, queries[s], j) for s, j in pairs]
+    return queries, pairs, [VR.oracle_answer_split(ot, queries[s], j) for s, j in pairs]
 
 
 _SHARED = {}
@@ -184,7 +307,7 @@ def vectors_answer(t, pl, why):
     queries, pairs, wanted = _SHARED[t.name]
     ans = VR.device_answers(*pl.vectors(QueryBatch(queries), [j for _, j in pairs], [s for s, _ in pairs]))
     for a, w, pr in zip(ans, wanted, pairs):
-        assert not a["refused"] and VR.agrees(a, w), (t.name, pr, why)
+        assert not a["refused"] and VR.agrees(a, w) and VR.agrees_split(a, w), (t.name, pr, why)
 
 
 @pytest.mark.parametrize("tree", ("plain", "bare"))

@@ -1,7 +1,9 @@
 """The closed form of ugp_vectors (usher_amd/csrc/ugp_vectors.hip) written down in Python over the per-position owner lists, step by
 step as the kernels compute it: the refusal, loop 1 with its merge pointer as a prefix maximum, the nearest owner g(p) of every row,
 the back-mutations of the root path ordered by position.  tests/test_vectors_cpu.py holds it against the literal mapper2_body of the
-oracle (OracleTree.node_vecs); the device is held against the oracle too, so this file only says WHY the kernel is right.
+oracle (OracleTree.node_vecs_split); the device is held against the oracle too, so this file only says WHY the kernel is right --
+and, through the trace and the faults of vectors(), WHERE a pair puts the kernel's steps of 64 and what a kernel that lost one piece
+of their bookkeeping would answer.
 """
 from bisect import bisect_left, bisect_right
 
@@ -98,8 +100,18 @@ def _probe(r, p, nuc):
     return lb, after, here, match, miss
 
 
-def vectors(T, sample, j_bfs):
-    """What ugp_vectors answers for one pair: a dict with the fields of ugp_vec_info and the two lists of (pos, ref, par, nuc)."""
+FAULTS = ("carry", "stop", "nm")   # the kernel's wave bookkeeping undone, one piece at a time: see vectors()
+
+
+def vectors(T, sample, j_bfs, trace=None, fault=None):
+    """What ugp_vectors answers for one pair: a dict with the fields of ugp_vec_info and the two lists of (pos, ref, par, nuc).
+    trace: a dict that receives what the kernel's 64-entry steps meet on this pair -- stop (br.stop - e0), nm, allvis, passed (per
+    passed entry its index, the index of the first entry that left the pointer behind its row, and whether only the pointer carried
+    in from an earlier step hides the row), own_asks (index, here) of every own_kept question, part3 (node, index within the node,
+    masked) of every entry of part 3 in the order found.  fault: the answer of a kernel that lost one piece of that bookkeeping --
+    "carry": start is not carried from one step of 64 to the next; "stop": br.stop = base instead of base + first_masked; "nm": the
+    masked entry is not counted.  Only tests/test_vectors_cpu.py passes one, to show that the cases would notice."""
+    assert fault is None or fault in FAULTS
     r = _Rows(sample)
     j = T.bfs2dfs[j_bfs]
     e0, e1 = T.moff[j], T.moff[j + 1]
@@ -107,13 +119,26 @@ def vectors(T, sample, j_bfs):
         return {"refused": 1, "excess": [], "imputed": [], "n_branch": 0, "set_difference": 0, "has_unique": 0, "eligible": 0}
     # part 1
     kept_e, start, stop, nm, common, hu, part1 = set(), 0, e1, 0, 0, False, []
+    afters, local, passed = [], 0, []
     if j != 0:
         for e in range(e0, e1):
+            if (e - e0) % 64 == 0:               # a new step of 64 lanes
+                local = 0
+                if fault == "carry":
+                    start = 0
             nm += 1
             if T.mpos[e] < 0:
                 hu, stop = True, e
+                if fault == "stop":
+                    stop = e - (e - e0) % 64
+                if fault == "nm":
+                    nm -= 1
                 break
             lb, after, here, match, miss = _probe(r, T.mpos[e], T.mnuc[e])
+            if here and lb < start:
+                passed.append((e - e0, next(x for x, a in enumerate(afters) if a > lb), lb >= local))
+            afters.append(after)
+            local = max(local, after)
             seen = here and lb >= start          # a row the pointer has passed is not seen
             kept = match if seen else T.mnuc[e] == T.mref[e]
             if kept:
@@ -124,8 +149,10 @@ def vectors(T, sample, j_bfs):
             else:
                 hu = True
             start = max(start, after)
+        kept_e = {e for e in kept_e if e < stop}
+    own_asks, found3 = [], []
 
-    def nearest_owner(p):
+    def nearest_owner(p, here):
         on = T.onode.get(p)
         if not on:
             return NIL
@@ -133,8 +160,10 @@ def vectors(T, sample, j_bfs):
         cur = T.pent[p][x - 1] if x else NIL
         while cur != NIL and j >= T.dend[T.mnode[cur]]:
             cur = T.mlink[cur]
-        if cur != NIL and j != 0 and T.mnode[cur] == j and cur not in kept_e:
-            cur = T.mlink[cur]
+        if cur != NIL and j != 0 and T.mnode[cur] == j:
+            own_asks.append((cur - e0, here))
+            if cur not in kept_e:
+                cur = T.mlink[cur]
         return cur
 
     # part 2 and the imputed list
@@ -143,7 +172,7 @@ def vectors(T, sample, j_bfs):
         if r.mis[k]:
             continue
         p, rr, a = r.pos[k], r.ref[k], r.nuc[k]
-        cur = nearest_owner(p)
+        cur = nearest_owner(p, True)
         anc = T.mnuc[cur] if cur != NIL else rr
         found, has_ref, amb = cur != NIL and (a & anc) != 0, (a & rr) != 0, (a & (a - 1)) != 0
         if found:
@@ -165,17 +194,22 @@ def vectors(T, sample, j_bfs):
                 continue
             if T.mpos[e] < 0:
                 masked.append((T.mpos[e], T.mref[e], T.mnuc[e], T.mref[e]))
+                found3.append((0, e - e0, True))
             elif T.mpos[e] not in rowpos:
                 back.append((T.mpos[e], T.mref[e], T.mnuc[e], T.mref[e]))
+                found3.append((0, e - e0, False))
     else:
         v = j
         while v != NIL:
             for e in range(T.moff[v], T.moff[v + 1]):
                 p = T.mpos[e]
-                if p >= 0 and T.owner[e] and T.mnuc[e] != T.mref[e] and p not in rowpos and nearest_owner(p) == e:
+                if p >= 0 and T.owner[e] and T.mnuc[e] != T.mref[e] and p not in rowpos and nearest_owner(p, False) == e:
                     back.append((p, T.mref[e], T.mnuc[e], T.mref[e]))
+                    found3.append((v, e - T.moff[v], False))
             v = T.dpar[v]
     part3 = masked + sorted(back)
+    if trace is not None:
+        trace.update(stop=stop - e0, nm=nm, allvis=not passed, passed=passed, own_asks=own_asks, part3=found3)
     lf = T.leaf[j]
     eligible = j == 0 or (hu and not lf and common > 0 and nm != common) or (lf and common > 0) or (not hu and not lf and nm == common)
     return {"refused": 0, "excess": part1 + part2 + part3, "imputed": imputed, "n_branch": len(part1), "set_difference": len(part2) + len(part3),
@@ -187,6 +221,21 @@ def oracle_answer(ot, sample, j_bfs):
     o = ot.node_vecs(sample, int(j_bfs))
     u = lambda l: [(p, a & 255, b & 255, c & 255) for p, a, b, c in l]
     return {"excess": u(o["excess"]), "imputed": u(o["imputed"]), "set_difference": o["set_difference"], "has_unique": int(o["has_unique"])}
+
+
+def oracle_answer_split(ot, sample, j_bfs):
+    """oracle_answer with the two fields the score folds together: n_branch and eligible, from OracleTree.node_vecs_split."""
+    o = ot.node_vecs_split(sample, int(j_bfs))
+    u = lambda l: [(p, a & 255, b & 255, c & 255) for p, a, b, c in l]
+    return {"excess": u(o["excess"]), "imputed": u(o["imputed"]), "set_difference": o["set_difference"], "has_unique": int(o["has_unique"]),
+            "n_branch": o["n_branch"], "eligible": o["eligible"]}
+
+
+def agrees_split(mine, orc):
+    """agrees, and n_branch, eligible and set_difference (the score before the +1) each on its own, exactly: orc is an
+    oracle_answer_split."""
+    return (agrees(mine, orc) and mine["n_branch"] == orc["n_branch"] and mine["eligible"] == orc["eligible"]
+            and mine["set_difference"] == orc["set_difference"] - (0 if orc["eligible"] else 1))
 
 
 def agrees(mine, orc):
