@@ -36,6 +36,7 @@ from tests import synth
 from tests import translate_cases as TC
 from tests import translate_ref as TR
 from tests import uncertainty_ref as UR
+from tests import vectors_ref as VR
 from usher_amd import Placer, QueryBatch
 
 NAMES = ("uncertainty", "annotate", "nearest", "relatives", "select", "mask", "subtree", "genotypes", "summary", "translate", "haplotypes")
@@ -203,6 +204,10 @@ class Family:
         if which not in self._wants:
             self._wants[which] = self.want(self.tree.X if which == "X" else self.tree.Y[which])
         return self._wants[which]
+
+    def check(self, pl, why):
+        """ask(pl) equals the reference's answer for X, exactly."""
+        assert self.ask(pl) == self.wanted(), (self.tree.name, self.name, why)
 
     def call_unattached(self, pl):
         L, h = pl._L, pl._h
@@ -408,6 +413,59 @@ def families(tree):
     if tree.name not in _FAMILIES:
         _FAMILIES[tree.name] = [Family(tree, name) for name in NAMES]
     return _FAMILIES[tree.name]
+
+
+# ---- vectors, which asks about (sample, node) pairs and so brings samples of its own --------------------------------------------------
+
+def vectors_questions(t):
+    if t.name == "plain":
+        arrays, queries = synth.make_case(2, n_leaves=250, n_queries=4, n_sites=60, genome_len=500)
+        assert np.array_equal(arrays["mut_pos"], t.X["mut_pos"]) and np.array_equal(arrays["mut_off"], t.X["mut_off"])
+    else:
+        ref = lambda p: ONEHOT[p % 4]
+        rows = lambda k: [(p, (None, 15 ^ ref(p), [a for a in ONEHOT if a != ref(p)][k % 3], ref(p) | 8)[(p // 2 + k) % 4]) for p in range(3 + 2 * k, 93, 6)]
+        queries = [{"name": "b%d" % k, "pos": np.asarray([p for p, _ in rows(k)], np.int32), "ref": np.asarray([ref(p) for p, _ in rows(k)], np.int8),
+                    "nuc": np.asarray([15 if a is None else a for _, a in rows(k)], np.int8),
+                    "is_missing": np.asarray([a is None for _, a in rows(k)], np.int8)} for k in range(3)]
+    pairs = [(s, j) for s in range(len(queries)) for j in t.nodes + [0]]
+    ot = capi.OracleTree(t.X)
+    return queries, pairs, [VR.oracle_answer_split(ot, queries[s], j) for s, j in pairs]
+
+
+_VECTORS = {}
+
+
+def vectors_asked(t):
+    """(queries, pairs, the oracle's answers) of a tree, computed once."""
+    if t.name not in _VECTORS:
+        _VECTORS[t.name] = vectors_questions(t)
+    return _VECTORS[t.name]
+
+
+def vectors_answer(t, pl, why):
+    queries, pairs, wanted = vectors_asked(t)
+    ans = VR.device_answers(*pl.vectors(QueryBatch(queries), [j for _, j in pairs], [s for s, _ in pairs]))
+    for a, w, pr in zip(ans, wanted, pairs):
+        assert not a["refused"] and VR.agrees(a, w) and VR.agrees_split(a, w), (t.name, pr, why)
+
+
+class Vectors:
+    """Vectors with the face of a Family, as far as attach and check go."""
+    name = "vectors"
+
+    def __init__(self, tree):
+        self.tree = tree
+
+    def attach(self, pl, arrays):
+        pl.vectors_attach(arrays)
+
+    def check(self, pl, why):
+        vectors_answer(self.tree, pl, why)
+
+
+def family(t, name):
+    """The Family of that name, or Vectors: something with attach(pl, arrays) and check(pl, why)."""
+    return Vectors(t) if name == "vectors" else next(f for f in families(t) if f.name == name)
 
 
 def flat(x):

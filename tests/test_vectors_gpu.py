@@ -11,7 +11,6 @@ import pytest
 from oracle import capi
 from tests import shared_tables_cases as S
 from tests import summary_cases as SMC
-from tests import synth
 from tests import vectors_cases as VC
 from tests import vectors_ref as VR
 from usher_amd import Placer, QueryBatch, UgpError
@@ -283,31 +282,7 @@ def _part2(case, s, j):
 
 # ---- beside the families that share the depth-first tables ----------------------------------------------------------------------------
 
-def shared_questions(t):
-    if t.name == "plain":
-        arrays, queries = synth.make_case(2, n_leaves=250, n_queries=4, n_sites=60, genome_len=500)
-        assert np.array_equal(arrays["mut_pos"], t.X["mut_pos"]) and np.array_equal(arrays["mut_off"], t.X["mut_off"])
-    else:
-        ref = lambda p: S.ONEHOT[p % 4]
-        rows = lambda k: [(p, (None, 15 ^ ref(p), [a for a in S.ONEHOT if a != ref(p)][k % 3], ref(p) | 8)[(p // 2 + k) % 4]) for p in range(3 + 2 * k, 93, 6)]
-        queries = [{"name": "b%d" % k, "pos": np.asarray([p for p, _ in rows(k)], np.int32), "ref": np.asarray([ref(p) for p, _ in rows(k)], np.int8),
-                    "nuc": np.asarray([15 if a is None else a for _, a in rows(k)], np.int8),
-                    "is_missing": np.asarray([a is None for _, a in rows(k)], np.int8)} for k in range(3)]
-    pairs = [(s, j) for s in range(len(queries)) for j in t.nodes + [0]]
-    ot = capi.OracleTree(t.X)
-    return queries, pairs, [VR.oracle_answer_split(ot, queries[s], j) for s, j in pairs]
-
-
-_SHARED = {}
-
-
-def vectors_answer(t, pl, why):
-    if t.name not in _SHARED:
-        _SHARED[t.name] = shared_questions(t)
-    queries, pairs, wanted = _SHARED[t.name]
-    ans = VR.device_answers(*pl.vectors(QueryBatch(queries), [j for _, j in pairs], [s for s, _ in pairs]))
-    for a, w, pr in zip(ans, wanted, pairs):
-        assert not a["refused"] and VR.agrees(a, w) and VR.agrees_split(a, w), (t.name, pr, why)
+vectors_answer = S.vectors_answer   # the questions and the oracle's answers live beside the other families'
 
 
 @pytest.mark.parametrize("tree", ("plain", "bare"))

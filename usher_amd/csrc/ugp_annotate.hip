@@ -27,7 +27,7 @@
 #include <vector>
 
 #include "ugp_annotate.hpp"
-#include "ugp_dense.hpp"
+#include "ugp_query.hpp"
 
 namespace ugp {
 namespace {
@@ -187,47 +187,26 @@ __global__ void __launch_bounds__(kBlock) k_tiewrite(DfsView t, Search S) {
 
 }  // namespace
 
-struct AnnState {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    const DfsTables *T = nullptr;   // the handle's
+struct AnnState : QueryBase {
     // per call
     DBuf<uint32_t> xs, cid, coff, len, ecnt, voff, eoff, cvoff, vis, vcl, veoff, oent, pc, pu, dout;
     DBuf<int32_t> ocnt;
     DBuf<int32_t> qpos, gpos, diff, seg, mn;
     DBuf<uint16_t> qnr, grow;
     DBuf<uint32_t> goff, tab, scnt, soff, total, ties;
-    ~AnnState() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
-void ann_free(AnnState *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    delete s;
-}
+void ann_free(AnnState *s) { query_free(s); }
 
 int ann_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
                DfsTables **tables, AnnState **out) {
-    if (!out) return set_error(UGP_ERR_INVALID, "null argument");
-    const int rc = dfs_tables(tree, dfs2bfs, bfs2dfs, device, 31, tables);
-    if (rc) return rc;
-    try {
-        if (int same = dfs_tables_same_arrays(**tables, tree, dfs2bfs, "ugp_annotate_attach")) return same;
-    } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }
-    AnnState *S = new (std::nothrow) AnnState();
-    if (!S) return set_error(UGP_ERR_NOMEM, "out of host memory");
-    S->device = device;
-    S->T = *tables;
-    const uint32_t tp = std::max<uint32_t>(S->T->tp, 1);
-    if (hipSetDevice(device) != hipSuccess) { delete S; return set_error(UGP_ERR_HIP, "hipSetDevice failed"); }
-    hipError_t err = hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking);
-    if (err == hipSuccess) err = S->tab.alloc(tp);
-    if (err == hipSuccess) err = hipMemsetAsync(S->tab.p, 0, (size_t)tp * sizeof(uint32_t), S->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(S->stream);
-    if (err != hipSuccess) { delete S; return set_error(UGP_ERR_HIP, std::string("annotate tables: ") + hipGetErrorString(err)); }
-    ann_free(*out);
-    *out = S;
-    return UGP_OK;
+    return query_attach("ugp_annotate_attach", tree, dfs2bfs, bfs2dfs, device, 31, tables, out, NoCheck(), [](AnnState *S) {
+        const uint32_t tp = std::max<uint32_t>(S->T->tp, 1);
+        hipError_t err = S->tab.alloc(tp);
+        if (err == hipSuccess) err = hipMemsetAsync(S->tab.p, 0, (size_t)tp * sizeof(uint32_t), S->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(S->stream);
+        return hip_rc("ugp_annotate_attach", err);
+    });
 }
 
 namespace {

@@ -317,7 +317,7 @@ struct ugp_mat {
     ugp::MskState *msk = nullptr;    // matUtils mask tables (ugp_mask_attach), or none
     ugp::SubState *sub = nullptr;    // induced-subtree tables (ugp_subtree_attach), or none
     ugp::HpState *hp = nullptr;      // matUtils summary --haplotype tables (ugp_haplotypes_attach), or none
-    ugp::DfsTables *dfs = nullptr;   // the depth-first tables uncertainty and annotate share (their first attach), or none
+    ugp::DfsTables *dfs = nullptr;   // the depth-first tables every query family reads (made by the first attach), or none
     hipEvent_t kb_done = nullptr;    // behind the latest k_best8 launch of this handle ...
     hipStream_t kb_done_on = nullptr;   // ... on this stream
 };
@@ -1881,8 +1881,9 @@ int ugp_subtree_mask(ugp_mat *m, uint32_t order, uint32_t root_j, uint32_t max_l
 
 // ---- matUtils uncertainty (ugp_uncertainty.hip) ----------------------------------------------------------------------
 
-// The attach calls take the handle's own tree (same parent array) and its depth-first expansion.
+// What every attach call begins with: it takes the handle's own tree (same parent array) and its depth-first expansion.
 static int check_handle_tree(ugp_mat *m, const ugp_tree_desc *tree) {
+    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
     const uint64_t N = m->flat.n_nodes;
     if (m->h_parent.size() != N) return fail(UGP_ERR_INVALID, "this handle has no host topology (created from a coarse tree?)");
     if (tree->n_nodes != N) return fail(UGP_ERR_INVALID, "the tree is not the handle's tree (node count)");
@@ -1893,7 +1894,6 @@ static int check_handle_tree(ugp_mat *m, const ugp_tree_desc *tree) {
 }
 
 int ugp_uncertainty_attach(ugp_mat *m, const ugp_tree_desc *tree) {
-    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
     if (int rc = check_handle_tree(m, tree)) return rc;
     return ugp::unc_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->unc);
 }
@@ -1907,7 +1907,6 @@ int ugp_uncertainty(ugp_mat *m, const uint32_t *nodes, uint64_t n, uint32_t cap,
 // ---- matUtils annotate (ugp_annotate.hip) --------------------------------------------------------------------------
 
 int ugp_annotate_attach(ugp_mat *m, const ugp_tree_desc *tree) {
-    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
     if (int rc = check_handle_tree(m, tree)) return rc;
     return ugp::ann_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->ann);
 }
@@ -1932,7 +1931,6 @@ int ugp_annotate_search(ugp_mat *m, const ugp_queries *q, uint32_t cap, int32_t 
 // ---- matUtils extract: k nearest samples (ugp_nearest.hip) -----------------------------------------------------------
 
 int ugp_nearest_attach(ugp_mat *m, const ugp_tree_desc *tree) {
-    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
     if (int rc = check_handle_tree(m, tree)) return rc;
     return ugp::nk_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->near);
 }
@@ -1951,7 +1949,6 @@ int ugp_nearest_k(ugp_mat *m, uint64_t n_queries, const uint32_t *nodes, const u
 // ---- matUtils extract: per-sample relatives (ugp_relatives.hip) ----------------------------------------------------------
 
 int ugp_relatives_attach(ugp_mat *m, const ugp_tree_desc *tree, const uint32_t *name_rank) {
-    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
     if (int rc = check_handle_tree(m, tree)) return rc;
     return ugp::rel_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, name_rank, &m->dfs, &m->rel);
 }
@@ -1995,7 +1992,6 @@ int ugp_relatives_time(ugp_mat *m, uint64_t n, const uint32_t *nodes, int within
 // ---- matUtils extract: sample selectors as leaf-rank bitmaps (ugp_select.hip) --------------------------------------------
 
 int ugp_select_attach(ugp_mat *m, const ugp_tree_desc *tree) {
-    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
     if (int rc = check_handle_tree(m, tree)) return rc;
     return ugp::sel_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->sel);
 }
@@ -2037,7 +2033,6 @@ int ugp_select_time(ugp_mat *m, uint64_t n_mut, const int32_t *pos, const uint8_
 // ---- the excess and imputed mutations of (sample, node) pairs (ugp_vectors.hip) -------------------------------------------
 
 int ugp_vectors_attach(ugp_mat *m, const ugp_tree_desc *tree) {
-    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
     if (int rc = check_handle_tree(m, tree)) return rc;
     return ugp::vec_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->vec);
 }
@@ -2091,7 +2086,6 @@ int ugp_vectors_time(ugp_mat *m, const ugp_queries *q, uint64_t n_pairs, const u
 // ---- matUtils mask: restricted samples and masked mutations in closed form (ugp_mask.hip) ---------------------------------
 
 int ugp_mask_attach(ugp_mat *m, const ugp_tree_desc *tree) {
-    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
     if (int rc = check_handle_tree(m, tree)) return rc;
     return ugp::msk_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->msk);
 }
@@ -2124,7 +2118,6 @@ int ugp_mask_time(ugp_mat *m, uint64_t n, const uint32_t *leaves_bfs, uint64_t n
 // ---- the subtree induced by a selection, in closed form (ugp_subtree.hip) ------------------------------------------------
 
 int ugp_subtree_attach(ugp_mat *m, const ugp_tree_desc *tree) {
-    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
     if (int rc = check_handle_tree(m, tree)) return rc;
     return ugp::sub_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->sub);
 }
@@ -2187,7 +2180,6 @@ int ugp_subtree_batch_time(ugp_mat *m, uint64_t n_sel, const uint64_t *sel_off, 
 // ---- matUtils extract -v: genotypes of a selection (ugp_genotypes.hip) -------------------------------------------------
 
 int ugp_genotypes_attach(ugp_mat *m, const ugp_tree_desc *tree) {
-    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
     if (int rc = check_handle_tree(m, tree)) return rc;
     return ugp::gt_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->gt);
 }
@@ -2222,7 +2214,6 @@ int ugp_genotype_rows_time(ugp_mat *m, uint64_t lo, uint64_t hi, uint32_t reps, 
 // ---- matUtils summary: mutation table, RoHo records, clade counts (ugp_summary.hip) -----------------------------------
 
 int ugp_summary_attach(ugp_mat *m, const ugp_tree_desc *tree) {
-    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
     if (int rc = check_handle_tree(m, tree)) return rc;
     return ugp::sm_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->sm);
 }
@@ -2257,7 +2248,6 @@ int ugp_summary_time(ugp_mat *m, uint32_t reps, double *sort_ms, double *roho_ms
 // ---- matUtils summary --translate: codon changes per node (ugp_translate.hip) ------------------------------------------
 
 int ugp_translate_attach(ugp_mat *m, const ugp_tree_desc *tree) {
-    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
     if (int rc = check_handle_tree(m, tree)) return rc;
     return ugp::tr_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->tr);
 }
@@ -2284,7 +2274,6 @@ int ugp_translate_time(ugp_mat *m, uint32_t reps, double *ms) {
 // ---- matUtils summary --haplotype: the distinct haplotypes of the leaves (ugp_haplotypes.hip) ----------------------------
 
 int ugp_haplotypes_attach(ugp_mat *m, const ugp_tree_desc *tree) {
-    if (!m || !tree || !tree->parent) return fail(UGP_ERR_INVALID, "null argument");
     if (int rc = check_handle_tree(m, tree)) return rc;
     return ugp::hp_attach(tree, m->h_dfs2bfs, m->h_bfs2dfs, m->device, &m->dfs, &m->hp);
 }
@@ -2316,7 +2305,7 @@ int ugp_haplotype_time(ugp_mat *m, uint32_t reps, double *scan_ms, double *sort_
 // ---- RIPPLES (ugp_ripples.hip) -----------------------------------------------------------------------------------------
 
 int ugp_ripples_attach(ugp_mat *m, const ugp_tree_desc *tree, const uint32_t *name_rank) {
-    if (!m || !tree || !tree->parent || !name_rank) return fail(UGP_ERR_INVALID, "null argument");
+    if (!name_rank) return fail(UGP_ERR_INVALID, "null argument");
     if (int rc = check_handle_tree(m, tree)) return rc;
     return ugp::rip_attach(tree, name_rank, m->h_bfs2dfs, m->device, &m->rip);
 }

@@ -1,4 +1,5 @@
-// ugp_dense.cpp -- the depth-first tables of a handle's tree (ugp_dense.hpp), built once for uncertainty and annotate.
+// ugp_dense.cpp -- the depth-first tables of a handle's tree (ugp_dense.hpp), built by the first attach of a handle and read by every
+// query family, with the host helpers their attaches share: the same-arrays check, the leaf ranks and the stored alleles.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,8 +14,8 @@
 namespace ugp {
 
 int dfs_tables_same_arrays(const DfsTables &T, const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const char *who) {
-    const std::string other = std::string("the handle's depth-first tables were built from other mutation arrays (an earlier uncertainty, annotate, "
-                                          "nearest, genotypes, summary, translate or relatives attach): ") + who + " needs the arrays of that attach, or a handle of its own";
+    const std::string other = std::string("the handle's depth-first tables were built from other mutation arrays (an earlier attach of this handle): ") +
+                              who + " needs the arrays of that attach, or a handle of its own";
     const uint64_t M = tree->mut_off[tree->n_nodes];
     if (T.m != M || T.n != tree->n_nodes) return set_error(UGP_ERR_INVALID, other);
     if (hipSetDevice(T.device) != hipSuccess) return set_error(UGP_ERR_HIP, "hipSetDevice failed");
@@ -54,6 +55,29 @@ void leaf_ranks(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs,
     for (uint32_t i = N; i-- > 1;) sz[bfs2dfs[tree->parent[dfs2bfs[i]]]] += sz[i];
     out->dend.resize(N);
     for (uint32_t i = 0; i < N; i++) out->dend[i] = i + sz[i];
+}
+
+int stored_alleles(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const DfsTables &T, const char *who, std::vector<uint8_t> *mpn) {
+    mpn->clear();
+    mpn->reserve(T.m);
+    for (uint32_t b : dfs2bfs)
+        for (uint64_t e = tree->mut_off[b]; e < tree->mut_off[b + 1]; e++) {
+            if (tree->mut_par[e] > 15 || tree->mut_nuc[e] > 15)
+                return set_error(UGP_ERR_UNSUPPORTED, std::string(who) + ": entry " + std::to_string(e) + " has an allele above 15");
+            mpn->push_back((uint8_t)(tree->mut_par[e] << 4 | tree->mut_nuc[e]));
+        }
+    if (mpn->size() != T.m) return set_error(UGP_ERR_INVALID, std::string(who) + ": the tables hold another number of entries");
+    return UGP_OK;
+}
+
+int coded_alleles(const ugp_tree_desc *tree, const DfsTables &T, const std::string &needs) {
+    if (T.m && !tree->mut_par) return set_error(UGP_ERR_INVALID, needs);
+    for (uint64_t k = 0; k < T.m; k++) {
+        if (tree->mut_pos[k] < 0) continue;
+        if (tree->mut_nuc[k] < 1 || tree->mut_nuc[k] > 15 || tree->mut_par[k] < 1 || tree->mut_par[k] > 15)
+            return set_error(UGP_ERR_UNSUPPORTED, "mut_nuc / mut_par of a non-masked mutation outside 1 .. 15");
+    }
+    return UGP_OK;
 }
 
 void dfs_tables_free(DfsTables *t) {

@@ -1,5 +1,5 @@
-// ugp_dense.hpp -- what the dense searches of ugp_uncertainty.hip and ugp_annotate.hip share, and the helpers RIPPLES
-// (ugp_ripples.hip) reads too: device buffers, the error macro, the entry bits and loop 2 of mapper2_body, the scans (ugp_scan.hpp), the
+// ugp_dense.hpp -- what the device query families share on the device and in their tables (ugp_query.hpp: the host code around
+// them), and the helpers RIPPLES (ugp_ripples.hip) reads too: device buffers, the error macro, the entry bits and loop 2 of mapper2_body, the scans (ugp_scan.hpp), the
 // depth-first tables of a handle's tree and the literal score of one node against one sample.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -101,7 +101,7 @@ struct DfsView {   // device tables, indexed by depth-first position / depth-fir
     const uint8_t *mflag, *leaf;
 };
 
-// Built by the first uncertainty or annotate attach of a handle and read by both.  Entries follow their nodes' depth-first
+// Built by the first attach of a handle, of whichever family, and read by all.  Entries follow their nodes' depth-first
 // order, and their stored order within a node (morig: index in the caller's CSR).  The OWNER of a position on a node is its
 // first non-masked entry there; poff / pent list the owners by position, in depth-first order of their node.  An owner's
 // parent state (mbits bits 16-24) and mlink come from the nearest owner above it at its position.  nrp[v] counts the
@@ -137,6 +137,13 @@ int dfs_tables_same_arrays(const DfsTables &t, const ugp_tree_desc *tree, const 
 // depth-first position i, dend[i] ([n]) the end of position i's subtree, leaf_dfs[r] the depth-first position of leaf r.
 struct LeafRanks { std::vector<uint32_t> lbefore, dend, leaf_dfs; };
 void leaf_ranks(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, LeafRanks *out);
+
+// What mask and subtree read: per depth-first entry (its node's depth-first order, stored order within the node) the stored parent
+// allele << 4 | allele.  Refuses an allele above 15, naming the call `who`.
+int stored_alleles(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const DfsTables &T, const char *who, std::vector<uint8_t> *mpn);
+// What genotypes, summary and translate ask of the caller's arrays: mut_par is there (else UGP_ERR_INVALID with the sentence `needs`)
+// and the codes of every non-masked entry lie in 1 .. 15.
+int coded_alleles(const ugp_tree_desc *tree, const DfsTables &T, const std::string &needs);
 
 // ---- the literal score: loop 1 run literally, loops 2 and 3 in closed form, the eligibility ------------------------
 

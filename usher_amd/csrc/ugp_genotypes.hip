@@ -29,7 +29,7 @@
 #include <string>
 #include <vector>
 
-#include "ugp_dense.hpp"
+#include "ugp_query.hpp"
 #include "ugp_genotypes.hpp"
 
 namespace ugp {
@@ -193,11 +193,7 @@ __global__ void __launch_bounds__(kBlock) k_gt_rows(DfsView t, uint32_t ncols, u
 
 }  // namespace
 
-struct GtState {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    const DfsTables *T = nullptr;                 // the handle's
-    const std::vector<uint32_t> *dfs2bfs = nullptr;
+struct GtState : QueryBase {
     uint32_t npo = 0, np = 0;                     // owners; positions that have owners
     DBuf<uint32_t> onode, oup, oj, coff;          // per owner: node, owner above, compact position; per compact position: first owner
     DBuf<uint8_t> oal, opar;
@@ -208,41 +204,22 @@ struct GtState {
     DBuf<uint8_t> flag, pflag, map, cells;
     DBuf<uint32_t> sel, seg, rank, coldfs, cnt, cov, first, sitej, nsites_d;
     DBuf<ugp_gt_site> tab;
-    ~GtState() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
-void gt_free(GtState *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    delete s;
-}
+void gt_free(GtState *s) { query_free(s); }
 
 int gt_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
               DfsTables **tables, GtState **out) {
-    if (!out) return set_error(UGP_ERR_INVALID, "null argument");
-    const int rc = dfs_tables(tree, dfs2bfs, bfs2dfs, device, 31, tables);
-    if (rc) return rc;
-    const uint64_t M = tree->mut_off[tree->n_nodes];
-    if (M && !tree->mut_par) return set_error(UGP_ERR_INVALID, "genotypes need mut_par: REF is the parent allele as stored");
-    for (uint64_t k = 0; k < M; k++) {
-        if (tree->mut_pos[k] < 0) continue;
-        if (tree->mut_nuc[k] < 1 || tree->mut_nuc[k] > 15 || tree->mut_par[k] < 1 || tree->mut_par[k] > 15)
-            return set_error(UGP_ERR_UNSUPPORTED, "mut_nuc / mut_par of a non-masked mutation outside 1 .. 15");
-    }
-    try {
-        const DfsTables &T = **tables;
-        if (int same = dfs_tables_same_arrays(T, tree, dfs2bfs, "ugp_genotypes_attach")) return same;
-        GtState *S = new GtState();
-        S->device = device;
-        S->T = *tables;
-        S->dfs2bfs = &dfs2bfs;
-        hipError_t err = hipSuccess;
-        if (err == hipSuccess) err = hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking);
-        // the positions that have owners, and each owner's index among them
-        std::vector<uint32_t> poff((size_t)T.tp + 1, 0), coff, oj;
-        std::vector<int32_t> cpos;
-        if (err == hipSuccess && T.tp) err = hipMemcpy(poff.data(), T.poff.p, poff.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        if (err == hipSuccess) {
+    return query_attach(
+        "ugp_genotypes_attach", tree, dfs2bfs, bfs2dfs, device, 31, tables, out,
+        [&](const DfsTables &T) { return coded_alleles(tree, T, "genotypes need mut_par: REF is the parent allele as stored"); },
+        [&](GtState *S) {
+            const DfsTables &T = *S->T;
+            hipStream_t st = S->stream;
+            // the positions that have owners, and each owner's index among them
+            std::vector<uint32_t> poff((size_t)T.tp + 1, 0), coff, oj;
+            std::vector<int32_t> cpos;
+            if (T.tp) UGP_HIP_TRY(hipMemcpy(poff.data(), T.poff.p, poff.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
             const uint32_t npo = poff[T.tp];
             oj.resize(npo);
             for (uint32_t p = 0; p < T.tp; p++) {
@@ -254,33 +231,30 @@ int gt_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, c
             coff.push_back(npo);
             S->npo = npo;
             S->np = (uint32_t)cpos.size();
-        }
-        DBuf<uint32_t> e2x;
-        DBuf<uint8_t> mpar;
-        if (err == hipSuccess) err = S->oj.upload(oj);
-        if (err == hipSuccess) err = S->coff.upload(coff);
-        if (err == hipSuccess) err = S->cpos.upload(cpos);
-        if (err == hipSuccess) err = S->onode.alloc(S->npo);
-        if (err == hipSuccess) err = S->oup.alloc(S->npo);
-        if (err == hipSuccess) err = S->oal.alloc(S->npo);
-        if (err == hipSuccess) err = S->opar.alloc(S->npo);
-        if (err == hipSuccess) err = e2x.alloc(M);
-        if (err == hipSuccess) err = mpar.upload(tree->mut_par, M, S->stream);
-        if (err == hipSuccess && S->npo) {
-            k_gt_e2x<<<blocks_for(S->npo), kBlock, 0, S->stream>>>(S->npo, T.pent.p, e2x.p);
-            k_gt_owner<<<blocks_for(S->npo), kBlock, 0, S->stream>>>(T.view(), S->npo, e2x.p, mpar.p, S->onode.p, S->oup.p, S->oal.p, S->opar.p);
-            err = hipGetLastError();
-        }
-        if (err == hipSuccess) err = hipStreamSynchronize(S->stream);
-        if (err != hipSuccess) { delete S; return set_error(UGP_ERR_HIP, std::string("genotype tables: ") + hipGetErrorString(err)); }
-        gt_free(*out);
-        *out = S;
-    } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }
-    return UGP_OK;
+            DBuf<uint32_t> e2x;
+            DBuf<uint8_t> mpar;
+            const StreamDrain drain{st};   // the vectors and temporaries above
+            hipError_t err = S->oj.upload(oj, st);
+            if (err == hipSuccess) err = S->coff.upload(coff, st);
+            if (err == hipSuccess) err = S->cpos.upload(cpos, st);
+            if (err == hipSuccess) err = S->onode.alloc(npo);
+            if (err == hipSuccess) err = S->oup.alloc(npo);
+            if (err == hipSuccess) err = S->oal.alloc(npo);
+            if (err == hipSuccess) err = S->opar.alloc(npo);
+            if (err == hipSuccess) err = e2x.alloc(T.m);
+            if (err == hipSuccess) err = mpar.upload(tree->mut_par, T.m, st);
+            if (err == hipSuccess && npo) {
+                k_gt_e2x<<<blocks_for(npo), kBlock, 0, st>>>(npo, T.pent.p, e2x.p);
+                k_gt_owner<<<blocks_for(npo), kBlock, 0, st>>>(T.view(), npo, e2x.p, mpar.p, S->onode.p, S->oup.p, S->oal.p, S->opar.p);
+                err = hipGetLastError();
+            }
+            if (err == hipSuccess) err = hipStreamSynchronize(st);   // the vectors and temporaries above are read until here
+            return hip_rc("ugp_genotypes_attach", err);
+        });
 }
 
 int gt_select(GtState *S, const uint32_t *nodes, uint64_t nsel, uint32_t *n_cols, uint64_t *n_sites) {
-    if (!S) return set_error(UGP_ERR_INVALID, "no genotype tables: call ugp_genotypes_attach first");
+    if (int rc = query_ready(S, "ugp_genotype_select", "genotypes")) return rc;
     if (!n_cols || !n_sites) return set_error(UGP_ERR_INVALID, "null argument");
     const uint32_t N = S->T->n;
     if (!nodes) nsel = 0;
@@ -342,7 +316,7 @@ int gt_select(GtState *S, const uint32_t *nodes, uint64_t nsel, uint32_t *n_cols
 }
 
 static int gt_ready(GtState *S, const char *what, uint64_t lo, uint64_t hi) {
-    if (!S) return set_error(UGP_ERR_INVALID, std::string(what) + ": no genotype tables: call ugp_genotypes_attach first");
+    if (int rc = query_ready(S, what, "genotypes")) return rc;
     if (!S->selected) return set_error(UGP_ERR_INVALID, std::string(what) + ": no selection: call ugp_genotype_select first");
     if (lo > hi || hi > S->nsites) return set_error(UGP_ERR_INVALID, std::string(what) + ": site range outside [0, n_sites]");
     return UGP_OK;
@@ -410,21 +384,7 @@ int gt_rows_time(GtState *S, uint64_t lo, uint64_t hi, uint32_t reps, double *ms
     *ms = 0;
     if (lo == hi) return UGP_OK;
     UGP_HIP_TRY(hipSetDevice(S->device));
-    hipEvent_t a = nullptr, b = nullptr;
-    UGP_HIP_TRY(hipEventCreate(&a));
-    if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); return set_error(UGP_ERR_HIP, "hipEventCreate failed"); }
-    int rc = gt_windows(S, lo, hi, nullptr, 0);   // warm-up: the workspace
-    hipError_t err = rc ? hipSuccess : hipEventRecord(a, S->stream);
-    for (uint32_t r = 0; r < reps && !rc && err == hipSuccess; r++) rc = gt_windows(S, lo, hi, nullptr, 0);
-    if (!rc && err == hipSuccess) err = hipEventRecord(b, S->stream);
-    if (!rc && err == hipSuccess) err = hipEventSynchronize(b);
-    float t = 0;
-    if (!rc && err == hipSuccess) err = hipEventElapsedTime(&t, a, b);
-    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-    if (rc) return rc;
-    if (err != hipSuccess) return set_error(UGP_ERR_HIP, std::string("ugp_genotype_rows_time: ") + hipGetErrorString(err));
-    *ms = (double)t / reps;
-    return UGP_OK;
+    return timed(S->stream, "ugp_genotype_rows_time", reps, ms, [&] { return gt_windows(S, lo, hi, nullptr, 0); });
 }
 
 }  // namespace ugp

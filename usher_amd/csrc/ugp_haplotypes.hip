@@ -27,7 +27,7 @@
 #include <string>
 #include <vector>
 
-#include "ugp_dense.hpp"
+#include "ugp_query.hpp"
 #include "ugp_haplotypes.hpp"
 #include "ugp_sort.hpp"
 #include "ugp_translate.hpp"
@@ -208,11 +208,7 @@ inline uint64_t low_mask(uint32_t bits) { return bits >= 64 ? ~0ull : (1ull << b
 
 }  // namespace
 
-struct HpState {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    const DfsTables *T = nullptr;                 // the handle's
-    const std::vector<uint32_t> *dfs2bfs = nullptr;
+struct HpState : QueryBase {
     std::vector<uint8_t> h_leaf;                  // by BFS index
     uint32_t nleaves = 0;
     uint64_t ndup = 0;
@@ -233,59 +229,39 @@ struct HpState {
     const uint64_t *fa() const { return f.p; }
     const uint64_t *fb() const { return f.p + T->n; }
     const uint64_t *fs() const { return f.p + 2 * (size_t)T->n; }
-    ~HpState() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
-void hp_free(HpState *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    delete s;
-}
+void hp_free(HpState *s) { query_free(s); }
 
 int hp_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
               DfsTables **tables, HpState **out) {
-    if (!out) return set_error(UGP_ERR_INVALID, "null argument");
-    const int rc = dfs_tables(tree, dfs2bfs, bfs2dfs, device, 31, tables);
-    if (rc) return rc;
-    try {
-        if (int same = dfs_tables_same_arrays(**tables, tree, dfs2bfs, "ugp_haplotypes_attach")) return same;
-        HpState *S = new HpState();
-        S->device = device;
-        S->T = *tables;
-        S->dfs2bfs = &dfs2bfs;
-        if (hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking) != hipSuccess) { delete S; return set_error(UGP_ERR_HIP, "hipStreamCreate failed"); }
-        auto build = [&]() -> int {
-            const uint32_t N = (*tables)->n;
-            LeafRanks lr;
-            leaf_ranks(tree, dfs2bfs, bfs2dfs, &lr);
-            S->nleaves = (uint32_t)lr.leaf_dfs.size();
-            S->h_leaf.assign(N, 0);
-            for (uint32_t i : lr.leaf_dfs) S->h_leaf[dfs2bfs[i]] = 1;
-            // the duplicate nodes: two non-masked entries at one position
-            std::vector<int32_t> seen;
-            for (uint32_t i = 0; i < N; i++) {
-                const uint32_t b = dfs2bfs[i];
-                seen.clear();
-                bool dup = false;
-                for (uint64_t k = tree->mut_off[b]; k < tree->mut_off[b + 1]; k++) {
-                    const int32_t p = tree->mut_pos[k];
-                    if (p < 0) continue;
-                    if (std::find(seen.begin(), seen.end(), p) != seen.end()) dup = true;
-                    else seen.push_back(p);
-                }
-                if (dup && !S->ndup++) S->first_dup = b;
+    return query_attach("ugp_haplotypes_attach", tree, dfs2bfs, bfs2dfs, device, 31, tables, out, NoCheck(), [&](HpState *S) {
+        const uint32_t N = S->T->n;
+        LeafRanks lr;
+        leaf_ranks(tree, dfs2bfs, bfs2dfs, &lr);
+        S->nleaves = (uint32_t)lr.leaf_dfs.size();
+        S->h_leaf.assign(N, 0);
+        for (uint32_t i : lr.leaf_dfs) S->h_leaf[dfs2bfs[i]] = 1;
+        // the duplicate nodes: two non-masked entries at one position
+        std::vector<int32_t> seen;
+        for (uint32_t i = 0; i < N; i++) {
+            const uint32_t b = dfs2bfs[i];
+            seen.clear();
+            bool dup = false;
+            for (uint64_t k = tree->mut_off[b]; k < tree->mut_off[b + 1]; k++) {
+                const int32_t p = tree->mut_pos[k];
+                if (p < 0) continue;
+                if (std::find(seen.begin(), seen.end(), p) != seen.end()) dup = true;
+                else seen.push_back(p);
             }
-            UGP_HIP_TRY(hipSetDevice(device));
-            UGP_HIP_TRY(S->ldfs.upload(lr.leaf_dfs, S->stream));
-            UGP_HIP_TRY(S->d2b.upload(dfs2bfs.data(), N, S->stream));
-            UGP_HIP_TRY(hipStreamSynchronize(S->stream));   // lr is read until here
-            return tr_owner_nodes(*tables, S->stream);
-        };
-        if (int rc2 = build()) { (void)hipStreamSynchronize(S->stream); delete S; return rc2; }
-        hp_free(*out);
-        *out = S;
-    } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }
-    return UGP_OK;
+            if (dup && !S->ndup++) S->first_dup = b;
+        }
+        const StreamDrain drain{S->stream};   // lr
+        UGP_HIP_TRY(S->ldfs.upload(lr.leaf_dfs, S->stream));
+        UGP_HIP_TRY(S->d2b.upload(dfs2bfs.data(), N, S->stream));
+        UGP_HIP_TRY(hipStreamSynchronize(S->stream));   // lr is read until here
+        return tr_owner_nodes(*tables, S->stream);
+    });
 }
 
 // The fingerprints of every node: S->f.
@@ -344,10 +320,7 @@ static int pass_verify(HpState *S) {
     return UGP_OK;
 }
 
-static int hp_ready(HpState *S, const char *who) {
-    if (!S) return set_error(UGP_ERR_INVALID, std::string(who) + ": no haplotype tables: call ugp_haplotypes_attach first");
-    return UGP_OK;
-}
+static int hp_ready(HpState *S, const char *who) { return query_ready(S, who, "haplotypes"); }
 
 static int refuse_duplicates(const HpState *S, const char *who) {
     return set_error(UGP_ERR_UNSUPPORTED, std::string(who) + ": " + std::to_string(S->ndup) +
@@ -470,33 +443,10 @@ int hp_time(HpState *S, uint32_t reps, double *scan_ms, double *sort_ms, double 
     UGP_HIP_TRY(hipSetDevice(S->device));
     hipStream_t st = S->stream;
     if (int rc = sort_workspace(S)) return rc;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipError_t err = hipSuccess;
-    for (int i = 0; i < 4 && err == hipSuccess; i++) err = hipEventCreate(&ev[i]);
-    int rc = UGP_OK;
-    if (err == hipSuccess) {   // warm-up: the workspaces
-        rc = pass_scan(S);
-        if (!rc) rc = pass_sort(S, 128);
-        if (!rc) rc = pass_verify(S);
-    }
-    if (!rc && err == hipSuccess) err = hipEventRecord(ev[0], st);
-    for (uint32_t r = 0; r < reps && !rc && err == hipSuccess; r++) rc = pass_scan(S);
-    if (!rc && err == hipSuccess) err = hipEventRecord(ev[1], st);
-    for (uint32_t r = 0; r < reps && !rc && err == hipSuccess; r++) rc = pass_sort(S, 128);
-    if (!rc && err == hipSuccess) err = hipEventRecord(ev[2], st);
-    for (uint32_t r = 0; r < reps && !rc && err == hipSuccess; r++) rc = pass_verify(S);
-    if (!rc && err == hipSuccess) err = hipEventRecord(ev[3], st);
-    if (!rc && err == hipSuccess) err = hipEventSynchronize(ev[3]);
-    float ms[3] = {0, 0, 0};
-    for (int i = 0; i < 3 && !rc && err == hipSuccess; i++) err = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
-    (void)hipStreamSynchronize(st);
-    for (int i = 0; i < 4; i++) if (ev[i]) (void)hipEventDestroy(ev[i]);
-    if (rc) return rc;
-    if (err != hipSuccess) return set_error(UGP_ERR_HIP, std::string("ugp_haplotype_time: ") + hipGetErrorString(err));
-    *scan_ms = (double)ms[0] / reps;
-    *sort_ms = (double)ms[1] / reps;
-    *verify_ms = (double)ms[2] / reps;
-    return UGP_OK;
+    const char *who = "ugp_haplotype_time";   // each stage reads what the stage before it left
+    if (int rc = timed(st, who, reps, scan_ms, [&] { return pass_scan(S); })) return rc;
+    if (int rc = timed(st, who, reps, sort_ms, [&] { return pass_sort(S, 128); })) return rc;
+    return timed(st, who, reps, verify_ms, [&] { return pass_verify(S); });
 }
 
 }  // namespace ugp

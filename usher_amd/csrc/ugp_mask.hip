@@ -22,8 +22,8 @@
 #include <string>
 #include <vector>
 
-#include "ugp_dense.hpp"
 #include "ugp_mask.hpp"
+#include "ugp_query.hpp"
 
 namespace ugp {
 namespace {
@@ -172,11 +172,7 @@ __global__ void __launch_bounds__(kBlock) k_msk_mutations(DfsView t, uint32_t m,
 
 }  // namespace
 
-struct MskState {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    const DfsTables *T = nullptr;                 // the handle's
-    const std::vector<uint32_t> *dfs2bfs = nullptr;
+struct MskState : QueryBase {
     uint32_t nleaf = 0, nwords = 0;               // nwords counts the zero word past the last leaf
     std::vector<uint32_t> h_lbefore, h_dend;      // [n + 1], [n]
     DBuf<uint32_t> lbefore;
@@ -191,77 +187,48 @@ struct MskState {
     DBuf<uint32_t> lpos, ltlo, lthi, lidx, lxoff, lxlo, lxhi, first;
     DBuf<uint8_t> lpar, lnuc, skip;
     DBuf<u64> counts;
-    ~MskState() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
-void msk_free(MskState *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    delete s;
-}
+void msk_free(MskState *s) { query_free(s); }
 
 int msk_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
                DfsTables **tables, MskState **out) {
-    if (!out) return set_error(UGP_ERR_INVALID, "null argument");
-    const int rc = dfs_tables(tree, dfs2bfs, bfs2dfs, device, 31, tables);
-    if (rc) return rc;
-    try {
-        if (int same = dfs_tables_same_arrays(**tables, tree, dfs2bfs, "ugp_mask_attach")) return same;
-        const uint32_t N = (*tables)->n;
-        const uint64_t M = (*tables)->m;
-        // per depth-first entry (its node's depth-first order, stored order within the node) the stored alleles
-        std::vector<uint8_t> mpn;
-        mpn.reserve(M);
-        for (uint32_t i = 0; i < N; i++) {
-            const uint32_t b = dfs2bfs[i];
-            for (uint64_t e = tree->mut_off[b]; e < tree->mut_off[b + 1]; e++) {
-                if (tree->mut_par[e] > 15 || tree->mut_nuc[e] > 15)
-                    return set_error(UGP_ERR_UNSUPPORTED, "ugp_mask_attach: entry " + std::to_string(e) + " has an allele above 15");
-                mpn.push_back((uint8_t)(tree->mut_par[e] << 4 | tree->mut_nuc[e]));
-            }
-        }
-        if (mpn.size() != M) return set_error(UGP_ERR_INVALID, "ugp_mask_attach: the tables hold another number of entries");
-        MskState *S = new MskState();
-        S->device = device;
-        S->T = *tables;
-        S->dfs2bfs = &dfs2bfs;
-        LeafRanks R;
-        leaf_ranks(tree, dfs2bfs, bfs2dfs, &R);
-        std::vector<uint8_t> hasleaf(N, 0);   // "has a leaf child"
-        for (uint32_t i : R.leaf_dfs) if (i) hasleaf[bfs2dfs[tree->parent[dfs2bfs[i]]]] = 1;
-        const uint32_t nleaf = (uint32_t)R.leaf_dfs.size();
-        S->h_lbefore = std::move(R.lbefore);
-        S->h_dend = std::move(R.dend);
-        S->nleaf = nleaf;
-        S->nwords = nleaf / 64u + 1u;
-        S->h_flag.resize(N);
-        auto fail = [&](int code, const std::string &msg) { (void)hipStreamSynchronize(S->stream); delete S; return set_error(code, msg); };
-        if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking) != hipSuccess)
-            return fail(UGP_ERR_HIP, "hipStreamCreate failed");
-        hipError_t err = S->lbefore.upload(S->h_lbefore, S->stream);
-        if (err == hipSuccess) err = S->hasleaf.upload(hasleaf, S->stream);
-        if (err == hipSuccess) err = S->mpn.upload(mpn, S->stream);
-        if (err == hipSuccess) err = S->words.alloc(S->nwords);
-        if (err == hipSuccess) err = S->wpre.alloc(S->nwords);
-        if (err == hipSuccess) err = S->diff.alloc((size_t)N + 1);
-        if (err == hipSuccess) err = S->seg.alloc(std::max(segs_for((uint64_t)N + 1), segs_for(S->nwords)));
-        if (err == hipSuccess) err = S->full.alloc(N);
-        if (err == hipSuccess) err = S->flag.alloc(N);
-        if (err == hipSuccess) err = S->nmasked.alloc(1);
-        if (err == hipSuccess) err = S->emask.alloc(M);
-        if (err == hipSuccess) err = S->first.alloc(M);
-        if (err == hipSuccess) err = hipStreamSynchronize(S->stream);   // hasleaf and mpn are read until here
-        if (err != hipSuccess) return fail(UGP_ERR_HIP, std::string("ugp_mask_attach: ") + hipGetErrorString(err));
-        msk_free(*out);
-        *out = S;
-    } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }
-    return UGP_OK;
+    std::vector<uint8_t> mpn;
+    return query_attach(
+        "ugp_mask_attach", tree, dfs2bfs, bfs2dfs, device, 31, tables, out,
+        [&](const DfsTables &T) { return stored_alleles(tree, dfs2bfs, T, "ugp_mask_attach", &mpn); },
+        [&](MskState *S) {
+            const uint32_t N = S->T->n;
+            const uint64_t M = S->T->m;
+            LeafRanks R;
+            leaf_ranks(tree, dfs2bfs, bfs2dfs, &R);
+            std::vector<uint8_t> hasleaf(N, 0);   // "has a leaf child"
+            for (uint32_t i : R.leaf_dfs) if (i) hasleaf[bfs2dfs[tree->parent[dfs2bfs[i]]]] = 1;
+            const uint32_t nleaf = (uint32_t)R.leaf_dfs.size();
+            S->h_lbefore = std::move(R.lbefore);
+            S->h_dend = std::move(R.dend);
+            S->nleaf = nleaf;
+            S->nwords = nleaf / 64u + 1u;
+            S->h_flag.resize(N);
+            const StreamDrain drain{S->stream};   // hasleaf and mpn
+            hipError_t err = S->lbefore.upload(S->h_lbefore, S->stream);
+            if (err == hipSuccess) err = S->hasleaf.upload(hasleaf, S->stream);
+            if (err == hipSuccess) err = S->mpn.upload(mpn, S->stream);
+            if (err == hipSuccess) err = S->words.alloc(S->nwords);
+            if (err == hipSuccess) err = S->wpre.alloc(S->nwords);
+            if (err == hipSuccess) err = S->diff.alloc((size_t)N + 1);
+            if (err == hipSuccess) err = S->seg.alloc(std::max(segs_for((uint64_t)N + 1), segs_for(S->nwords)));
+            if (err == hipSuccess) err = S->full.alloc(N);
+            if (err == hipSuccess) err = S->flag.alloc(N);
+            if (err == hipSuccess) err = S->nmasked.alloc(1);
+            if (err == hipSuccess) err = S->emask.alloc(M);
+            if (err == hipSuccess) err = S->first.alloc(M);
+            if (err == hipSuccess) err = hipStreamSynchronize(S->stream);   // hasleaf and mpn are read until here
+            return hip_rc("ugp_mask_attach", err);
+        });
 }
 
-static int msk_ready(MskState *S, const char *who) {
-    if (!S) return set_error(UGP_ERR_INVALID, std::string(who) + ": no mask tables: call ugp_mask_attach first");
-    return UGP_OK;
-}
+static int msk_ready(MskState *S, const char *who) { return query_ready(S, who, "mask"); }
 
 // ---- restricted samples -------------------------------------------------------------------------------------------------
 
@@ -461,26 +428,6 @@ int msk_mutations(MskState *S, uint64_t n_lines, const int32_t *pos, const uint8
 
 // ---- the passes alone ---------------------------------------------------------------------------------------------------
 
-template <class F>
-static int msk_timed(MskState *S, const char *who, uint32_t reps, double *ms, F run) {
-    hipEvent_t a = nullptr, b = nullptr;
-    UGP_HIP_TRY(hipEventCreate(&a));
-    if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); return set_error(UGP_ERR_HIP, "hipEventCreate failed"); }
-    int rc = run();   // warm-up
-    hipError_t err = rc ? hipSuccess : hipEventRecord(a, S->stream);
-    for (uint32_t r = 0; r < reps && !rc && err == hipSuccess; r++) rc = run();
-    if (!rc && err == hipSuccess) err = hipEventRecord(b, S->stream);
-    if (!rc && err == hipSuccess) err = hipEventSynchronize(b);
-    float t = 0;
-    if (!rc && err == hipSuccess) err = hipEventElapsedTime(&t, a, b);
-    (void)hipStreamSynchronize(S->stream);
-    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-    if (rc) return rc;
-    if (err != hipSuccess) return set_error(UGP_ERR_HIP, std::string(who) + ": " + hipGetErrorString(err));
-    *ms = (double)t / reps;
-    return UGP_OK;
-}
-
 int msk_time(MskState *S, uint64_t n, const uint32_t *leaves_bfs, uint64_t n_lines, const int32_t *pos, const uint8_t *par,
              const uint8_t *nuc, const uint32_t *node_bfs, const uint64_t *excl_off, const uint32_t *excl_bfs, uint32_t reps,
              double *restricted_ms, double *mutations_ms) {
@@ -493,7 +440,7 @@ int msk_time(MskState *S, uint64_t n, const uint32_t *leaves_bfs, uint64_t n_lin
             if (int rc = msk_ranks(S, "ugp_mask_time", n, leaves_bfs, &ranks)) return rc;
             if (int rc = msk_restricted_stage(S, ranks)) return rc;
             UGP_HIP_TRY(hipStreamSynchronize(S->stream));   // ranks is read until here
-            if (int rc = msk_timed(S, "ugp_mask_time", reps, restricted_ms, [&] { return msk_restricted_passes(S, (uint32_t)n); })) return rc;
+            if (int rc = timed(S->stream, "ugp_mask_time", reps, restricted_ms, [&] { return msk_restricted_passes(S, (uint32_t)n); })) return rc;
         }
         if (n_lines) {
             if (n_lines > kDefaultLines) return set_error(UGP_ERR_INVALID, "ugp_mask_time: more lines than one batch takes");
@@ -503,7 +450,7 @@ int msk_time(MskState *S, uint64_t n, const uint32_t *leaves_bfs, uint64_t n_lin
             UGP_HIP_TRY(S->counts.alloc(n_lines));
             LinesView L;
             if (int rc = msk_stage_lines(S, H, 0, n_lines, pos, par, nuc, &L)) return rc;
-            if (int rc = msk_timed(S, "ugp_mask_time", reps, mutations_ms, [&] {
+            if (int rc = timed(S->stream, "ugp_mask_time", reps, mutations_ms, [&] {
                     const int c = msk_clear_mutations(S, n_lines);
                     return c ? c : msk_launch_mutations(S, L, nullptr);
                 })) return rc;

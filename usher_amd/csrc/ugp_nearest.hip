@@ -30,7 +30,7 @@
 #include <string>
 #include <vector>
 
-#include "ugp_dense.hpp"
+#include "ugp_query.hpp"
 #include "ugp_nearest.hpp"
 
 namespace ugp {
@@ -266,11 +266,7 @@ __global__ void k_nk_tobfs(const NkQ *Q, const uint32_t *d2b, uint32_t n, uint32
 
 }  // namespace
 
-struct NearState {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    const DfsTables *T = nullptr;                 // the handle's
-    const std::vector<uint32_t> *dfs2bfs = nullptr;
+struct NearState : QueryBase {
     DBuf<uint32_t> lpre, d2b;
     // per call
     DBuf<uint32_t> qnode, qk, hist, pending, woff, cnt, onode, odist;
@@ -278,40 +274,21 @@ struct NearState {
     DBuf<NkItem> work;
     DBuf<unsigned long long> scratch;
     DBuf<uint64_t> soff;
-    ~NearState() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
-void nk_free(NearState *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    delete s;
-}
+void nk_free(NearState *s) { query_free(s); }
 
 int nk_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
               DfsTables **tables, NearState **out) {
-    if (!out) return set_error(UGP_ERR_INVALID, "null argument");
-    const int rc = dfs_tables(tree, dfs2bfs, bfs2dfs, device, 31, tables);
-    if (rc) return rc;
-    try {
-        if (int same = dfs_tables_same_arrays(**tables, tree, dfs2bfs, "ugp_nearest_attach")) return same;
-    } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }
-    NearState *S = new (std::nothrow) NearState();
-    if (!S) return set_error(UGP_ERR_NOMEM, "out of host memory");
-    S->device = device;
-    S->T = *tables;
-    S->dfs2bfs = &dfs2bfs;
-    const uint32_t n = S->T->n;
-    if (hipSetDevice(device) != hipSuccess) { delete S; return set_error(UGP_ERR_HIP, "hipSetDevice failed"); }
-    hipError_t err = hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking);
-    if (err == hipSuccess) err = S->lpre.alloc((size_t)n + 1);
-    if (err == hipSuccess) err = S->d2b.upload(dfs2bfs.data(), n, S->stream);
-    DBuf<uint32_t> seg;   // read until the synchronize below
-    if (err == hipSuccess) err = scan_flags(seg, n, S->T->leaf.p, S->lpre.p, S->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(S->stream);
-    if (err != hipSuccess) { delete S; return set_error(UGP_ERR_HIP, std::string("nearest tables: ") + hipGetErrorString(err)); }
-    nk_free(*out);
-    *out = S;
-    return UGP_OK;
+    return query_attach("ugp_nearest_attach", tree, dfs2bfs, bfs2dfs, device, 31, tables, out, NoCheck(), [&](NearState *S) {
+        const uint32_t n = S->T->n;
+        DBuf<uint32_t> seg;   // read until the synchronize below
+        hipError_t err = S->lpre.alloc((size_t)n + 1);
+        if (err == hipSuccess) err = S->d2b.upload(dfs2bfs.data(), n, S->stream);
+        if (err == hipSuccess) err = scan_flags(seg, n, S->T->leaf.p, S->lpre.p, S->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(S->stream);
+        return hip_rc("ugp_nearest_attach", err);
+    });
 }
 
 int nk_run(NearState *S, uint64_t nq, const uint32_t *nodes, const uint32_t *k, uint32_t stride, uint32_t *out_nodes, uint32_t *out_dist,

@@ -26,7 +26,7 @@
 #include <string>
 #include <vector>
 
-#include "ugp_dense.hpp"
+#include "ugp_query.hpp"
 #include "ugp_relatives.hpp"
 #include "ugp_sort.hpp"
 
@@ -313,10 +313,7 @@ struct RmqBufs {
 
 }  // namespace
 
-struct RelState {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    const DfsTables *T = nullptr;   // the handle's
+struct RelState : QueryBase {
     uint32_t nl = 0, maxcum = 0;
     bool ranks = false;
     DBuf<uint32_t> lpre, lcum, srank, sbfs, boff, snr, rank2bfs;
@@ -325,18 +322,13 @@ struct RelState {
     DBuf<uint32_t> qnode, cnt, win;
     DBuf<ugp_rel_info> info;
     DBuf<unsigned long long> off;
-    ~RelState() { if (stream) (void)hipStreamDestroy(stream); }
     RelView view() const {
         return RelView{T->n, nl, maxcum, T->dpar.p, T->dend.p, T->cum.p, lpre.p, srank.p, sbfs.p, boff.p, ranks ? rank2bfs.p : nullptr,
                        rc.view(lcum.p, nl), rn.view(snr.p, ranks ? nl : 0)};
     }
 };
 
-void rel_free(RelState *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    delete s;
-}
+void rel_free(RelState *s) { query_free(s); }
 
 static int rel_build(RelState *S, const std::vector<uint32_t> &dfs2bfs, const uint32_t *name_rank) {
     const DfsTables &T = *S->T;
@@ -374,44 +366,23 @@ static int rel_build(RelState *S, const std::vector<uint32_t> &dfs2bfs, const ui
 
 int rel_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
                const uint32_t *name_rank, DfsTables **tables, RelState **out) {
-    if (!out) return set_error(UGP_ERR_INVALID, "null argument");
-    const int rc = dfs_tables(tree, dfs2bfs, bfs2dfs, device, 31, tables);
-    if (rc) return rc;
-    try {
-        if (name_rank) {
-            const uint64_t N = tree->n_nodes;
-            std::vector<uint8_t> seen(N, 0);
-            for (uint64_t j = 0; j < N; j++) {
-                if (name_rank[j] >= N || seen[name_rank[j]]) return set_error(UGP_ERR_INVALID, "name_rank is not a permutation of 0 .. n - 1");
+    return query_attach(
+        "ugp_relatives_attach", tree, dfs2bfs, bfs2dfs, device, 31, tables, out,
+        [&](const DfsTables &T) {
+            std::vector<uint8_t> seen(name_rank ? T.n : 0, 0);
+            for (uint32_t j = 0; j < seen.size(); j++) {
+                if (name_rank[j] >= T.n || seen[name_rank[j]]) return set_error(UGP_ERR_INVALID, "name_rank is not a permutation of 0 .. n - 1");
                 seen[name_rank[j]] = 1;
             }
-        }
-        if (int same = dfs_tables_same_arrays(**tables, tree, dfs2bfs, "ugp_relatives_attach")) return same;
-        RelState *S = new RelState();
-        S->device = device;
-        S->T = *tables;
-        if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking) != hipSuccess) {
-            delete S;
-            return set_error(UGP_ERR_HIP, "hipStreamCreate failed");
-        }
-        if (int rc2 = rel_build(S, dfs2bfs, name_rank)) { (void)hipStreamSynchronize(S->stream); delete S; return rc2; }
-        rel_free(*out);
-        *out = S;
-    } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }
-    return UGP_OK;
+            return (int)UGP_OK;
+        },
+        [&](RelState *S) { return rel_build(S, dfs2bfs, name_rank); });
 }
-
-namespace {
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-}  // namespace
 
 int rel_run(RelState *S, bool within, uint64_t n, const uint32_t *nodes, uint32_t k, ugp_rel_info *info, uint64_t *out_off,
             uint32_t *out_nodes, uint64_t cap, uint64_t *n_out, uint32_t chunk_samples, double *kernel_ms) {
     const char *who = within ? "ugp_relatives_within" : "ugp_relatives_closest";
-    if (!S) return set_error(UGP_ERR_INVALID, std::string(who) + ": no relatives tables: call ugp_relatives_attach first");
+    if (int rc = query_ready(S, who, "relatives")) return rc;
     if (!n_out || (n && !nodes) || (n && !info && !kernel_ms) || (out_off && cap && !out_nodes)) return set_error(UGP_ERR_INVALID, "null argument");
     const uint32_t N = S->T->n;
     for (uint64_t i = 0; i < n; i++)
@@ -429,15 +400,8 @@ int rel_run(RelState *S, bool within, uint64_t n, const uint32_t *nodes, uint32_
         const std::vector<uint32_t> &b2d = S->T->bfs2dfs;
         const uint64_t most = std::min<uint64_t>(chunk, std::max<uint64_t>(n, 1));
         UGP_HIP_TRY(S->qnode.alloc(most)); UGP_HIP_TRY(S->cnt.alloc(most)); UGP_HIP_TRY(S->info.alloc(most)); UGP_HIP_TRY(S->off.alloc(most + 1));
-        Events ev;
-        if (kernel_ms) { UGP_HIP_TRY(hipEventCreate(&ev.a)); UGP_HIP_TRY(hipEventCreate(&ev.b)); }
-        auto lap = [&](double *acc) -> hipError_t {   // the time between the two events, once the second has passed
-            float t = 0;
-            hipError_t e = hipEventSynchronize(ev.b);
-            if (e == hipSuccess) e = hipEventElapsedTime(&t, ev.a, ev.b);
-            *acc += t;
-            return e;
-        };
+        EventPair ev(st);
+        if (kernel_ms) UGP_HIP_TRY(ev.create());
         std::vector<uint32_t> qn;
         std::vector<ugp_rel_info> hinfo;
         std::vector<unsigned long long> hoff;
@@ -446,12 +410,12 @@ int rel_run(RelState *S, bool within, uint64_t n, const uint32_t *nodes, uint32_
             qn.resize(nc);
             for (uint32_t i = 0; i < nc; i++) qn[i] = b2d[nodes[c0 + i]];
             UGP_HIP_TRY(S->qnode.upload(qn, st));
-            if (kernel_ms) UGP_HIP_TRY(hipEventRecord(ev.a, st));
+            if (kernel_ms) UGP_HIP_TRY(ev.start());
             if (within) k_rel_within<<<blocks_for(nc), kBlock, 0, st>>>(v, S->qnode.p, nc, k, S->info.p, S->cnt.p);
             else k_rel_closest<<<blocks_for(nc), kBlock, 0, st>>>(v, S->qnode.p, nc, S->info.p, S->cnt.p);
             if (lists) k_rel_scan<<<1, kBlock, 0, st>>>(S->cnt.p, nc, S->off.p);
             UGP_HIP_TRY(hipGetLastError());
-            if (kernel_ms) { UGP_HIP_TRY(hipEventRecord(ev.b, st)); UGP_HIP_TRY(lap(&kernel_ms[0])); }
+            if (kernel_ms) UGP_HIP_TRY(ev.lap(&kernel_ms[0]));
             uint64_t tot = 0;
             if (!kernel_ms) {
                 hinfo.resize(nc);
@@ -476,11 +440,11 @@ int rel_run(RelState *S, bool within, uint64_t n, const uint32_t *nodes, uint32_
                 if (!kernel_ms && base + w0 >= cap) break;
                 const uint64_t wl = std::min<uint64_t>(window, tot - w0);
                 const uint32_t grid = (nc + kBlock / 64 - 1) / (kBlock / 64);
-                if (kernel_ms) UGP_HIP_TRY(hipEventRecord(ev.a, st));
+                if (kernel_ms) UGP_HIP_TRY(ev.start());
                 if (within) k_rel_fill<true><<<grid, kBlock, 0, st>>>(v, S->qnode.p, S->info.p, S->off.p, nc, k, w0, wl, S->win.p);
                 else k_rel_fill<false><<<grid, kBlock, 0, st>>>(v, S->qnode.p, S->info.p, S->off.p, nc, k, w0, wl, S->win.p);
                 UGP_HIP_TRY(hipGetLastError());
-                if (kernel_ms) { UGP_HIP_TRY(hipEventRecord(ev.b, st)); UGP_HIP_TRY(lap(&kernel_ms[1])); continue; }
+                if (kernel_ms) { UGP_HIP_TRY(ev.lap(&kernel_ms[1])); continue; }
                 const uint64_t take = std::min<uint64_t>(wl, cap - (base + w0));
                 UGP_HIP_TRY(hipMemcpyAsync(out_nodes + base + w0, S->win.p, take * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
                 UGP_HIP_TRY(hipStreamSynchronize(st));

@@ -18,7 +18,7 @@
 #include <utility>
 #include <vector>
 
-#include "ugp_dense.hpp"
+#include "ugp_query.hpp"
 #include "ugp_select.hpp"
 #include "ugp_translate.hpp"
 
@@ -104,11 +104,7 @@ __global__ void __launch_bounds__(kBlock) k_sel_climb(DfsView t, const uint32_t 
 
 }  // namespace
 
-struct SelState {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    const DfsTables *T = nullptr;                 // the handle's
-    const std::vector<uint32_t> *dfs2bfs = nullptr;
+struct SelState : QueryBase {
     uint32_t nleaf = 0, nwords = 0;
     std::vector<uint32_t> h_lbefore, h_dend, h_bfs_by_rank;   // [n + 1], [n], [nleaf]
     DBuf<uint32_t> leaf_dfs, lbefore;
@@ -117,26 +113,13 @@ struct SelState {
     DBuf<uint8_t> qnuc;
     DBuf<uint32_t> rlo, rhi, mm;
     DBuf<u64> words, counts;
-    ~SelState() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
-void sel_free(SelState *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    delete s;
-}
+void sel_free(SelState *s) { query_free(s); }
 
 int sel_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
                DfsTables **tables, SelState **out) {
-    if (!out) return set_error(UGP_ERR_INVALID, "null argument");
-    const int rc = dfs_tables(tree, dfs2bfs, bfs2dfs, device, 31, tables);
-    if (rc) return rc;
-    try {
-        if (int same = dfs_tables_same_arrays(**tables, tree, dfs2bfs, "ugp_select_attach")) return same;
-        SelState *S = new SelState();
-        S->device = device;
-        S->T = *tables;
-        S->dfs2bfs = &dfs2bfs;
+    return query_attach("ugp_select_attach", tree, dfs2bfs, bfs2dfs, device, 31, tables, out, NoCheck(), [&](SelState *S) {
         LeafRanks R;
         leaf_ranks(tree, dfs2bfs, bfs2dfs, &R);
         const std::vector<uint32_t> &leaf_dfs = R.leaf_dfs;
@@ -145,26 +128,18 @@ int sel_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, 
         for (uint32_t i : leaf_dfs) S->h_bfs_by_rank.push_back(dfs2bfs[i]);
         S->nleaf = (uint32_t)leaf_dfs.size();
         S->nwords = (S->nleaf + 63u) / 64u;
-        auto fail = [&](int code, const std::string &msg) { (void)hipStreamSynchronize(S->stream); delete S; return set_error(code, msg); };
-        if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking) != hipSuccess)
-            return fail(UGP_ERR_HIP, "hipStreamCreate failed");
+        const StreamDrain drain{S->stream};   // leaf_dfs
         hipError_t err = S->leaf_dfs.upload(leaf_dfs, S->stream);
         if (err == hipSuccess) err = S->lbefore.upload(S->h_lbefore, S->stream);
         if (err == hipSuccess) err = S->words.alloc(S->nwords);
         if (err == hipSuccess) err = S->mm.alloc(5);
         if (err == hipSuccess) err = hipStreamSynchronize(S->stream);   // leaf_dfs is read until here
-        if (err != hipSuccess) return fail(UGP_ERR_HIP, std::string("ugp_select_attach: ") + hipGetErrorString(err));
-        if (int rc2 = tr_owner_nodes(*tables, S->stream)) { (void)hipStreamSynchronize(S->stream); delete S; return rc2; }
-        sel_free(*out);
-        *out = S;
-    } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }
-    return UGP_OK;
+        if (int rc = hip_rc("ugp_select_attach", err)) return rc;
+        return tr_owner_nodes(*tables, S->stream);
+    });
 }
 
-static int sel_ready(SelState *S, const char *who) {
-    if (!S) return set_error(UGP_ERR_INVALID, std::string(who) + ": no select tables: call ugp_select_attach first");
-    return UGP_OK;
-}
+static int sel_ready(SelState *S, const char *who) { return query_ready(S, who, "select"); }
 
 int sel_leaves(SelState *S, uint32_t *bfs_by_rank, uint64_t *n_leaves) {
     if (int rc = sel_ready(S, "ugp_select_leaves")) return rc;
@@ -277,23 +252,8 @@ int sel_time(SelState *S, uint64_t n_mut, const int32_t *pos, const uint8_t *nuc
     if (n_mut >= (1ull << 31)) return set_error(UGP_ERR_INVALID, "more than 2^31 mutation queries");
     *ms = 0;
     UGP_HIP_TRY(hipSetDevice(S->device));
-    hipEvent_t a = nullptr, b = nullptr;
-    UGP_HIP_TRY(hipEventCreate(&a));
-    if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); return set_error(UGP_ERR_HIP, "hipEventCreate failed"); }
-    int rc = sel_stage(S, n_mut, pos, nuc);
-    if (!rc) rc = sel_mutation_batches(S, n_mut, kDefaultQueries);   // warm-up
-    hipError_t err = rc ? hipSuccess : hipEventRecord(a, S->stream);
-    for (uint32_t r = 0; r < reps && !rc && err == hipSuccess; r++) rc = sel_mutation_batches(S, n_mut, kDefaultQueries);
-    if (!rc && err == hipSuccess) err = hipEventRecord(b, S->stream);
-    if (!rc && err == hipSuccess) err = hipEventSynchronize(b);
-    float t = 0;
-    if (!rc && err == hipSuccess) err = hipEventElapsedTime(&t, a, b);
-    (void)hipStreamSynchronize(S->stream);
-    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-    if (rc) return rc;
-    if (err != hipSuccess) return set_error(UGP_ERR_HIP, std::string("ugp_select_time: ") + hipGetErrorString(err));
-    *ms = (double)t / reps;
-    return UGP_OK;
+    if (int rc = sel_stage(S, n_mut, pos, nuc)) { (void)hipStreamSynchronize(S->stream); return rc; }
+    return timed(S->stream, "ugp_select_time", reps, ms, [&] { return sel_mutation_batches(S, n_mut, kDefaultQueries); });
 }
 
 }  // namespace ugp

@@ -92,15 +92,8 @@ __global__ void __launch_bounds__(kBlock) k_sub_merge(uint32_t g0, uint32_t g1, 
     if (i >= g1) return;
     const u64 k = key[i];
     if (i && key[i - 1] == k) { surv[i] = 0; return; }
-    bool open = false;
-    uint32_t first = 0, spar = 0, sn = 0, bad = 0;
-    for (uint32_t j = i; j < G && key[j] == k; j++) {
-        const uint32_t e = val[j], par = mpn[e] >> 4, nuc = mpn[e] & 15u;
-        if (!open) { open = true; first = e; spar = par; sn = nuc; }   // nothing is checked, par == nuc included
-        else if (spar != nuc) sn = nuc;
-        else if (sn == par) open = false;                               // a reversal empties the position
-        else bad++;                                                     // add_mutation's false: the entry is skipped
-    }
+    uint32_t first, sn, bad;
+    const bool open = walk_run(i, G, k, key, val, mpn, &first, &sn, &bad);
     surv[i] = open ? 1 : 0;
     if (open) { sfirst[i] = morig[first]; snuc[i] = (uint8_t)sn; }
     if (bad) {
@@ -141,59 +134,31 @@ __global__ void __launch_bounds__(kBlock) k_sub_owner(DfsView t, uint32_t nn, co
 
 }  // namespace
 
-void sub_free(SubState *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    delete s;
-}
+void sub_free(SubState *s) { query_free(s); }
 
 int sub_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
                DfsTables **tables, SubState **out) {
-    if (!out) return set_error(UGP_ERR_INVALID, "null argument");
-    const int rc = dfs_tables(tree, dfs2bfs, bfs2dfs, device, 31, tables);
-    if (rc) return rc;
-    try {
-        if (int same = dfs_tables_same_arrays(**tables, tree, dfs2bfs, "ugp_subtree_attach")) return same;
-        const uint32_t N = (*tables)->n;
-        const uint64_t M = (*tables)->m;
-        std::vector<uint8_t> mpn;
-        mpn.reserve(M);
-        for (uint32_t i = 0; i < N; i++) {
-            const uint32_t b = dfs2bfs[i];
-            for (uint64_t e = tree->mut_off[b]; e < tree->mut_off[b + 1]; e++) {
-                if (tree->mut_par[e] > 15 || tree->mut_nuc[e] > 15)
-                    return set_error(UGP_ERR_UNSUPPORTED, "ugp_subtree_attach: entry " + std::to_string(e) + " has an allele above 15");
-                mpn.push_back((uint8_t)(tree->mut_par[e] << 4 | tree->mut_nuc[e]));
-            }
-        }
-        if (mpn.size() != M) return set_error(UGP_ERR_INVALID, "ugp_subtree_attach: the tables hold another number of entries");
-        SubState *S = new SubState();
-        S->device = device;
-        S->T = *tables;
-        S->dfs2bfs = &dfs2bfs;
-        auto fail = [&](int code, const std::string &msg) { (void)hipStreamSynchronize(S->stream); delete S; return set_error(code, msg); };
-        if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking) != hipSuccess)
-            return fail(UGP_ERR_HIP, "hipStreamCreate failed");
-        hipError_t err = S->mpn.upload(mpn, S->stream);
-        if (err == hipSuccess) err = S->sel.alloc(N);
-        if (err == hipSuccess) err = S->kept.alloc(N);
-        if (err == hipSuccess) err = S->sb.alloc((size_t)N + 1);
-        if (err == hipSuccess) err = S->kb.alloc((size_t)N + 1);
-        if (err == hipSuccess) err = S->eflag.alloc(M);
-        if (err == hipSuccess) err = S->eb.alloc(M + 1);
-        if (err == hipSuccess) err = S->ctr.alloc(kCounters);
-        if (err == hipSuccess) err = hipStreamSynchronize(S->stream);   // mpn is read until here
-        if (err != hipSuccess) return fail(UGP_ERR_HIP, std::string("ugp_subtree_attach: ") + hipGetErrorString(err));
-        sub_free(*out);
-        *out = S;
-    } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }
-    return UGP_OK;
+    std::vector<uint8_t> mpn;
+    return query_attach(
+        "ugp_subtree_attach", tree, dfs2bfs, bfs2dfs, device, 31, tables, out,
+        [&](const DfsTables &T) { return stored_alleles(tree, dfs2bfs, T, "ugp_subtree_attach", &mpn); },
+        [&](SubState *S) {
+            const uint32_t N = S->T->n;
+            const uint64_t M = S->T->m;
+            hipError_t err = S->mpn.upload(mpn, S->stream);
+            if (err == hipSuccess) err = S->sel.alloc(N);
+            if (err == hipSuccess) err = S->kept.alloc(N);
+            if (err == hipSuccess) err = S->sb.alloc((size_t)N + 1);
+            if (err == hipSuccess) err = S->kb.alloc((size_t)N + 1);
+            if (err == hipSuccess) err = S->eflag.alloc(M);
+            if (err == hipSuccess) err = S->eb.alloc(M + 1);
+            if (err == hipSuccess) err = S->ctr.alloc(kCounters);
+            if (err == hipSuccess) err = hipStreamSynchronize(S->stream);   // mpn is read until here
+            return hip_rc("ugp_subtree_attach", err);
+        });
 }
 
-static int sub_ready(SubState *S, const char *who) {
-    if (!S) return set_error(UGP_ERR_INVALID, std::string(who) + ": no subtree tables: call ugp_subtree_attach first");
-    return UGP_OK;
-}
+static int sub_ready(SubState *S, const char *who) { return query_ready(S, who, "subtree"); }
 
 // The names as depth-first positions (duplicates stay: the flags take them once).
 static int sub_positions(SubState *S, const char *who, uint64_t n, const uint32_t *nodes_bfs, std::vector<uint32_t> *at) {
@@ -374,26 +339,6 @@ int sub_owner(SubState *S, uint64_t n, const uint32_t *nodes_bfs, uint32_t *owne
 
 // ---- the passes alone ---------------------------------------------------------------------------------------------------
 
-template <class F>
-static int sub_timed(SubState *S, uint32_t reps, double *ms, F run) {
-    hipEvent_t a = nullptr, b = nullptr;
-    UGP_HIP_TRY(hipEventCreate(&a));
-    if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); return set_error(UGP_ERR_HIP, "hipEventCreate failed"); }
-    int rc = run();   // warm-up
-    hipError_t err = rc ? hipSuccess : hipEventRecord(a, S->stream);
-    for (uint32_t r = 0; r < reps && !rc && err == hipSuccess; r++) rc = run();
-    if (!rc && err == hipSuccess) err = hipEventRecord(b, S->stream);
-    if (!rc && err == hipSuccess) err = hipEventSynchronize(b);
-    float t = 0;
-    if (!rc && err == hipSuccess) err = hipEventElapsedTime(&t, a, b);
-    (void)hipStreamSynchronize(S->stream);
-    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-    if (rc) return rc;
-    if (err != hipSuccess) return set_error(UGP_ERR_HIP, std::string("ugp_subtree_time: ") + hipGetErrorString(err));
-    *ms = (double)t / reps;
-    return UGP_OK;
-}
-
 int sub_time(SubState *S, uint64_t n, const uint32_t *nodes_bfs, uint32_t reps, double *nodes_ms, double *merge_ms) {
     if (int rc = sub_ready(S, "ugp_subtree_time")) return rc;
     if (!reps || !nodes_ms || !merge_ms) return set_error(UGP_ERR_INVALID, "null argument");
@@ -403,8 +348,8 @@ int sub_time(SubState *S, uint64_t n, const uint32_t *nodes_bfs, uint32_t reps, 
         uint32_t distinct = 0;
         if (int rc = sub_run(S, at, 0, &distinct)) return rc;   // stages the names and sizes the buffers
         const uint32_t nk = S->nk, G = S->G;
-        if (int rc = sub_timed(S, reps, nodes_ms, [&] { const int c = sub_node_passes(S, (uint32_t)n); return c ? c : sub_list_passes(S, nk); })) return rc;
-        if (int rc = sub_timed(S, reps, merge_ms, [&] { return sub_merge_passes(S, nk, G, 0); })) return rc;
+        if (int rc = timed(S->stream, "ugp_subtree_time", reps, nodes_ms, [&] { const int c = sub_node_passes(S, (uint32_t)n); return c ? c : sub_list_passes(S, nk); })) return rc;
+        if (int rc = timed(S->stream, "ugp_subtree_time", reps, merge_ms, [&] { return sub_merge_passes(S, nk, G, 0); })) return rc;
     } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }
     return UGP_OK;
 }

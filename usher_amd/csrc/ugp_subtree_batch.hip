@@ -188,15 +188,8 @@ __global__ void __launch_bounds__(kBlock) k_sbat_merge(uint32_t g0, uint32_t g1,
     if (i >= g1) return;
     const u64 k = key[i];
     if (i && key[i - 1] == k) { surv[i] = 0; return; }
-    bool open = false;
-    uint32_t first = 0, spar = 0, sn = 0, bad = 0;
-    for (uint32_t j = i; j < G && key[j] == k; j++) {
-        const uint32_t e = val[j], par = mpn[e] >> 4, nuc = mpn[e] & 15u;
-        if (!open) { open = true; first = e; spar = par; sn = nuc; }
-        else if (spar != nuc) sn = nuc;
-        else if (sn == par) open = false;
-        else bad++;
-    }
+    uint32_t first, sn, bad;
+    const bool open = walk_run(i, G, k, key, val, mpn, &first, &sn, &bad);
     surv[i] = open ? 1 : 0;
     if (open) { sfirst[i] = morig[first]; snuc[i] = (uint8_t)sn; }
     if (bad) {
@@ -310,26 +303,6 @@ int bat_merge_passes(SubState *S, BatState *B, const Group &g, uint64_t chunk) {
                                                            B->onuc.p);
     k_sbat_entoff<<<blocks_for((uint64_t)g.nk + 1), kBlock, 0, st>>>(g.nk, G, B->kout.p, B->sv.p, B->eoff.p);
     UGP_HIP_TRY(hipGetLastError());
-    return UGP_OK;
-}
-
-template <class F>
-int bat_timed(SubState *S, uint32_t reps, double *ms, F run) {
-    hipEvent_t a = nullptr, b = nullptr;
-    UGP_HIP_TRY(hipEventCreate(&a));
-    if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); return set_error(UGP_ERR_HIP, "hipEventCreate failed"); }
-    int rc = run();   // warm-up
-    hipError_t err = rc ? hipSuccess : hipEventRecord(a, S->stream);
-    for (uint32_t r = 0; r < reps && !rc && err == hipSuccess; r++) rc = run();
-    if (!rc && err == hipSuccess) err = hipEventRecord(b, S->stream);
-    if (!rc && err == hipSuccess) err = hipEventSynchronize(b);
-    float t = 0;
-    if (!rc && err == hipSuccess) err = hipEventElapsedTime(&t, a, b);
-    (void)hipStreamSynchronize(S->stream);
-    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-    if (rc) return rc;
-    if (err != hipSuccess) return set_error(UGP_ERR_HIP, std::string("ugp_subtree_batch_time: ") + hipGetErrorString(err));
-    *ms += (double)t / reps;
     return UGP_OK;
 }
 
@@ -512,8 +485,12 @@ int bat_run(SubState *S, const char *who, uint64_t ns, const uint64_t *sel_off, 
             I.lca = d2b[lca[b]];
         }
         if (tm) {
-            if (int r2 = bat_timed(S, tm->reps, &tm->nodes_ms, [&] { const int c = bat_node_passes(S, B, g); return c ? c : bat_list_passes(S, B, g); })) return r2;
-            if (int r2 = bat_timed(S, tm->reps, &tm->merge_ms, [&] { return bat_merge_passes(S, B, g, chunk); })) return r2;
+            double nodes_ms = 0, merge_ms = 0;   // of this group
+            if (int r2 = timed(S->stream, "ugp_subtree_batch_time", tm->reps, &nodes_ms,
+                               [&] { const int c = bat_node_passes(S, B, g); return c ? c : bat_list_passes(S, B, g); })) return r2;
+            if (int r2 = timed(S->stream, "ugp_subtree_batch_time", tm->reps, &merge_ms, [&] { return bat_merge_passes(S, B, g, chunk); })) return r2;
+            tm->nodes_ms += nodes_ms;
+            tm->merge_ms += merge_ms;
         }
     }
     A->kept_off[ns] = A->kept_bfs.size();
@@ -521,10 +498,7 @@ int bat_run(SubState *S, const char *who, uint64_t ns, const uint64_t *sel_off, 
     return UGP_OK;
 }
 
-int bat_ready(SubState *S, const char *who) {
-    if (!S) return set_error(UGP_ERR_INVALID, std::string(who) + ": no subtree tables: call ugp_subtree_attach first");
-    return UGP_OK;
-}
+int bat_ready(SubState *S, const char *who) { return query_ready(S, who, "subtree"); }
 
 int bat_answered(SubState *S, const char *who) {
     if (int rc = bat_ready(S, who)) return rc;

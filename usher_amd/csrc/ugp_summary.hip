@@ -28,7 +28,7 @@
 #include <string>
 #include <vector>
 
-#include "ugp_dense.hpp"
+#include "ugp_query.hpp"
 #include "ugp_sort.hpp"
 #include "ugp_summary.hpp"
 
@@ -206,11 +206,7 @@ __global__ void k_sm_clade_leaf(DfsView t, uint32_t ncols, uint32_t nleaves, con
 
 }  // namespace
 
-struct SmState {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    const DfsTables *T = nullptr;                 // the handle's
-    const std::vector<uint32_t> *dfs2bfs = nullptr;
+struct SmState : QueryBase {
     uint32_t m = 0, nruns = 0, ncand = 0, nleaves = 0;   // entries; non-masked runs; candidates; leaves
     unsigned lbits = 1;
     DBuf<uint8_t> mpar;
@@ -225,14 +221,9 @@ struct SmState {
     SmView view() const {
         return SmView{cand.p, inv.p, rid.p, rstart.p, onode.p, lcnt.p, ccount.p, bigcnt.p, bstart.p, brank.p, bskey.p, (1ull << lbits) - 1};
     }
-    ~SmState() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
-void sm_free(SmState *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    delete s;
-}
+void sm_free(SmState *s) { query_free(s); }
 
 static int sm_build(SmState *S, const ugp_tree_desc *tree) {
     const DfsTables &T = *S->T;
@@ -303,28 +294,10 @@ static int sm_build(SmState *S, const ugp_tree_desc *tree) {
 
 int sm_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
               DfsTables **tables, SmState **out) {
-    if (!out) return set_error(UGP_ERR_INVALID, "null argument");
-    const int rc = dfs_tables(tree, dfs2bfs, bfs2dfs, device, 31, tables);
-    if (rc) return rc;
-    const uint64_t M = tree->mut_off[tree->n_nodes];
-    if (M && !tree->mut_par) return set_error(UGP_ERR_INVALID, "summary needs mut_par: a mutation's name begins with the parent allele as stored");
-    for (uint64_t k = 0; k < M; k++) {
-        if (tree->mut_pos[k] < 0) continue;
-        if (tree->mut_nuc[k] < 1 || tree->mut_nuc[k] > 15 || tree->mut_par[k] < 1 || tree->mut_par[k] > 15)
-            return set_error(UGP_ERR_UNSUPPORTED, "mut_nuc / mut_par of a non-masked mutation outside 1 .. 15");
-    }
-    try {
-        if (int same = dfs_tables_same_arrays(**tables, tree, dfs2bfs, "ugp_summary_attach")) return same;
-        SmState *S = new SmState();
-        S->device = device;
-        S->T = *tables;
-        S->dfs2bfs = &dfs2bfs;
-        if (hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking) != hipSuccess) { delete S; return set_error(UGP_ERR_HIP, "hipStreamCreate failed"); }
-        if (int rc2 = sm_build(S, tree)) { (void)hipStreamSynchronize(S->stream); delete S; return rc2; }
-        sm_free(*out);
-        *out = S;
-    } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }
-    return UGP_OK;
+    return query_attach(
+        "ugp_summary_attach", tree, dfs2bfs, bfs2dfs, device, 31, tables, out,
+        [&](const DfsTables &T) { return coded_alleles(tree, T, "summary needs mut_par: a mutation's name begins with the parent allele as stored"); },
+        [&](SmState *S) { return sm_build(S, tree); });
 }
 
 int sm_mutations(SmState *S, ugp_sm_mutation *out, uint64_t cap, uint64_t *n_out, uint64_t chunk_items) {
@@ -458,34 +431,18 @@ int sm_time(SmState *S, uint32_t reps, double *sort_ms, double *roho_ms) {
     UGP_HIP_TRY(ukey.alloc(M)); UGP_HIP_TRY(skey.alloc(M)); UGP_HIP_TRY(uval.alloc(M)); UGP_HIP_TRY(sent.alloc(M));
     const uint32_t win = (uint32_t)std::min<uint64_t>(kDefaultItems, std::max<uint32_t>(S->ncand, 1));
     UGP_HIP_TRY(S->flag.alloc(win)); UGP_HIP_TRY(S->rec.alloc(win));
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    hipError_t err = hipSuccess;
-    for (int i = 0; i < 3 && err == hipSuccess; i++) err = hipEventCreate(&ev[i]);
-    if (err == hipSuccess) {
-        k_sm_keys<<<blocks_for(M), kBlock, 0, st>>>(t, M, S->mpar.p, ukey.p, uval.p);
-        err = sort_pairs(S->tmp, ukey.p, skey.p, uval.p, sent.p, M, kKeyBits, st);   // warm-up: the temporary storage
-    }
-    if (err == hipSuccess) err = hipEventRecord(ev[0], st);
-    for (uint32_t r = 0; r < reps && err == hipSuccess; r++) err = sort_pairs(S->tmp, ukey.p, skey.p, uval.p, sent.p, M, kKeyBits, st);
-    if (err == hipSuccess) err = hipEventRecord(ev[1], st);
-    for (uint32_t r = 0; r < reps && err == hipSuccess; r++) {
+    k_sm_keys<<<blocks_for(M), kBlock, 0, st>>>(t, M, S->mpar.p, ukey.p, uval.p);   // what the sort stage sorts
+    UGP_HIP_TRY(hipGetLastError());
+    const char *who = "ugp_summary_time";
+    if (int rc = timed(st, who, reps, sort_ms, [&] { return hip_rc(who, sort_pairs(S->tmp, ukey.p, skey.p, uval.p, sent.p, M, kKeyBits, st)); }))
+        return rc;
+    return timed(st, who, reps, roho_ms, [&] {
         for (uint64_t i0 = 0; i0 < S->ncand; i0 += win) {
             const uint32_t cnt = (uint32_t)std::min<uint64_t>(win, S->ncand - i0);
             k_sm_roho<<<blocks_for(cnt), kBlock, 0, st>>>(t, S->view(), (uint32_t)i0, cnt, S->flag.p, S->rec.p);
         }
-        err = hipGetLastError();
-    }
-    if (err == hipSuccess) err = hipEventRecord(ev[2], st);
-    if (err == hipSuccess) err = hipEventSynchronize(ev[2]);
-    float a = 0, b = 0;
-    if (err == hipSuccess) err = hipEventElapsedTime(&a, ev[0], ev[1]);
-    if (err == hipSuccess) err = hipEventElapsedTime(&b, ev[1], ev[2]);
-    (void)hipStreamSynchronize(st);
-    for (int i = 0; i < 3; i++) if (ev[i]) (void)hipEventDestroy(ev[i]);
-    if (err != hipSuccess) return set_error(UGP_ERR_HIP, std::string("ugp_summary_time: ") + hipGetErrorString(err));
-    *sort_ms = (double)a / reps;
-    *roho_ms = (double)b / reps;
-    return UGP_OK;
+        return hip_rc(who, hipGetLastError());
+    });
 }
 
 }  // namespace ugp

@@ -26,7 +26,7 @@
 #include <utility>
 #include <vector>
 
-#include "ugp_dense.hpp"
+#include "ugp_query.hpp"
 #include "ugp_translate.hpp"
 
 namespace ugp {
@@ -134,11 +134,7 @@ __global__ void k_tr_emit(uint32_t cnt, const uint8_t *flag, const uint32_t *off
 
 }  // namespace
 
-struct TrState {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    const DfsTables *T = nullptr;                 // the handle's
-    const std::vector<uint32_t> *dfs2bfs = nullptr;
+struct TrState : QueryBase {
     std::vector<uint32_t> h_moff, h_morig;        // host copies of the tables the item list is made from
     std::vector<int32_t> h_mpos;
     std::vector<uint8_t> h_mflag;
@@ -156,14 +152,9 @@ struct TrState {
     DBuf<uint32_t> seg, off, counters;
     DBuf<ugp_tr_record> rec, rout;
     TrView view() const { return TrView{ient.p, icod.p, T->onode.p, spos.p, sinit.p, mpar.p, (uint32_t)nitems}; }
-    ~TrState() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
-void tr_free(TrState *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    delete s;
-}
+void tr_free(TrState *s) { query_free(s); }
 
 int tr_owner_nodes(DfsTables *T, hipStream_t st) {
     if (!T) return set_error(UGP_ERR_INVALID, "null argument");
@@ -202,32 +193,14 @@ static int tr_build(TrState *S, DfsTables *tables, const ugp_tree_desc *tree) {
 
 int tr_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
               DfsTables **tables, TrState **out) {
-    if (!out) return set_error(UGP_ERR_INVALID, "null argument");
-    const int rc = dfs_tables(tree, dfs2bfs, bfs2dfs, device, 31, tables);
-    if (rc) return rc;
-    const uint64_t M = tree->mut_off[tree->n_nodes];
-    if (M && !tree->mut_par) return set_error(UGP_ERR_INVALID, "translate needs mut_par: a node's codons start from the parent allele as stored");
-    for (uint64_t k = 0; k < M; k++) {
-        if (tree->mut_pos[k] < 0) continue;
-        if (tree->mut_nuc[k] < 1 || tree->mut_nuc[k] > 15 || tree->mut_par[k] < 1 || tree->mut_par[k] > 15)
-            return set_error(UGP_ERR_UNSUPPORTED, "mut_nuc / mut_par of a non-masked mutation outside 1 .. 15");
-    }
-    try {
-        if (int same = dfs_tables_same_arrays(**tables, tree, dfs2bfs, "ugp_translate_attach")) return same;
-        TrState *S = new TrState();
-        S->device = device;
-        S->T = *tables;
-        S->dfs2bfs = &dfs2bfs;
-        if (hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking) != hipSuccess) { delete S; return set_error(UGP_ERR_HIP, "hipStreamCreate failed"); }
-        if (int rc2 = tr_build(S, *tables, tree)) { (void)hipStreamSynchronize(S->stream); delete S; return rc2; }
-        tr_free(*out);
-        *out = S;
-    } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }
-    return UGP_OK;
+    return query_attach(
+        "ugp_translate_attach", tree, dfs2bfs, bfs2dfs, device, 31, tables, out,
+        [&](const DfsTables &T) { return coded_alleles(tree, T, "translate needs mut_par: a node's codons start from the parent allele as stored"); },
+        [&](TrState *S) { return tr_build(S, *tables, tree); });
 }
 
 int tr_codons(TrState *S, uint64_t n_codons, const int32_t *slot_pos, const uint8_t *slot_init) {
-    if (!S) return set_error(UGP_ERR_INVALID, "ugp_translate_codons: no translate tables: call ugp_translate_attach first");
+    if (int rc = query_ready(S, "ugp_translate_codons", "translate")) return rc;
     if (n_codons && (!slot_pos || !slot_init)) return set_error(UGP_ERR_INVALID, "null argument");
     if (n_codons >= (1ull << 30)) return set_error(UGP_ERR_INVALID, "more than 2^30 codons");
     int32_t maxp = 0;
@@ -312,7 +285,7 @@ static int tr_windows(TrState *S, uint64_t win, uint64_t room, bool count, uint6
 }
 
 static int tr_ready(TrState *S, const char *who) {
-    if (!S) return set_error(UGP_ERR_INVALID, std::string(who) + ": no translate tables: call ugp_translate_attach first");
+    if (int rc = query_ready(S, who, "translate")) return rc;
     if (!S->have_codons) return set_error(UGP_ERR_INVALID, std::string(who) + ": no codon table: call ugp_translate_codons first");
     return UGP_OK;
 }
@@ -364,22 +337,7 @@ int tr_time(TrState *S, uint32_t reps, double *ms) {
     UGP_HIP_TRY(hipSetDevice(S->device));
     const uint64_t win = std::min<uint64_t>(kDefaultItems, S->nitems);
     if (int rc = tr_workspace(S, win, win)) return rc;
-    hipEvent_t a = nullptr, b = nullptr;
-    UGP_HIP_TRY(hipEventCreate(&a));
-    if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); return set_error(UGP_ERR_HIP, "hipEventCreate failed"); }
-    int rc = tr_windows(S, win, win, false, nullptr);   // warm-up
-    hipError_t err = rc ? hipSuccess : hipEventRecord(a, S->stream);
-    for (uint32_t r = 0; r < reps && !rc && err == hipSuccess; r++) rc = tr_windows(S, win, win, false, nullptr);
-    if (!rc && err == hipSuccess) err = hipEventRecord(b, S->stream);
-    if (!rc && err == hipSuccess) err = hipEventSynchronize(b);
-    float t = 0;
-    if (!rc && err == hipSuccess) err = hipEventElapsedTime(&t, a, b);
-    (void)hipStreamSynchronize(S->stream);
-    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-    if (rc) return rc;
-    if (err != hipSuccess) return set_error(UGP_ERR_HIP, std::string("ugp_translate_time: ") + hipGetErrorString(err));
-    *ms = (double)t / reps;
-    return UGP_OK;
+    return timed(S->stream, "ugp_translate_time", reps, ms, [&] { return tr_windows(S, win, win, false, nullptr); });
 }
 
 }  // namespace ugp

@@ -15,7 +15,7 @@
 #include <string>
 #include <vector>
 
-#include "ugp_dense.hpp"
+#include "ugp_query.hpp"
 #include "ugp_uncertainty.hpp"
 
 namespace ugp {
@@ -236,45 +236,22 @@ __global__ void k_final(Batch B) {
 
 }  // namespace
 
-struct UncState {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    const DfsTables *T = nullptr;   // the handle's
+struct UncState : QueryBase {
     // per-batch workspace
     DBuf<uint32_t> sdfs, qn, scnt, sfirst, slast, soff, total, shift, lca, ties, epps, nsize, tcount;
     DBuf<uint64_t> qoff;
     DBuf<int32_t> qpos, h0m, init, diff, seg, mn, top;
     DBuf<uint16_t> qnr, tab;
-    ~UncState() {
-        if (stream) { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
-    }
 };
 
-void unc_free(UncState *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    delete s;
-}
+void unc_free(UncState *s) { query_free(s); }
 
 int unc_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
                DfsTables **tables, UncState **out) {
-    if (!out) return set_error(UGP_ERR_INVALID, "null argument");
-    const int rc = dfs_tables(tree, dfs2bfs, bfs2dfs, device, 32, tables);
-    if (rc) return rc;
-    try {
-        if (int same = dfs_tables_same_arrays(**tables, tree, dfs2bfs, "ugp_uncertainty_attach")) return same;
-    } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }
-    if (!(*tables)->literal_ok) return set_error(UGP_ERR_UNSUPPORTED, "two mutations at one position on one branch");
-    UncState *S = new (std::nothrow) UncState();
-    if (!S) return set_error(UGP_ERR_NOMEM, "out of host memory");
-    S->device = device;
-    S->T = *tables;
-    if (hipSetDevice(device) != hipSuccess) { delete S; return set_error(UGP_ERR_HIP, "hipSetDevice failed"); }
-    const hipError_t err = hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking);
-    if (err != hipSuccess) { delete S; return set_error(UGP_ERR_HIP, std::string("uncertainty tables: ") + hipGetErrorString(err)); }
-    unc_free(*out);
-    *out = S;
-    return UGP_OK;
+    return query_attach(
+        "ugp_uncertainty_attach", tree, dfs2bfs, bfs2dfs, device, 32, tables, out,
+        [](const DfsTables &T) { return T.literal_ok ? (int)UGP_OK : set_error(UGP_ERR_UNSUPPORTED, "two mutations at one position on one branch"); },
+        [](UncState *) { return (int)UGP_OK; });
 }
 
 int unc_run(UncState *S, const uint32_t *nodes, uint64_t n, uint32_t cap, uint32_t *epps, uint32_t *nsize, uint32_t *tie_dfs, uint32_t *tie_count) {

@@ -22,7 +22,7 @@
 #include <string>
 #include <vector>
 
-#include "ugp_dense.hpp"
+#include "ugp_query.hpp"
 #include "ugp_translate.hpp"
 #include "ugp_vectors.hpp"
 
@@ -339,67 +339,46 @@ __global__ void __launch_bounds__(kBlock) k_vec_order(const ugp_vec_info *info, 
     ex[off_ex[lo] + first + rank] = mine;   // rank < cnt: at most cnt - 1 others are less
 }
 
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
 }  // namespace
 
-struct VecState {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    const DfsTables *T = nullptr;   // the handle's
+struct VecState : QueryBase {
     DBuf<uint8_t> spar;
     // per call
     DBuf<u64> ent_off, off_ex, off_im;
     DBuf<uint32_t> ps, pn, n3;
     DBuf<ugp_vec_info> info;
     DBuf<ugp_vec_entry> ex, tmp, im;
-    ~VecState() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
-void vec_free(VecState *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    delete s;
-}
+void vec_free(VecState *s) { query_free(s); }
 
 int vec_attach(const ugp_tree_desc *tree, const std::vector<uint32_t> &dfs2bfs, const std::vector<uint32_t> &bfs2dfs, int device,
                DfsTables **tables, VecState **out) {
-    if (!out) return set_error(UGP_ERR_INVALID, "null argument");
-    const int rc = dfs_tables(tree, dfs2bfs, bfs2dfs, device, 31, tables);
-    if (rc) return rc;
-    try {
-        if (int same = dfs_tables_same_arrays(**tables, tree, dfs2bfs, "ugp_vectors_attach")) return same;
-        const uint64_t M = tree->mut_off[tree->n_nodes];
-        if (M && !tree->mut_par) return set_error(UGP_ERR_INVALID, "ugp_vectors_attach needs mut_par: the node's own entries report the parent allele as stored");
-        std::vector<uint8_t> spar;
-        spar.reserve(M);
-        for (uint32_t b : dfs2bfs)
-            for (uint64_t k = tree->mut_off[b]; k < tree->mut_off[b + 1]; k++) {
-                if (tree->mut_nuc[k] > 15 || tree->mut_ref[k] > 15 || tree->mut_par[k] > 15)
-                    return set_error(UGP_ERR_UNSUPPORTED, "ugp_vectors_attach: an allele of entry " + std::to_string(k) + " is not a 4-bit code");
-                spar.push_back(tree->mut_par[k]);
-            }
-        VecState *S = new VecState();
-        S->device = device;
-        S->T = *tables;
-        auto fail = [&](int code, const std::string &msg) { if (S->stream) (void)hipStreamSynchronize(S->stream); delete S; return set_error(code, msg); };
-        if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking) != hipSuccess)
-            return fail(UGP_ERR_HIP, "hipStreamCreate failed");
-        hipError_t err = S->spar.upload(spar, S->stream);
-        if (err == hipSuccess) err = hipStreamSynchronize(S->stream);   // spar is read until here
-        if (err != hipSuccess) return fail(UGP_ERR_HIP, std::string("ugp_vectors_attach: ") + hipGetErrorString(err));
-        if (int rc2 = tr_owner_nodes(*tables, S->stream)) { (void)hipStreamSynchronize(S->stream); delete S; return rc2; }
-        vec_free(*out);
-        *out = S;
-    } catch (const std::bad_alloc &) { return set_error(UGP_ERR_NOMEM, "out of host memory"); }
-    return UGP_OK;
+    std::vector<uint8_t> spar;
+    return query_attach(
+        "ugp_vectors_attach", tree, dfs2bfs, bfs2dfs, device, 31, tables, out,
+        [&](const DfsTables &T) {
+            if (T.m && !tree->mut_par)
+                return set_error(UGP_ERR_INVALID, "ugp_vectors_attach needs mut_par: the node's own entries report the parent allele as stored");
+            spar.reserve(T.m);
+            for (uint32_t b : dfs2bfs)
+                for (uint64_t k = tree->mut_off[b]; k < tree->mut_off[b + 1]; k++) {
+                    if (tree->mut_nuc[k] > 15 || tree->mut_ref[k] > 15 || tree->mut_par[k] > 15)
+                        return set_error(UGP_ERR_UNSUPPORTED, "ugp_vectors_attach: an allele of entry " + std::to_string(k) + " is not a 4-bit code");
+                    spar.push_back(tree->mut_par[k]);
+                }
+            return (int)UGP_OK;
+        },
+        [&](VecState *S) {
+            hipError_t err = S->spar.upload(spar, S->stream);
+            if (err == hipSuccess) err = hipStreamSynchronize(S->stream);   // spar is read until here
+            if (int rc = hip_rc("ugp_vectors_attach", err)) return rc;
+            return tr_owner_nodes(*tables, S->stream);
+        });
 }
 
 int vec_check(VecState *S, const char *who, const ugp_queries *q, uint64_t n_pairs, const uint32_t *sample, const uint32_t *node) {
-    if (!S) return set_error(UGP_ERR_INVALID, std::string(who) + ": no vector tables: call ugp_vectors_attach first");
+    if (int rc = query_ready(S, who, "vectors")) return rc;
     if (!q || (n_pairs && !node)) return set_error(UGP_ERR_INVALID, "null argument");
     if (n_pairs >= (1ull << 32)) return set_error(UGP_ERR_INVALID, std::string(who) + ": more than 2^32 pairs");
     const uint32_t N = S->T->n;
@@ -424,15 +403,8 @@ int vec_run(VecState *S, const ugp_queries *q, const int32_t *d_pos, const uint8
         hipStream_t st = S->stream;
         const uint64_t chunk = chunk_pairs ? chunk_pairs : kDefaultPairs;
         const std::vector<uint32_t> &b2d = S->T->bfs2dfs;
-        Events ev;
-        if (timing) { UGP_HIP_TRY(hipEventCreate(&ev.a)); UGP_HIP_TRY(hipEventCreate(&ev.b)); }
-        auto lap = [&](double *acc) -> hipError_t {   // the time between the two events, once the second has passed
-            float t = 0;
-            hipError_t e = hipEventSynchronize(ev.b);
-            if (e == hipSuccess) e = hipEventElapsedTime(&t, ev.a, ev.b);
-            *acc += t;
-            return e;
-        };
+        EventPair ev(st);
+        if (timing) UGP_HIP_TRY(ev.create());
         if (n_pairs) {
             const uint64_t most = std::min<uint64_t>(chunk, n_pairs);
             UGP_HIP_TRY(S->ent_off.upload((const u64 *)q->ent_off, q->n_queries + 1, st));   // read until the first synchronisation below
@@ -449,11 +421,11 @@ int vec_run(VecState *S, const ugp_queries *q, const int32_t *d_pos, const uint8
             for (uint32_t i = 0; i < nc; i++) { hs[i] = sample ? sample[c0 + i] : (uint32_t)(c0 + i); hn[i] = b2d[node[c0 + i]]; }
             UGP_HIP_TRY(S->ps.upload(hs, st));
             UGP_HIP_TRY(S->pn.upload(hn, st));
-            if (timing) UGP_HIP_TRY(hipEventRecord(ev.a, st));
+            if (timing) UGP_HIP_TRY(ev.start());
             k_vec_count<<<grid, kBlock, 0, st>>>(v, S->ps.p, S->pn.p, nc, S->info.p, S->n3.p);
             k_vec_scan<<<2, kBlock, 0, st>>>(S->info.p, nc, S->off_ex.p, S->off_im.p);
             UGP_HIP_TRY(hipGetLastError());
-            if (timing) { UGP_HIP_TRY(hipEventRecord(ev.b, st)); UGP_HIP_TRY(lap(&kernel_ms[0])); }
+            if (timing) UGP_HIP_TRY(ev.lap(&kernel_ms[0]));
             const size_t firstoff = timing ? nc : 0;   // the bench hook needs the totals only
             hox.resize((size_t)nc + 1 - firstoff); hoi.resize(hox.size());
             if (!timing) UGP_HIP_TRY(hipMemcpyAsync(info + c0, S->info.p, nc * sizeof(ugp_vec_info), hipMemcpyDeviceToHost, st));
@@ -467,11 +439,11 @@ int vec_run(VecState *S, const ugp_queries *q, const int32_t *d_pos, const uint8
             const uint64_t take_im = timing || base_im >= im_cap ? 0 : std::min<uint64_t>(ti, im_cap - base_im);
             if ((tx || ti) && (timing || take_ex || take_im)) {
                 UGP_HIP_TRY(S->ex.alloc(tx)); UGP_HIP_TRY(S->tmp.alloc(tx)); UGP_HIP_TRY(S->im.alloc(ti));
-                if (timing) UGP_HIP_TRY(hipEventRecord(ev.a, st));
+                if (timing) UGP_HIP_TRY(ev.start());
                 k_vec_fill<<<grid, kBlock, 0, st>>>(v, S->ps.p, S->pn.p, nc, S->off_ex.p, S->off_im.p, S->ex.p, S->tmp.p, S->im.p);
                 if (tx) k_vec_order<<<blocks_for(tx), kBlock, 0, st>>>(S->info.p, S->n3.p, S->off_ex.p, nc, tx, S->tmp.p, S->ex.p);
                 UGP_HIP_TRY(hipGetLastError());
-                if (timing) { UGP_HIP_TRY(hipEventRecord(ev.b, st)); UGP_HIP_TRY(lap(&kernel_ms[1])); }
+                if (timing) UGP_HIP_TRY(ev.lap(&kernel_ms[1]));
                 if (take_ex) UGP_HIP_TRY(hipMemcpyAsync(excess + base_ex, S->ex.p, take_ex * sizeof(ugp_vec_entry), hipMemcpyDeviceToHost, st));
                 if (take_im) UGP_HIP_TRY(hipMemcpyAsync(imputed + base_im, S->im.p, take_im * sizeof(ugp_vec_entry), hipMemcpyDeviceToHost, st));
                 UGP_HIP_TRY(hipStreamSynchronize(st));
